@@ -22,8 +22,17 @@ overlap the next step's bulk; every step is rendered in full.  The serial
 frame latency is reported beside it (roofline.kernel_ms_serial).
 
 value = rays of all frames of all ranks / (max over ranks of the timed wall
-time), timed between barrier + synchronize on both sides.  `sustained`
-repeats the measurement over >= --sustain seconds, three times (median).
+time), timed between barrier + synchronize on both sides; ms_per_step = that
+wall time / --steps.
+
+A plain run sets up (tree, pool, launch plan, frame buffers), issues the
+--warmup steps, times the --steps steps, writes the last step's frames when
+--dump-outputs DIR is given (dump_outputs) and prints the result line.
+Everything below is measured or checked only with --full, after the headline
+window, and is null in a plain run's line.
+
+`sustained` repeats the measurement over >= --sustain seconds, three times
+(median).
 
 The same line carries config 5 (BASELINE configs[4]) under "bounce": the same
 frames with one mirrored secondary ray per hit pixel, in-block wavefront
@@ -246,6 +255,32 @@ def frame_size(n_gpus: int, width: int | None, height: int | None, scaling: str)
         return 3840, 2160                                  # configs[3]
     s = math.sqrt(n_gpus)
     return int(round(1920 * s)), int(round(1080 * s))
+
+
+DUMP_MAX_BYTES = 32 * 2**20
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, frames):
+    """--dump-outputs: the RGBA8 frames of the last timed step (views x H x W
+    packed pixels, as the timed path leaves them for its caller) written to
+    out_dir/frames.npy as float32 channel values 0..255, shape (views, H, W, 4):
+    each pixel's four bytes in memory order.  A frame set whose float32 form
+    would pass DUMP_MAX_BYTES is written as
+    a fixed sample instead: shape (n, 4), the pixels at the sorted indices
+    (into the flattened views x H x W array) that numpy's default_rng(DUMP_SEED)
+    draws without replacement -- the same pixels in every run of one frame size.
+    The scene, the cameras and the launch options are fixed, so two builds
+    given the same arguments write arrays that can be compared value for value."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    px = np.ascontiguousarray(frames).view(np.uint8).reshape(*frames.shape, 4)
+    n_px = px.size // 4
+    keep = DUMP_MAX_BYTES // 16
+    if n_px > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_px, size=keep, replace=False))
+        px = px.reshape(n_px, 4)[idx]
+    np.save(out_dir / "frames.npy", px.astype(np.float32))
 
 
 def coll(fn, t, *args, **kw):
@@ -579,16 +614,18 @@ def group_bench(a):
         frames = [g.download(r) for r in range(n)]
         rays = W * H * len(cams)
         sustained = None
-        if a.sustain > 0:
+        if a.full and a.sustain > 0:
             n_s = max(a.steps, int(math.ceil(a.sustain / (el / a.steps))))
             vals = [rays * n_s / window(n_s) / 1e6 for _ in range(3)]
             sustained = {"value": round(statistics.median(vals), 2), "unit": "Mrays/s", "steps_per_run": n_s,
                          "values": [round(v, 2) for v in vals]}
     finally:
         g.close()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, np.asarray(frames[0]))
     parity = None
     wd.enter("cpu leg", DEADLINES["cpu leg"])
-    if not a.no_parity:
+    if a.full and not a.no_parity:
         _, parity = cpu_leg(tree.nodes, tree.root, a.depth, W, H, frames[0], None, time_it=False, budget_s=0)
         parity["devices_equal_rank0"] = all(np.array_equal(f, frames[0]) for f in frames)
         if not parity["devices_equal_rank0"]:
@@ -597,7 +634,7 @@ def group_bench(a):
         "metric": METRIC,
         "value": round(rays * a.steps / el / 1e6, 2), "unit": "Mrays/s", "n_gpus": n, "steps": a.steps,
         "warmup": a.warmup, "ms_per_step": round(el / a.steps * 1e3, 4), "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+        "scaling": "strong", "vs_baseline": None, "dtype": "f32", "full": a.full,
         "data": "synthetic: the reference's terrain fill at depth %d, built on the GPU (och_build_terrain)" % a.depth,
         "config": {"workload": (f"{W}x{H}, two views per step, depth-{a.depth} DAG over {n} MI355X from one process "
                                 "(och_frame_group_*)"),
@@ -812,6 +849,15 @@ def main():
                     help="N > 1: skip the checksum check of one exchanged frame before the timed window")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline window, also run every side measurement and check (sustained runs, "
+                         "cull-off / split / moving-camera / config-5 windows, trace-batch paths, roofline, the other "
+                         "configs, the exchange check and scaling_base at N > 1, the CPU baseline and the oracle "
+                         "parity check); each has its own --no-* switch.  Without it the run sets up, warms up, times "
+                         "the --steps steps and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the RGBA8 frames of the last timed step (what a caller of the timed path receives) "
+                         "to DIR/frames.npy as float32 channel values; see dump_outputs")
     ap.add_argument("--warm-issue", choices=("native", "step"), default="native",
                     help="how the W warmup steps are issued: as the window issues its steps (default), "
                          "or one C-ABI render call per step")
@@ -907,6 +953,8 @@ def main():
                     help="GPU_MAX_HW_QUEUES for this process (set before HIP starts); default the "
                          "environment's (4 on the box), 8 at N >= 8")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     # Frames in flight and hardware queues by world size (tools/proxy_rank.py,
     # every shard, profiles/r03/proxy/r03z*): at N = 8 a rank's launches are half
@@ -1062,36 +1110,38 @@ def main():
 
     # PUSH counts of this rank's rays (for the algorithmic byte count): trace
     # the rank's own rows once with counting on; not part of the timed region.
-    rows = torch.from_numpy(slice_row_map(H, a.row_chunk, world, rank, deal))
+    # With the trace-only paths below, a side measurement (--full).
     push_total, walk_push, culled, hits_total, rays_rank = 0, 0, 0, 0, 0
-    dirs = torch.empty(W * H * 3, dtype=torch.float32, device=dev)
-    o_t = torch.tensor(ORIGIN, dtype=torch.float32, device=dev)
     n_px = W * H
-    hd = torch.empty(n_px, dtype=torch.int32, device=dev)
-    hv = torch.empty(n_px, dtype=torch.int32, device=dev)
-    ht = torch.empty(n_px, dtype=torch.float32, device=dev)
-    hp = torch.empty(n_px, dtype=torch.int32, device=dev)
-    mine = rows[rows >= 0].to(dev).long()
-    cull = pool.get_option("cull")
-    for cam in cams:
-        pool.raygen_dev(cam, dirs)
-        pool.set_option("cull", 0)             # the reference's PUSH counts
-        pool.trace_batch_dev(o_t, dirs, hd, hv, ht, hp)
-        push_total += int(hp.view(H, W)[mine].sum().item())
-        hits_total += int((hd.view(H, W)[mine] < 6).sum().item())
-        rays_rank += int(mine.numel()) * W
-        if cull:                               # the PUSHes the timed (culled) launches walk
-            pool.set_option("cull", 2)
+    if a.full:
+        rows = torch.from_numpy(slice_row_map(H, a.row_chunk, world, rank, deal))
+        dirs = torch.empty(W * H * 3, dtype=torch.float32, device=dev)
+        o_t = torch.tensor(ORIGIN, dtype=torch.float32, device=dev)
+        hd = torch.empty(n_px, dtype=torch.int32, device=dev)
+        hv = torch.empty(n_px, dtype=torch.int32, device=dev)
+        ht = torch.empty(n_px, dtype=torch.float32, device=dev)
+        hp = torch.empty(n_px, dtype=torch.int32, device=dev)
+        mine = rows[rows >= 0].to(dev).long()
+        cull = pool.get_option("cull")
+        for cam in cams:
+            pool.raygen_dev(cam, dirs)
+            pool.set_option("cull", 0)             # the reference's PUSH counts
             pool.trace_batch_dev(o_t, dirs, hd, hv, ht, hp)
-            walked = hp.view(H, W)[mine]
-            walk_push += int(walked.sum().item())
-            culled += int((walked == 0).sum().item())
-    if not cull:
-        walk_push = push_total
-    pool.set_option("cull", cull)
+            push_total += int(hp.view(H, W)[mine].sum().item())
+            hits_total += int((hd.view(H, W)[mine] < 6).sum().item())
+            rays_rank += int(mine.numel()) * W
+            if cull:                               # the PUSHes the timed (culled) launches walk
+                pool.set_option("cull", 2)
+                pool.trace_batch_dev(o_t, dirs, hd, hv, ht, hp)
+                walked = hp.view(H, W)[mine]
+                walk_push += int(walked.sum().item())
+                culled += int((walked == 0).sum().item())
+        if not cull:
+            walk_push = push_total
+        pool.set_option("cull", cull)
     # trace-only throughput over resident rays (the och_gpu_trace_batch_dev path), N=1 only
     trace_only = None
-    if world == 1:
+    if a.full and world == 1:
         tms = []
         for cam in cams:
             pool.raygen_dev(cam, dirs)
@@ -1186,7 +1236,8 @@ def main():
                                    "rays_per_launch": 2 * n_px,
                                    "path": "och_gpu_trace_batch_dev over both views' rays (row-major) in one launch"}
         del both, bd, bv, bt
-    del hd, hv, ht, hp, dirs
+    if a.full:
+        del hd, hv, ht, hp, dirs
 
     # timing events for every step of a window, created once, outside the timed region
     ev_pool = [(make_event(a.step_events), make_event(a.step_events)) for _ in range(max(a.steps, 1))]
@@ -1434,13 +1485,13 @@ def main():
         rank_s.append([float(el.item())])
         return float(el.item())
 
-    # N > 1: one frame through the exchange the window will time, checked before
-    # anything is timed -- every rank's checksum of its own slice against the
+    # N > 1 (--full): one frame through the exchange the window will time, checked
+    # before anything is timed -- every rank's checksum of its own slice against the
     # receiving ranks' copies.  A library-communicator exchange that delivers
     # wrong bytes falls back to torch.distributed's all-gather (checked again);
     # a second mismatch ends the run with a non-zero status.
     exchange_check = None
-    if world > 1 and not a.no_exchange_check:
+    if a.full and world > 1 and not a.no_exchange_check:
         def one_frame():
             if sharded_steps is not None:
                 prepare_sharded(1, False, None)()
@@ -1477,7 +1528,7 @@ def main():
             step(0, lat if k >= max(a.warmup, 1) else None)
             torch.cuda.synchronize()
         return float(np.median([x.elapsed_time(y) for x, y in lat]))
-    latency_ms = lone_latency()
+    latency_ms = lone_latency() if a.full else None
     if trace_only is not None:
         # per ray against a lone render launch (both views, raygen + trace + shade)
         lone = latency_ms / (W * H * len(cams))
@@ -1493,7 +1544,9 @@ def main():
     ev = ev or []
     per_rank_ms = [round(t / a.steps * 1e3, 4) for t in rank_s[-1]]
     last = (a.steps - 1) % len(sfs)
-    frames_host = sfs[last].frames.cpu().numpy() if rank == 0 else None
+    frames_host = sfs[last].frames.cpu().numpy() if rank == 0 and (a.full or a.dump_outputs) else None
+    if frames_host is not None and a.dump_outputs:
+        dump_outputs(a.dump_outputs, frames_host)
     pool.set_stream(stream)
     kms = np.array([x.elapsed_time(y) for x, y in ev])
     # the window's GPU span: the first launch's start to the last launch's end
@@ -1514,7 +1567,7 @@ def main():
 
     # Sustained: >= a.sustain seconds of steps, three runs, median.
     sustained = None
-    if a.sustain > 0:
+    if a.full and a.sustain > 0:
         n_s = max(a.steps, int(math.ceil(a.sustain / (elapsed / a.steps))))
         runs = [timed(n_s, stage="window (sustained)") for _ in range(3)]
         vals = [W * H * len(cams) * n_s / r / 1e6 for r in runs]
@@ -1526,7 +1579,7 @@ def main():
     # ncclRecv) -- beside it, on the same frames, deal and streams, after its
     # own one-frame check.  Not the line's value: configs[3] names the all-gather.
     exchange_gather = None
-    if world > 1 and sharded_steps is not None and exch_mode == "all_gather" and a.shade == "display":
+    if a.full and world > 1 and sharded_steps is not None and exch_mode == "all_gather" and a.shade == "display":
         arm_steps = {False: ShardedSteps(sfs, streams, comm, cams, exchange="gather")}
         wd.enter("exchange check (gather)", DEADLINES["exchange check"])
         prepare_sharded(1, False, None)()
@@ -1551,7 +1604,7 @@ def main():
     # The same window with the occupied-box cull off (every ray walks): the
     # traversal speed like-for-like with round 1 and with the CPU baseline.
     cull_off = None
-    if not a.no_cull_off and pool.get_option("cull"):
+    if a.full and not a.no_cull_off and pool.get_option("cull"):
         c_prev = pool.get_option("cull")
         pool.set_option("cull", 0)
         if pool.get_option("tile_order") >= 2:
@@ -1570,7 +1623,7 @@ def main():
     # (the split waves walk the coarse levels once per lane).  Same cameras,
     # the same window; its last frames must equal the headline's.
     split_arm = None
-    if world == 1 and direct and not a.no_split_arm:
+    if a.full and world == 1 and direct and not a.no_split_arm:
         # Interleaved, in the same state of the GPU: by now it has rendered for
         # seconds, and windows this late run faster than the headline's (the
         # warm-up ramp) -- compare the arms here, not with the
@@ -1618,7 +1671,7 @@ def main():
     # once from the first step's (as an interactive app would plan from an
     # earlier frame), and the same window runs in natural order for comparison.
     moving, moving_frames = None, None
-    if direct and a.moving_steps > 0:
+    if a.full and direct and a.moving_steps > 0:
         from octree_ray_tracing_amd._lib import Camera, load as load_lib
         lib = load_lib()
         n_mv = a.moving_steps
@@ -1671,7 +1724,7 @@ def main():
     # pipelining and timing discipline.  Rays = primary + secondary.
     bounce = None
     bounce_host = None
-    if not a.no_bounce:
+    if a.full and not a.no_bounce:
         def bounce_run(n):
             # warmup as for the primary line, then the median of three timed runs
             # (one 20-step window alone swings by +-10 %)
@@ -1729,82 +1782,85 @@ def main():
     # pipelined step, against the chip's issue peak.  HBM: SURVEY §8(d)'s
     # canonical algorithmic bytes, 24 B in + 12 B out + 4 B per PUSH per ray.
     step_s = elapsed / a.steps
-    k_avg_ms = float(kms.mean()) if kms.size else latency_ms    # --no-step-events: the lone launch instead
-    # SURVEY §8(d)'s canonical count takes the reference's PUSHes of every ray
-    # (the walk without the cull); the walked figure counts what the timed,
-    # culled launch walks (proven misses read nothing).  Both per launch.
-    canon_bytes = 36 * rays_rank + 4 * push_total
-    walked_bytes = 36 * rays_rank + 4 * walk_push
+    roof = None
+    if a.full:
+        k_avg_ms = float(kms.mean()) if kms.size else latency_ms    # --no-step-events: the lone launch instead
+        # SURVEY §8(d)'s canonical count takes the reference's PUSHes of every ray
+        # (the walk without the cull); the walked figure counts what the timed,
+        # culled launch walks (proven misses read nothing).  Both per launch.
+        canon_bytes = 36 * rays_rank + 4 * push_total
+        walked_bytes = 36 * rays_rank + 4 * walk_push
 
-    def gbs(nbytes, ms):
-        return round(nbytes / (ms * 1e-3) / 1e9, 2) if ms else None
+        def gbs(nbytes, ms):
+            return round(nbytes / (ms * 1e-3) / 1e9, 2) if ms else None
 
-    hbm = {"bound": "hbm", "bytes_per_launch": int(canon_bytes),
-           "bytes_model": "SURVEY 8(d) canonical: 24 B ray in + 12 B hit record out per ray + 4 B per PUSH of the "
-                          "reference's walk (push_per_ray: every ray walks, as sse_trace does)",
-           "achieved": gbs(canon_bytes, k_avg_ms), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-           "frac": round(canon_bytes / (k_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-           "achieved_per_step": gbs(canon_bytes, step_s * 1e3),
-           "frac_per_step": round(canon_bytes / step_s / 1e9 / HBM_PEAK_GBS, 5),
-           "walked_bytes_per_launch": int(walked_bytes),
-           "walked_bytes_model": "the same with the PUSHes the timed launch walks (walked_push_per_ray: rays the "
-                                 "occupied-box cull proves to miss walk none)",
-           "walked_achieved": gbs(walked_bytes, k_avg_ms),
-           "walked_frac_per_step": round(walked_bytes / step_s / 1e9 / HBM_PEAK_GBS, 5),
-           "note": "achieved / frac: per launch, over the launch's mean duration in the timed window (HIP events "
-                   "recorded by its dispatch; three frames overlap, so a launch lasts longer than a step); "
-                   "*_per_step: over the pipelined step time"}
-    rgba_launch = direct or not indexed
-    pmc, pmc_src = load_pmc("k_render_rgba" if rgba_launch else "k_render", f"d{a.depth}_{W}x{H}_n{world}")
-    roof = {"kernel": f"k_trace_grid<CameraSource,{'FrameSink' if rgba_launch else 'CodeSink'}> (2 views per launch)",
-            "kernel_ms": round(k_avg_ms, 4), "kernel_ms_serial": round(latency_ms, 4),
-            "host_issue_ms": host_issue_ms,
-            "window_gpu_span_ms": None if gpu_span_ms is None else round(gpu_span_ms, 4),
-            "window_overhead_ms": None if gpu_span_ms is None else round(elapsed * 1e3 - gpu_span_ms, 4),
-            "host_issue_ms_per_step": round(host_issue_ms / max(a.steps, 1), 5),
-            "ms_per_step": round(step_s * 1e3, 4), "frames_in_flight": len(streams),
-            "push_per_ray": round(push_total / rays_rank, 3), "rays_per_launch": rays_rank,
-            "walked_push_per_ray": round(walk_push / rays_rank, 3), "culled_frac": round(culled / rays_rank, 4),
-            "traffic": None if pmc is None else pmc.get("hbm_bytes_per_launch"),
-            "traffic_note": "PMC 2*FETCH_SIZE + WRITE_SIZE per render launch (MI355X_MICROARCH.md HBM): bytes "
-                            "leaving L2, Infinity-Cache hits included", "pmc_source": pmc_src, "hbm": hbm,
-            "window_profile": load_window()}
-    if pmc and "SQ_INSTS_VALU" in pmc:
-        insts = float(pmc["SQ_INSTS_VALU"])
-        ach = insts / step_s / 1e9
-        # the PMC passes' own launch duration: rocprofv3 serialises the
-        # dispatches of a counter pass, so this is one launch alone
-        prof_ms = float(pmc.get("pmc_mean_ms") or 0.0)
-        if prof_ms:
-            hbm["achieved_pmc_launch"] = gbs(canon_bytes, prof_ms)
-            hbm["frac_pmc_launch"] = round(canon_bytes / (prof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-            hbm["walked_frac_pmc_launch"] = round(walked_bytes / (prof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
-        roof.update({"bound": "valu-issue", "achieved": round(ach, 1), "peak": VALU_PEAK_GINST_S,
-                     "unit": "G VALU wave-instructions/s", "frac": round(ach / VALU_PEAK_GINST_S, 4),
-                     "valu_insts_per_launch": int(insts), "valu_insts_per_wave": pmc.get("valu_insts_per_wave"),
-                     "valu_lane_utilization": pmc.get("valu_lane_utilization"),
-                     "achieved_per_launch": round(insts / (k_avg_ms * 1e-3) / 1e9, 1),
-                     # per launch, from the profile alone: SQ_INSTS_VALU / the PMC passes' mean (serialised)
-                     # launch duration, both in profiles/pmc_summary.json
-                     "frac_profile": round(insts / (prof_ms * 1e-3) / 1e9 / VALU_PEAK_GINST_S, 4) if prof_ms else None,
-                     "profile_mean_ms": prof_ms or None,
-                     "profile_mean_ms_basis": "pmc_mean_ms: the PMC passes' mean launch duration (dispatches "
-                                              "serialised by the profiler)",
-                     "frac_serial_launch": round(insts / (latency_ms * 1e-3) / 1e9 / VALU_PEAK_GINST_S, 4),
-                     "effective_clock_ghz": pmc.get("effective_clock_ghz"),
-                     "note": "frac = issue rate over the pipelined step (three frames overlap, so a launch lasts "
-                             "longer than a step: window_profile shows the overlap); frac_profile = the same "
-                             "instructions over one serialised launch under the profiler (pmc_mean_ms); "
-                             "frac_serial_launch = over kernel_ms_serial, one launch on an idle GPU timed here; "
-                             "the DAG is L2/MALL-resident, so HBM is far from binding (see hbm)"})
-    else:
-        roof.update({k: hbm[k] for k in ("bound", "achieved", "peak", "unit", "frac")})
+        hbm = {"bound": "hbm", "bytes_per_launch": int(canon_bytes),
+               "bytes_model": "SURVEY 8(d) canonical: 24 B ray in + 12 B hit record out per ray + 4 B per PUSH of the "
+                              "reference's walk (push_per_ray: every ray walks, as sse_trace does)",
+               "achieved": gbs(canon_bytes, k_avg_ms), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+               "frac": round(canon_bytes / (k_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+               "achieved_per_step": gbs(canon_bytes, step_s * 1e3),
+               "frac_per_step": round(canon_bytes / step_s / 1e9 / HBM_PEAK_GBS, 5),
+               "walked_bytes_per_launch": int(walked_bytes),
+               "walked_bytes_model": "the same with the PUSHes the timed launch walks (walked_push_per_ray: rays the "
+                                     "occupied-box cull proves to miss walk none)",
+               "walked_achieved": gbs(walked_bytes, k_avg_ms),
+               "walked_frac_per_step": round(walked_bytes / step_s / 1e9 / HBM_PEAK_GBS, 5),
+               "note": "achieved / frac: per launch, over the launch's mean duration in the timed window (HIP events "
+                       "recorded by its dispatch; three frames overlap, so a launch lasts longer than a step); "
+                       "*_per_step: over the pipelined step time"}
+        rgba_launch = direct or not indexed
+        pmc, pmc_src = load_pmc("k_render_rgba" if rgba_launch else "k_render", f"d{a.depth}_{W}x{H}_n{world}")
+        roof = {"kernel": f"k_trace_grid<CameraSource,{'FrameSink' if rgba_launch else 'CodeSink'}> (2 views per launch)",
+                "kernel_ms": round(k_avg_ms, 4), "kernel_ms_serial": round(latency_ms, 4),
+                "host_issue_ms": host_issue_ms,
+                "window_gpu_span_ms": None if gpu_span_ms is None else round(gpu_span_ms, 4),
+                "window_overhead_ms": None if gpu_span_ms is None else round(elapsed * 1e3 - gpu_span_ms, 4),
+                "host_issue_ms_per_step": round(host_issue_ms / max(a.steps, 1), 5),
+                "ms_per_step": round(step_s * 1e3, 4), "frames_in_flight": len(streams),
+                "push_per_ray": round(push_total / rays_rank, 3), "rays_per_launch": rays_rank,
+                "walked_push_per_ray": round(walk_push / rays_rank, 3), "culled_frac": round(culled / rays_rank, 4),
+                "traffic": None if pmc is None else pmc.get("hbm_bytes_per_launch"),
+                "traffic_note": "PMC 2*FETCH_SIZE + WRITE_SIZE per render launch: bytes leaving L2, Infinity-Cache "
+                                "hits included", "pmc_source": pmc_src, "hbm": hbm,
+                "window_profile": load_window()}
+        if pmc and "SQ_INSTS_VALU" in pmc:
+            insts = float(pmc["SQ_INSTS_VALU"])
+            ach = insts / step_s / 1e9
+            # the PMC passes' own launch duration: rocprofv3 serialises the
+            # dispatches of a counter pass, so this is one launch alone
+            prof_ms = float(pmc.get("pmc_mean_ms") or 0.0)
+            if prof_ms:
+                hbm["achieved_pmc_launch"] = gbs(canon_bytes, prof_ms)
+                hbm["frac_pmc_launch"] = round(canon_bytes / (prof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+                hbm["walked_frac_pmc_launch"] = round(walked_bytes / (prof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)
+            roof.update({"bound": "valu-issue", "achieved": round(ach, 1), "peak": VALU_PEAK_GINST_S,
+                         "unit": "G VALU wave-instructions/s", "frac": round(ach / VALU_PEAK_GINST_S, 4),
+                         "valu_insts_per_launch": int(insts), "valu_insts_per_wave": pmc.get("valu_insts_per_wave"),
+                         "valu_lane_utilization": pmc.get("valu_lane_utilization"),
+                         "achieved_per_launch": round(insts / (k_avg_ms * 1e-3) / 1e9, 1),
+                         # per launch, from the profile alone: SQ_INSTS_VALU / the PMC passes' mean (serialised)
+                         # launch duration, both in profiles/pmc_summary.json
+                         "frac_profile": (round(insts / (prof_ms * 1e-3) / 1e9 / VALU_PEAK_GINST_S, 4)
+                                          if prof_ms else None),
+                         "profile_mean_ms": prof_ms or None,
+                         "profile_mean_ms_basis": "pmc_mean_ms: the PMC passes' mean launch duration (dispatches "
+                                                  "serialised by the profiler)",
+                         "frac_serial_launch": round(insts / (latency_ms * 1e-3) / 1e9 / VALU_PEAK_GINST_S, 4),
+                         "effective_clock_ghz": pmc.get("effective_clock_ghz"),
+                         "note": "frac = issue rate over the pipelined step (three frames overlap, so a launch lasts "
+                                 "longer than a step: window_profile shows the overlap); frac_profile = the same "
+                                 "instructions over one serialised launch under the profiler (pmc_mean_ms); "
+                                 "frac_serial_launch = over kernel_ms_serial, one launch on an idle GPU timed here; "
+                                 "the DAG is L2/MALL-resident, so HBM is far from binding (see hbm)"})
+        else:
+            roof.update({k: hbm[k] for k in ("bound", "achieved", "peak", "unit", "frac")})
 
     # N > 1: the like-for-like one-GPU rate of this same frame (rank 0 alone,
     # the other ranks idle at a barrier), so a scaling curve compares frames
     # of one size: the driver's N = 1 line is configs[2]'s 1920x1080 frame.
     scaling_base = None
-    if world > 1 and not a.no_scaling_base:
+    if a.full and world > 1 and not a.no_scaling_base:
         wd.enter("scaling base", DEADLINES["scaling base"])
         drain()
         dist.barrier()
@@ -1818,7 +1874,7 @@ def main():
     # depth-8 och::octree (0-based pool) at 512x512, one trace batch of
     # resident rays, next to the CPU oracle on the same rays.
     others = None
-    if world == 1 and not a.no_other_configs:
+    if a.full and world == 1 and not a.no_other_configs:
         wd.enter("other configs", DEADLINES["other configs"])
         others = other_configs(a, dev, stream)
 
@@ -1826,7 +1882,7 @@ def main():
     # the other ranks go on to the teardown while rank 0 checks parity
     wd.enter("cpu leg" if rank == 0 else "teardown",
              DEADLINES["cpu leg"] + (0 if rank == 0 else DEADLINES["teardown"]))
-    if rank == 0 and not a.no_parity:
+    if a.full and rank == 0 and not a.no_parity:
         cpu, parity = cpu_leg(nodes, root, a.depth, W, H, frames_host, bounce_host,
                               time_it=world == 1 and not a.no_cpu_baseline, budget_s=a.cpu_budget,
                               moving=moving_frames)
@@ -1862,6 +1918,7 @@ def main():
             "scaling": "weak" if (world > 1 and a.scaling == "weak") else "strong",
             "vs_baseline": None,
             "dtype": "f32",
+            "full": a.full,                # False: the side measurements below were not run (null)
             "data": "synthetic: the reference's terrain fill (simplex heightmap + tunnels) at depth 12, voxelised, "
                     "hash-consed and renumbered on the GPU (och_build_terrain)",
             "config": {"workload": workload,
@@ -1904,7 +1961,7 @@ def main():
             "cull_off": cull_off,
             **({"split": split_arm} if split_arm else {}),
             **({"moving_camera": moving} if moving else {}),
-            "walked_rays_per_s": round(value * (1 - culled / rays_rank), 2),
+            "walked_rays_per_s": round(value * (1 - culled / rays_rank), 2) if a.full else None,
             "walked_rays_note": "Mrays/s of the rays that walk the DAG (value x (1 - culled_frac)); the "
                                 "occupied-box cull ends the rest as proven misses",
             "per_rank_ms_per_step": per_rank_ms,

@@ -30,3 +30,23 @@ def test_committed_profiles_match_this_kernel_source():
     win = bench.load_window()
     assert win is not None and not win.get("stale")
     assert 0 < win["busy_union_ms_per_step"] <= win["ms_per_step_trace"] + 1e-9
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float32 channel values of the packed RGBA8 pixels, whole
+    when small; above the byte budget the same seeded sample in every call."""
+    import numpy as np
+    rng = np.random.default_rng(3)
+    frames = rng.integers(0, 2**32, (2, 9, 16), dtype=np.uint32)
+    bench.dump_outputs(tmp_path / "a", frames)
+    got = np.load(tmp_path / "a" / "frames.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 9, 16, 4)
+    assert np.array_equal(got.astype(np.uint8).reshape(2, 9, 64).view(np.uint32), frames)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16 * 100)           # room for 100 pixels of the 288
+    bench.dump_outputs(tmp_path / "b", frames)
+    bench.dump_outputs(tmp_path / "c", frames.view(np.int32))        # the torch frames are int32
+    b, c = np.load(tmp_path / "b" / "frames.npy"), np.load(tmp_path / "c" / "frames.npy")
+    assert b.shape == (100, 4) and b.dtype == np.float32 and np.array_equal(b, c)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(288, size=100, replace=False))
+    assert np.array_equal(b, got.reshape(288, 4)[idx])
+    assert bench.DUMP_MAX_BYTES <= 64 * 10**6

@@ -18,7 +18,7 @@ from pathlib import Path
 import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
-SMALL = ["--depth", "10", "--steps", "5", "--warmup", "2", "--sustain", "0", "--no-bounce", "--no-cull-off",
+SMALL = ["--full", "--depth", "10", "--steps", "5", "--warmup", "2", "--sustain", "0", "--no-bounce", "--no-cull-off",
          "--no-cpu-baseline", "--no-other-configs", "--moving-steps", "0"]
 
 
@@ -59,3 +59,35 @@ def test_bench_two_gloo_ranks_exchange_check_and_scaling_base():
     assert line["parity"]["mismatches"] == 0 and line["parity"]["pixels"] == 2 * 960 * 544
     base = line["scaling_base"]
     assert base["frames_equal_sharded"] is True and base["value"] > 0 and base["frames_in_flight"] == 3
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_last_frames(tmp_path, ort, O):
+    """A plain run (no --full): the headline fields, every side measurement
+    null, and --dump-outputs writes the last timed step's frames -- here small
+    enough to be written whole, and equal to the oracle's."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    W, H, depth = 256, 144, 8
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--depth", str(depth), "--width", str(W),
+                        "--height", str(H), "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = _line(p.stdout)
+    assert line["full"] is False and line["steps"] == 4 and line["warmup"] == 1
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "Mrays/s"
+    # value = the steps' rays / their wall time; ms_per_step is that time, rounded to 1e-4 ms
+    assert abs(line["value"] - 2 * W * H / line["ms_per_step"] / 1e3) <= line["value"] * (1e-4 / line["ms_per_step"] + 1e-3)
+    for k in ("roofline", "cpu_baseline", "parity", "sustained", "cull_off", "trace_batch", "bounce", "other_configs"):
+        assert line[k] is None, k
+    assert [f.name for f in tmp_path.iterdir()] == ["frames.npy"]
+    got = np.load(tmp_path / "frames.npy")
+    assert got.dtype == np.float32 and got.shape == (2, H, W, 4)
+    tree = ort.build_terrain(depth)
+    ref_pool, rcp = O.OraclePool(tree.nodes, tree.root, depth, 1), O.Rcp(None)
+    pal = ort.VoxelData().get_colours()
+    for v, pitch in enumerate(bench.PITCHES):
+        r = O.trace_batch(ref_pool, rcp, np.array(bench.ORIGIN, np.float32), O.raygen(bench.YAW, pitch, bench.FOV, W, H))
+        want = O.shade_fast(r["dir"], r["voxel"], pal).reshape(H, W)
+        assert np.array_equal(got[v].astype(np.uint8).reshape(H, W * 4).view(np.uint32), want), f"view {v}"

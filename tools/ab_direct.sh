@@ -3,7 +3,7 @@
 set -o pipefail
 O=${O:-gpurun_out/ab_direct}; mkdir -p $O
 export OCH_TREE_CACHE=/tmp/och_tree_d12.npz
-ARGS="--no-cpu-baseline --no-parity --no-other-configs --no-bounce --no-cull-off --sustain 1"
+ARGS="--full --no-cpu-baseline --no-parity --no-other-configs --no-bounce --no-cull-off --sustain 1"
 for r in 1 2 3; do
   timeout -k 10 200 python -u bench.py $ARGS > $O/direct_$r.json 2>> $O/err.log || exit 1
   timeout -k 10 200 python -u bench.py $ARGS --no-direct > $O/codes_$r.json 2>> $O/err.log || exit 2

@@ -3,6 +3,8 @@
 # round, every run a fresh bench.py process (HIP maps streams to hardware queues
 # in creation order, so arms never share a process).
 #   bash tools/ab_libs.sh TAG ROUNDS "BENCH ARGS" ARM [ARM ...]
+# BENCH ARGS: with --full for the sustained, lone-launch, parity and config-5
+# columns of the summary (a plain bench run prints None there).
 # ARM is LABEL:LIB[:EXTRA BENCH ARGS], LIB a build_variants/liboch_gpu_LIB.so name
 # or "default" (the in-tree library).  Outputs gpurun_out/TAG/bench_LABELr.json (r = round),
 # and a one-line summary per run on stdout.  The first failing run ends it.

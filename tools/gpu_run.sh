@@ -11,6 +11,8 @@
 #   pytest=PATHS            these test files / node ids         -> pytest_<i>.log
 #   smoke                   __graft_entry__.smoke()             -> smoke.log
 #   bench[:LABEL]=ARGS      python bench.py ARGS                -> bench_LABEL.json / .err
+#                           (put --full in ARGS for anything beyond the headline window: sustained,
+#                           roofline, config 5, parity, ...; a plain run leaves them null)
 #   torchrun1[:LABEL]=ARGS  bench.py under torch.distributed.run, one rank (the driver's N > 1 launch form)
 #   nccl_host               tools/nccl_host_cost.py, one RCCL rank -> nccl_host.json
 #   profile                 tools/profile.sh TAG (PMC passes + window trace)
@@ -27,7 +29,7 @@
 #   pmcpy:LABEL=COUNTERS@SCRIPT ARGS   the same pass over python -u tools/SCRIPT ARGS, every dispatch
 #                           summarised (no window) -> pmc_LABEL.json
 # Example:
-#   bash tools/gpu_run.sh r04a pytest=tests/test_gpu_comm.py "bench:sharded=--sharded --no-cpu-baseline" nccl_host
+#   bash tools/gpu_run.sh r04a pytest=tests/test_gpu_comm.py "bench:sharded=--full --sharded --no-cpu-baseline" nccl_host
 set -o pipefail
 TAG=${1:?tag}; shift
 O=gpurun_out/$TAG

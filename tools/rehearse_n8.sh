@@ -11,6 +11,6 @@
 set -o pipefail
 O=gpurun_out/rehearse_n8; mkdir -p $O
 OCH_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-    --master-addr 127.0.0.1 --master-port 29557 bench.py --gpus 8 --steps 5 --warmup 2 --no-cpu-baseline --sustain 0.3 \
+    --master-addr 127.0.0.1 --master-port 29557 bench.py --gpus 8 --full --steps 5 --warmup 2 --no-cpu-baseline --sustain 0.3 \
     --hw-queues 2 "$@" > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
 cut -c1-600 $O/bench.json

@@ -7,7 +7,7 @@
 set -o pipefail
 out=${1:?outdir}; rounds=${2:-2}; arms=${3:-"0 50"}; worlds=${4:-"1 8"}
 mkdir -p "$out"
-BA="--steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-bounce --moving-steps 0 --no-cull-off"
+BA="--full --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline --no-bounce --moving-steps 0 --no-cull-off"
 for r in $(seq "$rounds"); do
   for t in $arms; do
     opt="--opt split=0"; [[ "$t" != 0 ]] && opt="--opt split=$t --opt split_segs=4 --opt split_level=6"
