@@ -12,6 +12,7 @@
 #include <mutex>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "och_internal.h"
@@ -129,6 +130,60 @@ const HostRcp &host_rcp()
     return cap;
 }
 
+// A device buffer that only grows.  A reallocation that fails leaves it empty,
+// so the pointer never names freed memory.
+template <class T>
+struct DevBuf {
+    T *d = nullptr;
+    size_t n = 0;                   // elements allocated
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { (void)release(); }
+    hipError_t release()
+    {
+        n = 0;
+        return d ? hipFree(std::exchange(d, nullptr)) : hipSuccess;
+    }
+    void swap(DevBuf &o) { std::swap(d, o.d); std::swap(n, o.n); }
+    hipError_t reserve(size_t want)
+    {
+        if (want <= n) return hipSuccess;
+        hipError_t e = release();
+        if (e == hipSuccess) e = hipMalloc(&d, want * sizeof(T));
+        if (e == hipSuccess) n = want;
+        return e;
+    }
+    hipError_t upload(const std::vector<T> &v)
+    {
+        const hipError_t e = reserve(v.size());
+        return e != hipSuccess ? e : hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    }
+};
+
+// One cost-planned launch order (och_gpu_plan_views, och_gpu_plan_batch_tiled)
+// and the launch it was planned for (frame_key, batch_key).
+struct LaunchPlan {
+    DevBuf<uint32_t> order;         // OCH_OPT_TILE_ORDER = 2
+    DevBuf<uint32_t> order_xcd;     // OCH_OPT_TILE_ORDER = 3: grouped per XCD
+    uint32_t blocks = 0;            // entries of the current plan (its launch's grid)
+    int64_t key[9] = {};
+    // no plan until a new one is in place: later launches run in natural order
+    void invalidate() { key[0] = -1; }
+    bool matches(const int64_t k[9]) const { return order.d && std::memcmp(k, key, sizeof key) == 0; }
+};
+
+// The primary plan's split form (OCH_OPT_SPLIT, plan_split): the heavy tiles'
+// split waves first, then the plan's other workgroups, and the waves' task
+// rows; valid with plans[0]'s key while params matches the options it was
+// made with
+struct SplitPlan {
+    DevBuf<uint32_t> order, tasks;
+    uint32_t n = 0, extra = 0, tiles = 0;
+    int params[3] = {0, 0, 0};      // threshold, segments, level
+    void invalidate() { n = extra = tiles = params[0] = params[1] = params[2] = 0; }
+};
+
 }  // namespace
 
 // ------------------------------------------------------------ pool object
@@ -182,33 +237,23 @@ struct och_gpu_pool {
     bool box_any = false;
     int32_t box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
     // host-call staging
-    void *d_scratch = nullptr;
-    size_t scratch_bytes = 0;
+    DevBuf<char> scratch;
     // editor flush staging (och::pool_scatter_slots): pinned host + device, grown on demand
-    uint32_t *h_stage = nullptr, *d_stage = nullptr;
+    uint32_t *h_stage = nullptr;
     size_t stage_words = 0;
-    // cost-planned launch order (och_gpu_plan_views, OCH_OPT_TILE_ORDER = 2)
+    DevBuf<uint32_t> d_stage;
+    // cost-planned launch orders (och_gpu_plan_views, OCH_OPT_TILE_ORDER = 2)
     // [0] primary frames (grid kernel), [1] config-5 frames (bounce kernel),
     // [2] tiled trace batches (och_gpu_plan_batch_tiled)
-    uint32_t *d_order[3] = {nullptr, nullptr, nullptr};
-    uint32_t *d_order_xcd[3] = {nullptr, nullptr, nullptr};   // OCH_OPT_TILE_ORDER = 3: grouped per XCD
-    uint32_t order_blocks[3] = {0, 0, 0};     // allocated entries
-    uint32_t plan_blocks[3] = {0, 0, 0};      // entries of the current plan (its launch's grid)
-    int64_t plan_key[3][9] = {};
-    // the primary plan's split form (OCH_OPT_SPLIT, plan_split): the heavy tiles'
-    // split waves first, then the plan's other workgroups, and the waves' task
-    // rows; valid with plan_key[0] while split_params matches the options it was
-    // made with
-    uint32_t *d_order_split = nullptr, *d_split_tasks = nullptr;
-    uint32_t split_alloc = 0, task_alloc = 0, split_n = 0, split_extra = 0, split_tiles = 0;
-    int split_params[3] = {0, 0, 0};          // threshold, segments, level
+    LaunchPlan plans[3];
+    SplitPlan split;
     // row deal (och_gpu_set_row_deal): for frames of deal_h rows in chunks of
     // deal_chunk over deal_n shards, chunk g belongs to a chosen shard instead
     // of g % n; slices hold deal_max chunks (the largest shard's, the rest padded)
     int deal_h = 0, deal_chunk = 0, deal_n = 0, deal_max = 0;
     uint64_t deal_serial = 0;                 // changes with every deal (plan keys)
-    int32_t *d_chunk_map = nullptr;           // [deal_n][deal_max] global chunk, -1 = padding
-    int32_t *d_owner = nullptr;               // [n_chunks] shard << 16 | local chunk
+    DevBuf<int32_t> d_chunk_map;              // [deal_n][deal_max] global chunk, -1 = padding
+    DevBuf<int32_t> d_owner;                  // [n_chunks] shard << 16 | local chunk
     std::vector<int32_t> deal_table;          // the chunk -> shard table as set
     bool deal_for(int H, int rc, int n) const { return deal_n && H == deal_h && rc == deal_chunk && n == deal_n; }
     int slice_rows(int H, int rc, int n) const { return deal_for(H, rc, n) ? deal_max * rc : och_shard_rows(H, rc, n); }
@@ -217,20 +262,12 @@ struct och_gpu_pool {
 
     och::Schedule schedule() const
     {
-        och::Schedule sc;
+        och::Schedule sc = {};          // no order, no cost output, no split, no events
         sc.block = opt_block;
         sc.tile_order = opt_tile_order;
         sc.bounce_compact = opt_bounce_compact;
         sc.stamps = stamps;
         sc.stamp_cap = stamp_cap;
-        sc.order = nullptr;
-        sc.order_n = 0;
-        sc.cost = nullptr;
-        sc.split_tasks = nullptr;
-        sc.split_level = 0;
-        sc.split_extra = 0;
-        sc.ev_start = nullptr;
-        sc.ev_stop = nullptr;
         return sc;
     }
 
@@ -268,12 +305,7 @@ namespace {
 
 int ensure_scratch(och_gpu_pool *p, size_t bytes)
 {
-    if (bytes <= p->scratch_bytes) return OCH_OK;
-    if (p->d_scratch) OCH_HIP(hipFree(p->d_scratch));
-    p->d_scratch = nullptr;
-    p->scratch_bytes = 0;
-    OCH_HIP(hipMalloc(&p->d_scratch, bytes));
-    p->scratch_bytes = bytes;
+    OCH_HIP(p->scratch.reserve(bytes));
     return OCH_OK;
 }
 
@@ -658,17 +690,8 @@ OCH_API int och_gpu_pool_destroy(och_gpu_pool *p)
     if (p->d_lut) (void)hipFree(p->d_lut);
     if (p->d_palette) (void)hipFree(p->d_palette);
     if (p->d_code_table) (void)hipFree(p->d_code_table);
-    if (p->d_scratch) (void)hipFree(p->d_scratch);
     if (p->h_stage) (void)hipHostFree(p->h_stage);
-    if (p->d_stage) (void)hipFree(p->d_stage);
-    for (uint32_t *o : p->d_order)
-        if (o) (void)hipFree(o);
-    if (p->d_order_split) (void)hipFree(p->d_order_split);
-    if (p->d_split_tasks) (void)hipFree(p->d_split_tasks);
-    for (uint32_t *o : p->d_order_xcd)
-        if (o) (void)hipFree(o);
-    if (p->d_chunk_map) (void)hipFree(p->d_chunk_map);
-    if (p->d_owner) (void)hipFree(p->d_owner);
+    // the scratch, the editor stage, the plans and the row deal's tables: DevBuf, freed by delete below
     if (p->ev_start) (void)hipEventDestroy(p->ev_start);
     if (p->ev_stop) (void)hipEventDestroy(p->ev_stop);
     if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
@@ -822,24 +845,24 @@ int och::pool_scatter_slots(och_gpu_pool *p, const uint32_t *ids, uint32_t count
     p->last_writer = 0;                 // until pool_commit
     // staging: [ids | raw | packed]
     const size_t words = (size_t)count * (packed ? 17 : 9);
+    const size_t cap = std::max<size_t>(words, 1 << 16);
     if (words > p->stage_words) {
         if (p->h_stage) OCH_HIP(hipHostFree(p->h_stage));
-        if (p->d_stage) OCH_HIP(hipFree(p->d_stage));
-        p->h_stage = p->d_stage = nullptr;
+        p->h_stage = nullptr;
         p->stage_words = 0;
-        const size_t cap = std::max<size_t>(words, 1 << 16);
         OCH_HIP(hipHostMalloc(&p->h_stage, cap * 4, hipHostMallocDefault));
-        OCH_HIP(hipMalloc(&p->d_stage, cap * 4));
         p->stage_words = cap;
     }
+    OCH_HIP(p->d_stage.reserve(cap));
     std::memcpy(p->h_stage, ids, (size_t)count * 4);
     std::memcpy(p->h_stage + count, raw, (size_t)count * 32);
     if (packed) std::memcpy(p->h_stage + 9 * (size_t)count, packed, (size_t)count * 32);
     for (uint32_t i = 0; i < count; ++i)       // host mirror (user numbering, slot s at row s - 1)
         std::memcpy(p->mirror.data() + (size_t)(ids[i] - 1) * 8, raw + (size_t)i * 8, 32);
     const hipStream_t s = p->stream();
-    OCH_HIP(hipMemcpyAsync(p->d_stage, p->h_stage, words * 4, hipMemcpyHostToDevice, s));
-    OCH_HIP(och::launch_scatter_slots(p->d_stage, p->d_stage + count, packed ? p->d_stage + 9 * (size_t)count : nullptr,
+    uint32_t *stage = p->d_stage.d;
+    OCH_HIP(hipMemcpyAsync(stage, p->h_stage, words * 4, hipMemcpyHostToDevice, s));
+    OCH_HIP(och::launch_scatter_slots(stage, stage + count, packed ? stage + 9 * (size_t)count : nullptr,
                                       count, p->d_nodes, packed ? p->d_packed : nullptr, s));
     OCH_HIP(hipStreamSynchronize(s));
     return OCH_OK;
@@ -886,6 +909,258 @@ int och::pool_mark_torn(och_gpu_pool *p)
     p->torn = true;
     return OCH_OK;
 }
+
+// ------------------------------------------------------------ launch planning
+// The pure planners: vectors and integers in and out, no HIP call, no pool; external
+// linkage, so that a host program can call them (tests/test_plan_host.py pins them).
+namespace och {
+namespace plan {
+
+// The stable costliest-first permutation of the workgroups.
+std::vector<uint32_t> by_cost(const std::vector<uint32_t> &costs)
+{
+    std::vector<uint32_t> order(costs.size());
+    for (uint32_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return costs[a] > costs[b]; });
+    return order;
+}
+
+// The launch order from the costliest-first list (OCH_OPT_PLAN): 0 = all
+// workgroups costliest first; P in 1..99 = the costliest P % first, then the
+// rest in natural order (the tails a frame ends on start early, while the bulk
+// keeps the raster order's mix of sky and terrain tiles); 100 = alternate the
+// costliest and the cheapest left.  Default 10: with frames in flight, every
+// frame starting all its costly tiles at once cost 3.5 % over long runs
+// (DESIGN.md §5; profiles/r03/ab/plan_*).
+void shape(std::vector<uint32_t> &order, int mode)
+{
+    const size_t n = order.size();
+    if (mode <= 0 || n < 2) return;
+    std::vector<uint32_t> out;
+    out.reserve(n);
+    if (mode >= 100) {
+        for (size_t i = 0, j = n - 1; i <= j && j < n; ++i, --j) {
+            out.push_back(order[i]);
+            if (j != i) out.push_back(order[j]);
+            if (j == 0) break;
+        }
+    } else {
+        const size_t head = n * (size_t)mode / 100;
+        std::vector<uint8_t> taken(n, 0);
+        for (size_t i = 0; i < head; ++i) {
+            out.push_back(order[i]);
+            taken[order[i]] = 1;
+        }
+        for (uint32_t b = 0; b < n; ++b)
+            if (!taken[b]) out.push_back(b);
+    }
+    order.swap(out);
+}
+
+// Grouped per XCD (OCH_OPT_TILE_ORDER = 3): workgroup slot i runs on XCD
+// i % 8, so deal 64x64-pixel supertiles over the XCDs (each XCD's L2 then
+// holds the nodes of its own neighbouring tiles) and keep the costliest-
+// first order within each XCD's list.  Workgroup b starts at tile b * (block / 64).
+std::vector<uint32_t> group_by_xcd(const std::vector<uint32_t> &order, uint32_t tiles_x, uint32_t tiles_y, uint32_t block)
+{
+    const uint32_t stx = (tiles_x + 7) / 8, sty = (tiles_y + 7) / 8;
+    std::vector<std::vector<uint32_t>> lists(8);
+    for (uint32_t b : order) {
+        const uint32_t tile = b * (block / 64), view = tile / (tiles_x * tiles_y), t = tile % (tiles_x * tiles_y);
+        const uint32_t super = (view * sty + (t / tiles_x) / 8) * stx + (t % tiles_x) / 8;
+        lists[super % 8].push_back(b);
+    }
+    std::vector<uint32_t> grouped;
+    grouped.reserve(order.size());
+    std::vector<size_t> at(8, 0);
+    while (grouped.size() < order.size())
+        for (uint32_t x = 0; x < 8 && grouped.size() < order.size(); ++x) {
+            uint32_t from = x;
+            if (at[x] == lists[x].size())       // this XCD's list ran dry: the fullest other list
+                for (uint32_t y = 0; y < 8; ++y)
+                    if (lists[y].size() - at[y] > lists[from].size() - at[from]) from = y;
+            grouped.push_back(lists[from][at[from]++]);
+        }
+    return grouped;
+}
+
+// A split tile's rays longer than this % of its longest walk over
+// OCH_OPT_SPLIT_SEGS lanes; the others take one lane and walk whole
+// (tools/split_model.c: 30 % keeps the critical path of splitting every ray
+// and adds almost no work).
+constexpr int kSplitRayPct = 30;
+
+// The split form of a primary plan (OCH_OPT_SPLIT; DESIGN.md §4d).  The tiles
+// whose planning cost reaches opt_split % of the costliest one's are split:
+// one counting render gives every pixel's walked PUSHes, a tile's rays longer
+// than kSplitRayPct % of its longest get opt_split_segs lanes each (segment
+// lanes), the others one, and its rays are packed, costliest first, into
+// waves of 64 lanes with every lane of a ray in one wave (their records merge
+// through that wave's LDS).  Rows of d_split_tasks: the tile, then 64 lane
+// tasks (pixel | seg << 6 | log2(S) << 10, ~0 idle).  The order: the split
+// waves (1 << 31 | row), then the plan's other workgroups in its order.
+// Block 64 only (workgroup = tile), packed layout, tiles < 2^24, and a split
+// level above the leaves; otherwise no split plan.
+
+// One tile's waves, 64 lane tasks each, from its pixels' PUSHes (-1: outside the frame).
+std::vector<uint32_t> pack_split_tile(const int cnt[64], int S)
+{
+    const int log2s = __builtin_ctz((unsigned)S), mx = std::max(0, *std::max_element(cnt, cnt + 64));
+    auto long_ray = [&](int l) { return cnt[l] * 100 > kSplitRayPct * mx; };
+    std::vector<std::pair<int, int>> rays;                  // (estimated lane cost, pixel)
+    for (int l = 0; l < 64; ++l)
+        if (cnt[l] >= 0) rays.push_back({long_ray(l) ? cnt[l] / S : cnt[l], l});
+    std::stable_sort(rays.begin(), rays.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
+    std::vector<uint32_t> waves, used;                      // 64 words per wave, idle at first; lanes taken
+    for (const auto &r : rays) {
+        const uint32_t l = (uint32_t)r.second, lanes = long_ray(r.second) ? (uint32_t)S : 1u;
+        size_t w = 0;
+        while (w < used.size() && used[w] + lanes > 64) ++w;
+        if (w == used.size()) {
+            used.push_back(0);
+            waves.resize(waves.size() + 64, ~0u);
+        }
+        for (uint32_t s = 0; s < lanes; ++s)
+            waves[w * 64 + used[w]++] = l | s << 6 | (uint32_t)(lanes > 1 ? log2s : 0) << 10;
+    }
+    return waves;
+}
+
+struct Split {
+    std::vector<uint32_t> order, tasks;
+    uint32_t tiles = 0, extra = 0;      // heavy tiles; waves - heavy tiles
+};
+
+// The heavy tiles (pct % of the costliest, at most max(1, n / 16): a bound on the
+// planner's work), their waves, and the split order; push: slices of rows x W.
+Split split_order(const std::vector<uint16_t> &push, int W, int rows, const std::vector<uint32_t> &by_cost,
+                  const std::vector<uint32_t> &order, const std::vector<uint32_t> &c, int pct, int S)
+{
+    Split sp;
+    const uint32_t n = (uint32_t)order.size();
+    if (pct <= 0 || n == 0) return sp;
+    const double thr = (double)c[by_cost[0]] * pct / 100.0;
+    const uint32_t cap = std::max(1u, n / 16);
+    const uint32_t tiles_x = (uint32_t)(W + 7) / 8, per_view = tiles_x * (uint32_t)((rows + 7) / 8);
+    std::vector<uint8_t> heavy(n, 0);
+    for (uint32_t k = 0; k < n && k < cap && (double)c[by_cost[k]] >= thr; ++k, ++sp.tiles) {
+        const uint32_t t = by_cost[k];
+        heavy[t] = 1;
+        const uint32_t view = t / per_view, tt = t % per_view, ty = tt / tiles_x, tx = tt % tiles_x;
+        int cnt[64];
+        for (int l = 0; l < 64; ++l) {
+            const uint32_t col = tx * 8 + (uint32_t)(l % 8), srow = ty * 8 + (uint32_t)(l / 8);
+            cnt[l] = col < (uint32_t)W && srow < (uint32_t)rows ? push[((size_t)view * rows + srow) * W + col] : -1;
+        }
+        const std::vector<uint32_t> waves = pack_split_tile(cnt, S);
+        for (size_t w = 0; w < waves.size(); w += 64) {
+            sp.order.push_back(0x80000000u | (uint32_t)(sp.tasks.size() / 65));
+            sp.tasks.push_back(t);
+            sp.tasks.insert(sp.tasks.end(), waves.begin() + w, waves.begin() + w + 64);
+        }
+    }
+    sp.extra = (uint32_t)sp.order.size() - sp.tiles;
+    for (uint32_t b : order)
+        if (!heavy[b]) sp.order.push_back(b);
+    return sp;
+}
+
+// A workgroup's time spread over its per_block tiles (natural 8x8-tile order), a
+// tile's over its 8 rows, summed per chunk of row_chunk rows (och_gpu_chunk_costs).
+std::vector<float> spread_chunk_costs(const std::vector<uint32_t> &c, int n_views, int W, int H, uint32_t per_block,
+                                      int row_chunk)
+{
+    const uint32_t tiles_x = (uint32_t)(W + 7) / 8, tiles_y = (uint32_t)(H + 7) / 8;
+    const uint32_t tiles = (uint32_t)n_views * tiles_x * tiles_y;
+    std::vector<double> acc((H + row_chunk - 1) / row_chunk, 0.0);
+    for (uint32_t b = 0; b < c.size(); ++b)
+        for (uint32_t t = b * per_block; t < std::min(tiles, (b + 1) * per_block); ++t) {
+            const uint32_t ty = (t % (tiles_x * tiles_y)) / tiles_x;
+            const int r0 = (int)ty * 8, r1 = std::min(H, r0 + 8);
+            for (int r = r0; r < r1; ++r) acc[r / row_chunk] += (double)c[b] / per_block / (r1 - r0);
+        }
+    return std::vector<float>(acc.begin(), acc.end());
+}
+
+}  // namespace plan
+}  // namespace och
+
+namespace {
+
+int tiled_args(const och_gpu_pool *p, const float *origin, int origin_stride, const float *dirs, uint32_t n,
+               uint32_t width)
+{
+    if (!p || (n && (!origin || !dirs))) return fail(OCH_E_INVALID, "NULL argument");
+    if (origin_stride != 0 && origin_stride != 3) return fail(OCH_E_INVALID, "origin_stride must be 0 or 3");
+    if (width == 0) return fail(OCH_E_INVALID, "width must be positive");
+    const uint64_t rows = ((uint64_t)n + width - 1) / width;
+    if ((uint64_t)((width + 7) / 8) * ((rows + 7) / 8) * 64 >= (1ull << 32))
+        return fail(OCH_E_INVALID, "batch of %u rays %u wide too large", n, width);
+    return check_ready(p);
+}
+
+// The key of a tiled batch's launch plan: the geometry and the block size.
+void batch_key(const och_gpu_pool *p, uint32_t n, uint32_t width, int64_t key[9])
+{
+    const int64_t k[9] = {n, width, p->opt_block, 0, 0, 0, 0, 0, 0};
+    std::memcpy(key, k, sizeof k);
+}
+
+// The key of a frame's launch plan: the geometry, the sharding, the block
+// size, config 5's compaction and the row deal the frame was made for.
+void frame_key(const och_gpu_pool *p, const och::DevFrame &f, bool bounce, int64_t key[9])
+{
+    const int64_t k[9] = {f.cams[0].width, f.cams[0].height, f.n_views, f.row_chunk, f.shard, f.n_shards, p->opt_block,
+                          bounce ? p->opt_bounce_compact : 0, f.chunk_map ? (int64_t)p->deal_serial : 0};
+    std::memcpy(key, k, sizeof k);
+}
+
+int check_views(const och_camera *cams, int n_views)
+{
+    for (int v = 0; v < n_views; ++v)
+        if (cams[v].width != cams[0].width || cams[v].height != cams[0].height || cams[v].width <= 0 || cams[v].height <= 0)
+            return fail(OCH_E_INVALID, "views must share one positive width and height");
+    return OCH_OK;
+}
+
+// The frame of n_views checked views (check_views) as the kernels take it,
+// with this shard's slice height and, under a row deal, its chunk map.
+och::DevFrame make_frame(const och_gpu_pool *p, const och_camera *cams, int n_views, uint32_t *out, uint8_t *codes,
+                         int row_chunk, int shard, int n_shards)
+{
+    och::DevFrame f;
+    for (int v = 0; v < n_views; ++v) f.cams[v] = cams[v];
+    f.n_views = n_views;
+    f.palette = p->d_palette;
+    f.n_voxels = p->n_voxels;
+    f.out = out;
+    f.codes = codes;
+    f.row_chunk = row_chunk;
+    f.shard = shard;
+    f.n_shards = n_shards;
+    f.slice_rows = p->slice_rows(cams[0].height, row_chunk, n_shards);
+    const bool dealt = p->deal_for(cams[0].height, row_chunk, n_shards);
+    f.chunk_map = dealt ? p->d_chunk_map.d + (size_t)shard * p->deal_max : nullptr;
+    return f;
+}
+
+// A planning render: launch(sc) in natural order, sc.cost naming n_words words preset to
+// 0xFFFFFFFF that every launched workgroup overwrites with its duration; c receives them.
+template <class Launch>
+int cost_render(och_gpu_pool *p, uint32_t *cost, uint32_t n_words, std::vector<uint32_t> &c, Launch launch)
+{
+    och::Schedule sc = p->schedule();
+    sc.tile_order = 0;
+    sc.cost = cost;
+    OCH_HIP(hipMemsetAsync(cost, 0xFF, (size_t)n_words * 4, p->stream()));
+    OCH_HIP(launch(sc));
+    c.resize(n_words);
+    OCH_HIP(hipMemcpyAsync(c.data(), cost, (size_t)n_words * 4, hipMemcpyDeviceToHost, p->stream()));
+    OCH_HIP(hipStreamSynchronize(p->stream()));
+    return OCH_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1010,7 +1285,7 @@ OCH_API int och_gpu_get_option(const och_gpu_pool *p, int option, int *value)
     case OCH_OPT_SPLIT: *value = p->opt_split; return OCH_OK;
     case OCH_OPT_SPLIT_SEGS: *value = p->opt_split_segs; return OCH_OK;
     case OCH_OPT_SPLIT_LEVEL: *value = p->opt_split_level; return OCH_OK;
-    case OCH_OPT_SPLIT_TILES: *value = (int)p->split_tiles; return OCH_OK;
+    case OCH_OPT_SPLIT_TILES: *value = (int)p->split.tiles; return OCH_OK;
     case 0: case 2: case 3: case 7: case 9: case 12: case 13:
         return retired_option(option);
     default: return fail(OCH_E_INVALID, "unknown option %d", option);
@@ -1072,6 +1347,29 @@ int timed_done(och_gpu_pool *p, const och::Schedule &sc, bool launched)
     }
     return OCH_OK;
 }
+
+// A frame loop points the pool at each frame's stream and hands each launch its events; when
+// it ends, also after a failure, the pool's own stream is back and no event waits for a launch.
+struct FrameLoopScope {
+    och_gpu_pool *const p;
+    const bool had_ext = p->use_ext;
+    const hipStream_t prev = p->ext_stream;
+    ~FrameLoopScope()
+    {
+        p->next_ev_start = p->next_ev_stop = nullptr;
+        p->ext_stream = prev;
+        p->use_ext = had_ext;
+    }
+    void frame(void *stream, void *const *start_events, void *const *stop_events, int k)
+    {
+        p->ext_stream = static_cast<hipStream_t>(stream);
+        p->use_ext = true;
+        if (start_events) {
+            p->next_ev_start = static_cast<hipEvent_t>(start_events[k]);
+            p->next_ev_stop = static_cast<hipEvent_t>(stop_events[k]);
+        }
+    }
+};
 
 }  // namespace
 
@@ -1142,29 +1440,6 @@ OCH_API int och_gpu_trace_bounce_batch_dev(och_gpu_pool *p, const float *origin,
     return timed_done(p, sc, n > 0);
 }
 
-namespace {
-
-int tiled_args(const och_gpu_pool *p, const float *origin, int origin_stride, const float *dirs, uint32_t n,
-               uint32_t width)
-{
-    if (!p || (n && (!origin || !dirs))) return fail(OCH_E_INVALID, "NULL argument");
-    if (origin_stride != 0 && origin_stride != 3) return fail(OCH_E_INVALID, "origin_stride must be 0 or 3");
-    if (width == 0) return fail(OCH_E_INVALID, "width must be positive");
-    const uint64_t rows = ((uint64_t)n + width - 1) / width;
-    if ((uint64_t)((width + 7) / 8) * ((rows + 7) / 8) * 64 >= (1ull << 32))
-        return fail(OCH_E_INVALID, "batch of %u rays %u wide too large", n, width);
-    return check_ready(p);
-}
-
-// The key of a tiled batch's launch plan: the geometry and the block size.
-void batch_key(const och_gpu_pool *p, uint32_t n, uint32_t width, int64_t key[9])
-{
-    const int64_t k[9] = {n, width, p->opt_block, 0, 0, 0, 0, 0, 0};
-    std::memcpy(key, k, sizeof k);
-}
-
-}  // namespace
-
 OCH_API int och_gpu_trace_batch_tiled_dev(och_gpu_pool *p, const float *origin, int origin_stride, const float *dirs,
                                           uint32_t n, uint32_t width, int32_t *hit_dir, uint32_t *hit_voxel,
                                           float *hit_time, uint32_t *push_count)
@@ -1176,12 +1451,12 @@ OCH_API int och_gpu_trace_batch_tiled_dev(och_gpu_pool *p, const float *origin, 
     int ts;
     och::Schedule sc = timed_schedule(p, ts);
     if (ts) return ts;
-    if (p->opt_tile_order >= 2 && p->d_order[2]) {
+    if (p->opt_tile_order >= 2 && p->plans[2].order.d) {
         int64_t key[9];
         batch_key(p, n, width, key);
-        if (std::memcmp(key, p->plan_key[2], sizeof key) == 0) {
-            sc.order = p->d_order[2];
-            sc.order_n = p->plan_blocks[2];
+        if (p->plans[2].matches(key)) {
+            sc.order = p->plans[2].order.d;
+            sc.order_n = p->plans[2].blocks;
         }
     }
     OCH_HIP(och::launch_trace_batch_tiled(p->dev(), origin, origin_stride, dirs, n, width, hit_dir, hit_voxel,
@@ -1201,35 +1476,21 @@ OCH_API int och_gpu_plan_batch_tiled(och_gpu_pool *p, const float *origin, int o
     const size_t out_bytes = (((size_t)n * 4 + 255) & ~(size_t)255);
     int st = ensure_scratch(p, 3 * out_bytes + (size_t)max_blocks * 4);
     if (st != OCH_OK) return st;
-    char *base = static_cast<char *>(p->d_scratch);
-    uint32_t *cost = reinterpret_cast<uint32_t *>(base + 3 * out_bytes);
-    OCH_HIP(hipMemsetAsync(cost, 0xFF, (size_t)max_blocks * 4, p->stream()));
-    och::Schedule sc = p->schedule();
-    sc.tile_order = 0;
-    sc.cost = cost;
-    OCH_HIP(och::launch_trace_batch_tiled(p->dev(), origin, origin_stride, dirs, n, width,
-                                          reinterpret_cast<int32_t *>(base), reinterpret_cast<uint32_t *>(base + out_bytes),
-                                          reinterpret_cast<uint32_t *>(base + 2 * out_bytes), nullptr, sc, p->stream()));
-    std::vector<uint32_t> c(max_blocks);
-    OCH_HIP(hipMemcpyAsync(c.data(), cost, (size_t)max_blocks * 4, hipMemcpyDeviceToHost, p->stream()));
-    OCH_HIP(hipStreamSynchronize(p->stream()));
-    std::vector<uint32_t> order(max_blocks);
-    for (uint32_t i = 0; i < max_blocks; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return c[a] > c[b]; });
-    p->plan_key[2][0] = -1;                   // no plan until the new one is in place (a failure below leaves none)
+    char *base = p->scratch.d;
+    std::vector<uint32_t> c;
+    st = cost_render(p, reinterpret_cast<uint32_t *>(base + 3 * out_bytes), max_blocks, c, [&](const och::Schedule &sc) {
+        return och::launch_trace_batch_tiled(p->dev(), origin, origin_stride, dirs, n, width,
+                                             reinterpret_cast<int32_t *>(base), reinterpret_cast<uint32_t *>(base + out_bytes),
+                                             reinterpret_cast<uint32_t *>(base + 2 * out_bytes), nullptr, sc, p->stream());
+    });
+    if (st != OCH_OK) return st;
+    const std::vector<uint32_t> order = och::plan::by_cost(c);
+    LaunchPlan &plan = p->plans[2];
+    plan.invalidate();                        // no plan until the new one is in place (a failure below leaves none)
     if (int ds = och::pool_drain(p)) return ds;   // launches in flight on other streams may read the old order
-    if (p->order_blocks[2] < max_blocks) {
-        for (uint32_t **o : {&p->d_order[2], &p->d_order_xcd[2]}) {
-            if (*o) OCH_HIP(hipFree(*o));
-            *o = nullptr;
-        }
-        p->order_blocks[2] = 0;
-        OCH_HIP(hipMalloc(&p->d_order[2], (size_t)max_blocks * 4));
-        p->order_blocks[2] = max_blocks;
-    }
-    OCH_HIP(hipMemcpy(p->d_order[2], order.data(), (size_t)max_blocks * 4, hipMemcpyHostToDevice));
-    batch_key(p, n, width, p->plan_key[2]);
-    p->plan_blocks[2] = max_blocks;
+    OCH_HIP(plan.order.upload(order));
+    batch_key(p, n, width, plan.key);
+    plan.blocks = max_blocks;
     return OCH_OK;
 }
 
@@ -1252,7 +1513,7 @@ int host_batch(och_gpu_pool *p, const float *origin, int origin_stride, const fl
     const size_t b_out = ((size_t)n * 4 + 255) & ~(size_t)255;
     int st = ensure_scratch(p, b_orig + b_dirs + 3 * b_out);
     if (st != OCH_OK) return st;
-    char *base = static_cast<char *>(p->d_scratch);
+    char *base = p->scratch.d;
     float *d_orig = reinterpret_cast<float *>(base);
     float *d_dirs = reinterpret_cast<float *>(base + b_orig);
     int32_t *d_dir = reinterpret_cast<int32_t *>(base + b_orig + b_dirs);
@@ -1355,43 +1616,30 @@ int render_views(och_gpu_pool *p, const och_camera *cams, int n_views, uint32_t 
     if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
     if (row_chunk <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards)
         return fail(OCH_E_INVALID, "bad sharding (%d, %d, %d)", row_chunk, shard, n_shards);
-    for (int v = 0; v < n_views; ++v)
-        if (cams[v].width != cams[0].width || cams[v].height != cams[0].height || cams[v].width <= 0 || cams[v].height <= 0)
-            return fail(OCH_E_INVALID, "views must share one positive width and height");
+    if (int vs = check_views(cams, n_views)) return vs;
     if ((uint64_t)cams[0].width * cams[0].height * n_views >= (1ull << 32))
         return fail(OCH_E_INVALID, "frame too large");
     if (int rs = check_ready(p)) return rs;
     DeviceGuard g(p->device);
-    och::DevFrame f;
-    for (int v = 0; v < n_views; ++v) f.cams[v] = cams[v];
-    f.n_views = n_views;
-    f.palette = p->d_palette;
-    f.n_voxels = p->n_voxels;
-    f.out = rgba_slices;
-    f.codes = code_slices;
-    f.row_chunk = row_chunk;
-    f.shard = shard;
-    f.n_shards = n_shards;
-    f.slice_rows = p->slice_rows(cams[0].height, row_chunk, n_shards);
-    const bool dealt = p->deal_for(cams[0].height, row_chunk, n_shards);
-    f.chunk_map = dealt ? p->d_chunk_map + (size_t)shard * p->deal_max : nullptr;
+    const och::DevFrame f = make_frame(p, cams, n_views, rgba_slices, code_slices, row_chunk, shard, n_shards);
     int ts;
     och::Schedule sc = timed_schedule(p, ts);
     if (ts) return ts;
-    const int which = bounce ? 1 : 0;
-    if (p->opt_tile_order >= 2 && p->d_order[which]) {
-        const int64_t key[9] = {cams[0].width, cams[0].height, n_views, row_chunk, shard, n_shards, p->opt_block,
-                                bounce ? p->opt_bounce_compact : 0, dealt ? (int64_t)p->deal_serial : 0};
-        if (std::memcmp(key, p->plan_key[which], sizeof key) == 0) {
-            sc.order = p->opt_tile_order == 3 ? p->d_order_xcd[which] : p->d_order[which];
-            sc.order_n = p->plan_blocks[which];
+    const LaunchPlan &plan = p->plans[bounce ? 1 : 0];
+    if (p->opt_tile_order >= 2 && plan.order.d) {
+        int64_t key[9];
+        frame_key(p, f, bounce, key);
+        if (plan.matches(key)) {
+            sc.order = p->opt_tile_order == 3 ? plan.order_xcd.d : plan.order.d;
+            sc.order_n = plan.blocks;
             // the plan's split form, while the options it was made with hold
-            if (!bounce && p->opt_tile_order == 2 && p->split_n && p->dev().packed && p->opt_split == p->split_params[0] &&
-                p->opt_split_segs == p->split_params[1] && p->opt_split_level == p->split_params[2]) {
-                sc.order = p->d_order_split;
-                sc.order_n = p->split_n;
-                sc.split_extra = p->split_extra;
-                sc.split_tasks = p->d_split_tasks;
+            const SplitPlan &sp = p->split;
+            if (!bounce && p->opt_tile_order == 2 && sp.n && p->dev().packed && p->opt_split == sp.params[0] &&
+                p->opt_split_segs == sp.params[1] && p->opt_split_level == sp.params[2]) {
+                sc.order = sp.order.d;
+                sc.order_n = sp.n;
+                sc.split_extra = sp.extra;
+                sc.split_tasks = sp.tasks.d;
                 sc.split_level = (uint32_t)p->opt_split_level;
             }
         }
@@ -1405,143 +1653,39 @@ int render_views(och_gpu_pool *p, const och_camera *cams, int n_views, uint32_t 
     return timed_done(p, sc, true);
 }
 
-}  // namespace
-
-namespace {
-
-// The launch order from the costliest-first list (OCH_OPT_PLAN): 0 = all
-// workgroups costliest first; P in 1..99 = the costliest P % first, then the
-// rest in natural order (the tails a frame ends on start early, while the bulk
-// keeps the raster order's mix of sky and terrain tiles); 100 = alternate the
-// costliest and the cheapest left.  Default 10: with frames in flight, every
-// frame starting all its costly tiles at once cost 3.5 % over long runs
-// (DESIGN.md §5; profiles/r03/ab/plan_*).
-void plan_shape(std::vector<uint32_t> &order, int mode)
-{
-    const size_t n = order.size();
-    if (mode <= 0 || n < 2) return;
-    std::vector<uint32_t> out;
-    out.reserve(n);
-    if (mode >= 100) {
-        for (size_t i = 0, j = n - 1; i <= j && j < n; ++i, --j) {
-            out.push_back(order[i]);
-            if (j != i) out.push_back(order[j]);
-            if (j == 0) break;
-        }
-    } else {
-        const size_t head = n * (size_t)mode / 100;
-        std::vector<uint8_t> taken(n, 0);
-        for (size_t i = 0; i < head; ++i) {
-            out.push_back(order[i]);
-            taken[order[i]] = 1;
-        }
-        for (uint32_t b = 0; b < n; ++b)
-            if (!taken[b]) out.push_back(b);
-    }
-    order.swap(out);
-}
-
-// A split tile's rays longer than this % of its longest walk over
-// OCH_OPT_SPLIT_SEGS lanes; the others take one lane and walk whole
-// (tools/split_model.c: 30 % keeps the critical path of splitting every ray
-// and adds almost no work).
-constexpr int kSplitRayPct = 30;
-
-// The split form of a primary plan (OCH_OPT_SPLIT; DESIGN.md §4d).  The tiles
-// whose planning cost reaches opt_split % of the costliest one's are split:
-// one counting render gives every pixel's walked PUSHes, a tile's rays longer
-// than kSplitRayPct % of its longest get opt_split_segs lanes each (segment
-// lanes), the others one, and its rays are packed, costliest first, into
-// waves of 64 lanes with every lane of a ray in one wave (their records merge
-// through that wave's LDS).  Rows of d_split_tasks: the tile, then 64 lane
-// tasks (pixel | seg << 6 | log2(S) << 10, ~0 idle).  The order: the split
-// waves (1 << 31 | row), then the plan's other workgroups in its order.
-// Block 64 only (workgroup = tile), packed layout, tiles < 2^24, and a split
-// level above the leaves; otherwise no split plan.
+// The primary plan's split form (och::plan::split_order has the whole story):
+// the counting render, the split order and task rows, their upload.
 int plan_split(och_gpu_pool *p, const och::DevFrame &f, const std::vector<uint32_t> &by_cost,
                const std::vector<uint32_t> &order, const std::vector<uint32_t> &c)
 {
-    p->split_n = p->split_extra = p->split_tiles = 0;
-    p->split_params[0] = p->split_params[1] = p->split_params[2] = 0;
+    SplitPlan &sp = p->split;
+    sp.invalidate();
     const uint32_t n = (uint32_t)order.size();
-    const int S = p->opt_split_segs, log2s = __builtin_ctz((unsigned)S);
     if (p->opt_split <= 0 || p->opt_block != 64 || !p->dev().packed || p->opt_split_level >= p->depth || n == 0 ||
         n >= (1u << 24))
         return OCH_OK;
-    const double thr = (double)c[by_cost[0]] * p->opt_split / 100.0;
-    std::vector<uint32_t> heavy_tiles;
-    const uint32_t cap = std::max(1u, n / 16);                  // a bound on the planner's work
-    for (uint32_t k = 0; k < n && k < cap && (double)c[by_cost[k]] >= thr; ++k) heavy_tiles.push_back(by_cost[k]);
     // every pixel's walked PUSHes (one counting render of the planned frame)
-    const int W = f.cams[0].width, rows = f.slice_rows;
-    const size_t px = (size_t)f.n_views * rows * W;
-    uint16_t *d_push = nullptr;
-    OCH_HIP(hipMalloc(&d_push, px * 2));
-    std::vector<uint16_t> push(px);
+    std::vector<uint16_t> push((size_t)f.n_views * f.slice_rows * f.cams[0].width);
+    DevBuf<uint16_t> d_push;
+    OCH_HIP(d_push.reserve(push.size()));
     och::Schedule sc = p->schedule();
     sc.tile_order = 0;
-    hipError_t e = och::launch_render_push(p->dev(), f, sc, d_push, p->stream());
-    if (e == hipSuccess) e = hipMemcpyAsync(push.data(), d_push, px * 2, hipMemcpyDeviceToHost, p->stream());
+    hipError_t e = och::launch_render_push(p->dev(), f, sc, d_push.d, p->stream());
+    if (e == hipSuccess) e = hipMemcpyAsync(push.data(), d_push.d, push.size() * 2, hipMemcpyDeviceToHost, p->stream());
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream());
-    (void)hipFree(d_push);
+    (void)d_push.release();
     if (e != hipSuccess) return fail(OCH_E_HIP, "split plan: counting render: %s", hipGetErrorString(e));
-    const uint32_t tiles_x = (uint32_t)(W + 7) / 8, per_view = tiles_x * (uint32_t)((rows + 7) / 8);
-    std::vector<uint32_t> rowsv, split;                         // task rows (65 words each), order
-    std::vector<uint8_t> heavy(n, 0);
-    for (uint32_t t : heavy_tiles) {
-        heavy[t] = 1;
-        const uint32_t view = t / per_view, tt = t % per_view, ty = tt / tiles_x, tx = tt % tiles_x;
-        int cnt[64], mx = 0;
-        for (int l = 0; l < 64; ++l) {
-            const uint32_t col = tx * 8 + (uint32_t)(l % 8), srow = ty * 8 + (uint32_t)(l / 8);
-            cnt[l] = col < (uint32_t)W && srow < (uint32_t)rows ? push[((size_t)view * rows + srow) * W + col] : -1;
-            mx = std::max(mx, cnt[l]);
-        }
-        // rays costliest first (a long ray by its segments' share), first fit into waves
-        std::vector<std::pair<int, int>> rays;                  // (estimated lane cost, pixel)
-        for (int l = 0; l < 64; ++l)
-            if (cnt[l] >= 0) rays.push_back({cnt[l] * 100 > kSplitRayPct * mx ? cnt[l] / S : cnt[l], l});
-        std::stable_sort(rays.begin(), rays.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
-        std::vector<std::vector<uint32_t>> waves;
-        for (const auto &r : rays) {
-            const int l = r.second;
-            const bool long_ray = cnt[l] * 100 > kSplitRayPct * mx;
-            const size_t lanes = long_ray ? (size_t)S : 1;
-            size_t w = 0;
-            while (w < waves.size() && waves[w].size() + lanes > 64) ++w;
-            if (w == waves.size()) waves.emplace_back();
-            for (size_t s_ = 0; s_ < lanes; ++s_)
-                waves[w].push_back((uint32_t)l | (uint32_t)s_ << 6 | (uint32_t)(long_ray ? log2s : 0) << 10);
-        }
-        for (auto &w : waves) {
-            split.push_back(0x80000000u | (uint32_t)(rowsv.size() / 65));
-            rowsv.push_back(t);
-            for (size_t l = 0; l < 64; ++l) rowsv.push_back(l < w.size() ? w[l] : ~0u);
-        }
-    }
-    if (heavy_tiles.empty()) return OCH_OK;
-    const uint32_t n_waves = (uint32_t)split.size();
-    for (uint32_t b : order)
-        if (!heavy[b]) split.push_back(b);
-    auto upload = [&](uint32_t *&d, uint32_t &alloc, const std::vector<uint32_t> &v) -> hipError_t {
-        if (alloc < v.size()) {
-            if (d) (void)hipFree(d);
-            d = nullptr;
-            alloc = 0;
-            const hipError_t me = hipMalloc(&d, v.size() * 4);
-            if (me != hipSuccess) return me;
-            alloc = (uint32_t)v.size();
-        }
-        return hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice);
-    };
-    OCH_HIP(upload(p->d_order_split, p->split_alloc, split));
-    OCH_HIP(upload(p->d_split_tasks, p->task_alloc, rowsv));
-    p->split_n = (uint32_t)split.size();
-    p->split_extra = n_waves - (uint32_t)heavy_tiles.size();
-    p->split_tiles = (uint32_t)heavy_tiles.size();
-    p->split_params[0] = p->opt_split;
-    p->split_params[1] = S;
-    p->split_params[2] = p->opt_split_level;
+    const och::plan::Split s = och::plan::split_order(push, f.cams[0].width, f.slice_rows, by_cost, order, c, p->opt_split,
+                                                      p->opt_split_segs);
+    if (s.tiles == 0) return OCH_OK;
+    OCH_HIP(sp.order.upload(s.order));
+    OCH_HIP(sp.tasks.upload(s.tasks));
+    sp.n = (uint32_t)s.order.size();
+    sp.extra = s.extra;
+    sp.tiles = s.tiles;
+    sp.params[0] = p->opt_split;
+    sp.params[1] = p->opt_split_segs;
+    sp.params[2] = p->opt_split_level;
     return OCH_OK;
 }
 
@@ -1554,97 +1698,46 @@ OCH_API int och_gpu_plan_views(och_gpu_pool *p, const och_camera *cams, int n_vi
     if (!p || !cams) return fail(OCH_E_INVALID, "NULL argument");
     if (n_views < 1 || n_views > OCH_MAX_VIEWS || row_chunk <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards)
         return fail(OCH_E_INVALID, "bad plan arguments");
+    if (int vs = check_views(cams, n_views)) return vs;
     if (int rs = check_ready(p)) return rs;
     DeviceGuard g(p->device);
     // One planning render per kernel (primary grid, config-5 bounce) into
     // scratch in natural order, timing every workgroup.
-    const int W = cams[0].width, H = cams[0].height;
-    const int rows = p->slice_rows(H, row_chunk, n_shards);
-    const bool dealt = p->deal_for(H, row_chunk, n_shards);
+    const int W = cams[0].width, rows = p->slice_rows(cams[0].height, row_chunk, n_shards);
+    const uint32_t tiles_x = (uint32_t)(W + 7) / 8, tiles_y = (uint32_t)(rows + 7) / 8;
     const size_t frame_bytes = (size_t)n_views * rows * W * 4;
-    const uint32_t max_blocks = (uint32_t)((size_t)n_views * ((rows + 7) / 8) * ((W + 7) / 8)) + 1024;
+    const uint32_t max_blocks = (uint32_t)((size_t)n_views * tiles_y * tiles_x) + 1024;
     int st = ensure_scratch(p, frame_bytes + (size_t)max_blocks * 4);
     if (st != OCH_OK) return st;
-    uint32_t *cost = reinterpret_cast<uint32_t *>(static_cast<char *>(p->d_scratch) + frame_bytes);
-    och::DevFrame f;
-    for (int v = 0; v < n_views; ++v) f.cams[v] = cams[v];
-    f.n_views = n_views;
-    f.palette = p->d_palette;
-    f.n_voxels = p->n_voxels;
-    f.out = static_cast<uint32_t *>(p->d_scratch);
-    f.codes = nullptr;
-    f.row_chunk = row_chunk;
-    f.shard = shard;
-    f.n_shards = n_shards;
-    f.slice_rows = rows;
-    f.chunk_map = dealt ? p->d_chunk_map + (size_t)shard * p->deal_max : nullptr;
+    uint32_t *cost = reinterpret_cast<uint32_t *>(p->scratch.d + frame_bytes);
+    const och::DevFrame f = make_frame(p, cams, n_views, reinterpret_cast<uint32_t *>(p->scratch.d), nullptr, row_chunk,
+                                       shard, n_shards);
     for (int which = 0; which < 2; ++which) {
-        OCH_HIP(hipMemsetAsync(cost, 0xFF, (size_t)max_blocks * 4, p->stream()));
-        och::Schedule sc = p->schedule();
-        sc.tile_order = 0;
-        sc.cost = cost;
-        if (which == 0)
-            OCH_HIP(och::launch_render(p->dev(), f, sc, p->stream()));
-        else
-            OCH_HIP(och::launch_render_bounce(p->dev(), f, sc, p->stream()));
-        std::vector<uint32_t> c(max_blocks);
-        OCH_HIP(hipMemcpyAsync(c.data(), cost, (size_t)max_blocks * 4, hipMemcpyDeviceToHost, p->stream()));
-        OCH_HIP(hipStreamSynchronize(p->stream()));
-        uint32_t n_blocks = 0;
-        while (n_blocks < max_blocks && c[n_blocks] != 0xFFFFFFFFu) ++n_blocks;   // launched blocks wrote a cost
-        if (n_blocks == 0) {
-            p->plan_key[which][0] = -1;          // no plan: later launches run in natural order
+        LaunchPlan &plan = p->plans[which];
+        std::vector<uint32_t> c;
+        st = cost_render(p, cost, max_blocks, c, [&](const och::Schedule &sc) {
+            return which ? och::launch_render_bounce(p->dev(), f, sc, p->stream())
+                         : och::launch_render(p->dev(), f, sc, p->stream());
+        });
+        if (st != OCH_OK) return st;
+        c.resize(std::find(c.begin(), c.end(), 0xFFFFFFFFu) - c.begin());   // launched blocks wrote a cost
+        if (c.empty()) {
+            plan.invalidate();                   // no plan: later launches run in natural order
             return fail(OCH_E_INVALID, "planning render wrote no workgroup costs (kernel without cost output?)");
         }
-        std::vector<uint32_t> order(n_blocks);
-        for (uint32_t i = 0; i < n_blocks; ++i) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return c[a] > c[b]; });
-        const std::vector<uint32_t> by_cost = order;
-        plan_shape(order, p->opt_plan);
-        // Grouped per XCD (OCH_OPT_TILE_ORDER = 3): workgroup slot i runs on XCD
-        // i % 8, so deal 64x64-pixel supertiles over the XCDs (each XCD's L2 then
-        // holds the nodes of its own neighbouring tiles) and keep the costliest-
-        // first order within each XCD's list.
+        const std::vector<uint32_t> by_cost = och::plan::by_cost(c);
+        std::vector<uint32_t> order = by_cost;
+        och::plan::shape(order, p->opt_plan);
         const uint32_t block = (uint32_t)(which ? std::max(och::kBounceBlock, p->opt_block) : p->opt_block);
-        const uint32_t tiles_x = (uint32_t)(W + 7) / 8, tiles_y = (uint32_t)(rows + 7) / 8;
-        const uint32_t stx = (tiles_x + 7) / 8, sty = (tiles_y + 7) / 8;
-        std::vector<std::vector<uint32_t>> lists(8);
-        for (uint32_t b : order) {
-            const uint32_t tile = b * (block / 64), view = tile / (tiles_x * tiles_y), t = tile % (tiles_x * tiles_y);
-            const uint32_t st = (view * sty + (t / tiles_x) / 8) * stx + (t % tiles_x) / 8;
-            lists[st % 8].push_back(b);
-        }
-        std::vector<uint32_t> grouped;
-        grouped.reserve(n_blocks);
-        std::vector<size_t> at(8, 0);
-        while (grouped.size() < n_blocks)
-            for (uint32_t x = 0; x < 8 && grouped.size() < n_blocks; ++x) {
-                uint32_t from = x;
-                if (at[x] == lists[x].size())       // this XCD's list ran dry: the fullest other list
-                    for (uint32_t y = 0; y < 8; ++y)
-                        if (lists[y].size() - at[y] > lists[from].size() - at[from]) from = y;
-                grouped.push_back(lists[from][at[from]++]);
-            }
-        p->plan_key[which][0] = -1;           // no plan until the new one is in place (a failure below leaves none)
+        const std::vector<uint32_t> grouped = och::plan::group_by_xcd(order, tiles_x, tiles_y, block);
+        plan.invalidate();                    // no plan until the new one is in place (a failure below leaves none)
         if (int ds = och::pool_drain(p)) return ds;   // launches in flight on other streams may read the old order
-        if (p->order_blocks[which] < n_blocks) {
-            for (uint32_t **o : {&p->d_order[which], &p->d_order_xcd[which]}) {
-                if (*o) OCH_HIP(hipFree(*o));
-                *o = nullptr;
-            }
-            p->order_blocks[which] = 0;
-            OCH_HIP(hipMalloc(&p->d_order[which], (size_t)n_blocks * 4));
-            OCH_HIP(hipMalloc(&p->d_order_xcd[which], (size_t)n_blocks * 4));
-            p->order_blocks[which] = n_blocks;
-        }
-        OCH_HIP(hipMemcpy(p->d_order[which], order.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice));
-        OCH_HIP(hipMemcpy(p->d_order_xcd[which], grouped.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice));
+        OCH_HIP(plan.order.upload(order));
+        OCH_HIP(plan.order_xcd.upload(grouped));
         if (which == 0)
             if (int ss = plan_split(p, f, by_cost, order, c)) return ss;
-        const int64_t key[9] = {W, H, n_views, row_chunk, shard, n_shards, p->opt_block,
-                                which ? p->opt_bounce_compact : 0, dealt ? (int64_t)p->deal_serial : 0};
-        std::memcpy(p->plan_key[which], key, sizeof key);
-        p->plan_blocks[which] = n_blocks;
+        frame_key(p, f, which != 0, plan.key);
+        plan.blocks = (uint32_t)order.size();
     }
     return OCH_OK;
 }
@@ -1681,30 +1774,18 @@ OCH_API int och_gpu_set_row_deal(och_gpu_pool *p, int height, int row_chunk, int
             }
     }
     DeviceGuard g(p->device);
-    int32_t *d_map = nullptr, *d_own = nullptr;
+    DevBuf<int32_t> d_map, d_own;             // the new tables; after the swap below, the old ones (freed on return)
     if (chunk_shard) {
-        hipError_t e = hipMalloc(&d_map, map.size() * 4);
-        if (e == hipSuccess) e = hipMalloc(&d_own, owner.size() * 4);
-        if (e == hipSuccess) e = hipMemcpy(d_map, map.data(), map.size() * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_own, owner.data(), owner.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            if (d_map) (void)hipFree(d_map);
-            if (d_own) (void)hipFree(d_own);
-            return fail(OCH_E_HIP, "row deal tables: %s", hipGetErrorString(e));
-        }
+        hipError_t e = d_map.upload(map);
+        if (e == hipSuccess) e = d_own.upload(owner);
+        if (e != hipSuccess) return fail(OCH_E_HIP, "row deal tables: %s", hipGetErrorString(e));
     }
     // frames in flight may still read the old tables; on failure the new ones
     // are freed and the old deal stays
     const hipError_t se = hipDeviceSynchronize();
-    if (se != hipSuccess) {
-        if (d_map) (void)hipFree(d_map);
-        if (d_own) (void)hipFree(d_own);
-        return fail(OCH_E_HIP, "row deal: hipDeviceSynchronize: %s", hipGetErrorString(se));
-    }
-    if (p->d_chunk_map) (void)hipFree(p->d_chunk_map);
-    if (p->d_owner) (void)hipFree(p->d_owner);
-    p->d_chunk_map = d_map;
-    p->d_owner = d_own;
+    if (se != hipSuccess) return fail(OCH_E_HIP, "row deal: hipDeviceSynchronize: %s", hipGetErrorString(se));
+    p->d_chunk_map.swap(d_map);
+    p->d_owner.swap(d_own);
     ++p->deal_serial;
     if (!chunk_shard) {                        // back to round-robin
         p->deal_n = p->deal_h = p->deal_chunk = p->deal_max = 0;
@@ -1731,57 +1812,30 @@ OCH_API int och_gpu_chunk_costs(och_gpu_pool *p, const och_camera *cams, int n_v
     OCH_ENTRY();
     if (!p || !cams || !costs || row_chunk <= 0) return fail(OCH_E_INVALID, "bad chunk-cost arguments");
     if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
-    for (int v = 0; v < n_views; ++v)
-        if (cams[v].width != cams[0].width || cams[v].height != cams[0].height || cams[v].width <= 0 || cams[v].height <= 0)
-            return fail(OCH_E_INVALID, "views must share one positive width and height");
+    if (int vs = check_views(cams, n_views)) return vs;
     if (int rs = check_ready(p)) return rs;
     DeviceGuard g(p->device);
     // one whole-frame render, natural 8x8-tile order, every workgroup timed
     const int W = cams[0].width, H = cams[0].height;
-    const uint32_t tiles_x = (uint32_t)(W + 7) / 8, tiles_y = (uint32_t)(H + 7) / 8;
     // tiles per workgroup exactly as launch_as sizes the grid kernel's grid
-    const uint32_t tiles = (uint32_t)n_views * tiles_x * tiles_y,
+    const uint32_t tiles = (uint32_t)n_views * ((uint32_t)(W + 7) / 8) * ((uint32_t)(H + 7) / 8),
                    per_block = (uint32_t)p->opt_block / 64;
     const uint32_t n_blocks = (tiles + per_block - 1) / per_block;
     const size_t frame_bytes = ((size_t)n_views * H * W * 4 + 255) & ~(size_t)255;
     int st = ensure_scratch(p, frame_bytes + (size_t)n_blocks * 4);
     if (st != OCH_OK) return st;
-    uint32_t *cost = reinterpret_cast<uint32_t *>(static_cast<char *>(p->d_scratch) + frame_bytes);
-    och::DevFrame f;
-    for (int v = 0; v < n_views; ++v) f.cams[v] = cams[v];
-    f.n_views = n_views;
-    f.palette = p->d_palette;
-    f.n_voxels = p->n_voxels;
-    f.out = static_cast<uint32_t *>(p->d_scratch);
-    f.codes = nullptr;
-    f.row_chunk = H;
-    f.shard = 0;
-    f.n_shards = 1;
-    f.slice_rows = H;
-    f.chunk_map = nullptr;
+    const och::DevFrame f = make_frame(p, cams, n_views, reinterpret_cast<uint32_t *>(p->scratch.d), nullptr, H, 0, 1);
     // The grid kernel writes the costs: every launched workgroup overwrites its 0xFFFFFFFF, so a
     // block the launch did not cover is caught below instead of being read as
     // uninitialised scratch.
-    och::Schedule sc = p->schedule();
-    sc.tile_order = 0;
-    sc.cost = cost;
-    OCH_HIP(hipMemsetAsync(cost, 0xFF, (size_t)n_blocks * 4, p->stream()));
-    OCH_HIP(och::launch_render(p->dev(), f, sc, p->stream()));
-    std::vector<uint32_t> c(n_blocks);
-    OCH_HIP(hipMemcpyAsync(c.data(), cost, (size_t)n_blocks * 4, hipMemcpyDeviceToHost, p->stream()));
-    OCH_HIP(hipStreamSynchronize(p->stream()));
+    std::vector<uint32_t> c;
+    st = cost_render(p, reinterpret_cast<uint32_t *>(p->scratch.d + frame_bytes), n_blocks, c,
+                     [&](const och::Schedule &sc) { return och::launch_render(p->dev(), f, sc, p->stream()); });
+    if (st != OCH_OK) return st;
     for (uint32_t b = 0; b < n_blocks; ++b)
         if (c[b] == 0xFFFFFFFFu) return fail(OCH_E_INVALID, "chunk-cost render left workgroup %u untimed", b);
-    // a workgroup's time spread over its tiles, a tile's over its 8 rows
-    const int n_chunks = (H + row_chunk - 1) / row_chunk;
-    std::vector<double> acc(n_chunks, 0.0);
-    for (uint32_t b = 0; b < n_blocks; ++b)
-        for (uint32_t t = b * per_block; t < std::min(tiles, (b + 1) * per_block); ++t) {
-            const uint32_t ty = (t % (tiles_x * tiles_y)) / tiles_x;
-            const int r0 = (int)ty * 8, r1 = std::min(H, r0 + 8);
-            for (int r = r0; r < r1; ++r) acc[r / row_chunk] += (double)c[b] / per_block / (r1 - r0);
-        }
-    for (int k = 0; k < n_chunks; ++k) costs[k] = (float)acc[k];
+    const std::vector<float> spread = och::plan::spread_chunk_costs(c, n_views, W, H, per_block, row_chunk);
+    std::copy(spread.begin(), spread.end(), costs);
     return OCH_OK;
 }
 
@@ -1850,22 +1904,13 @@ OCH_API int och_gpu_render_steps_dev(och_gpu_pool *p, const och_camera *cams, in
     // The frame loop of update_image (ORT/test_och_h_octree.cpp:437-457), one
     // launch per frame, issued here rather than by the caller's interpreter.
     // The pool's stream is restored afterwards, also after a failure.
-    const bool had_ext = p->use_ext;
-    const hipStream_t prev = p->ext_stream;
+    FrameLoopScope loop{p};
     int st = OCH_OK;
     for (int k = 0; k < n_steps && st == OCH_OK; ++k) {
         const int b = k % n_buffers;
-        p->ext_stream = static_cast<hipStream_t>(streams[b]);
-        p->use_ext = true;
-        if (start_events) {
-            p->next_ev_start = static_cast<hipEvent_t>(start_events[k]);
-            p->next_ev_stop = static_cast<hipEvent_t>(stop_events[k]);
-        }
+        loop.frame(streams[b], start_events, stop_events, k);
         st = render_views(p, cams, n_views, frames[b], row_chunk, 0, 1, bounce != 0);
     }
-    p->next_ev_start = p->next_ev_stop = nullptr;
-    p->ext_stream = prev;
-    p->use_ext = had_ext;
     return st;
 }
 
@@ -1895,10 +1940,7 @@ OCH_API int och_gpu_render_sharded_steps_dev(och_gpu_pool *p, och_comm *comm, co
         if (receives && (!gathered || !gathered[b])) return fail(OCH_E_INVALID, "rank %d needs gathered[%d]", rank, b);
         if (shades && (!frames || !frames[b])) return fail(OCH_E_INVALID, "rank %d needs frames[%d]", rank, b);
     }
-    for (int v = 0; v < n_views; ++v)
-        if (cams[v].width != cams[0].width || cams[v].height != cams[0].height || cams[v].width <= 0 ||
-            cams[v].height <= 0)
-            return fail(OCH_E_INVALID, "views must share one positive width and height");
+    if (int vs = check_views(cams, n_views)) return vs;
     if (shades && !p->d_code_table)
         return fail(OCH_E_INVALID, "no code table: set a palette of at most %d voxel ids", OCH_CODE_MAX_VOXELS);
     const int W = cams[0].width, H = cams[0].height;
@@ -1907,19 +1949,13 @@ OCH_API int och_gpu_render_sharded_steps_dev(och_gpu_pool *p, och_comm *comm, co
     // Per frame: render -> exchange -> shade, all on the frame's stream, so
     // the three are ordered on the device and the host never waits.  A
     // buffer set is reused only behind the previous frame on its stream.
-    const bool had_ext = p->use_ext;
-    const hipStream_t prev = p->ext_stream;
     int st = OCH_OK;
     bool issued = false;                     // a collective of this window is queued
+    FrameLoopScope loop{p};
     for (int k = 0; k < n_steps && st == OCH_OK; ++k) {
         const int b = k % n_buffers;
         const hipStream_t s = static_cast<hipStream_t>(streams[b]);
-        p->ext_stream = s;
-        p->use_ext = true;
-        if (start_events) {
-            p->next_ev_start = static_cast<hipEvent_t>(start_events[k]);
-            p->next_ev_stop = static_cast<hipEvent_t>(stop_events[k]);
-        }
+        loop.frame(streams[b], start_events, stop_events, k);
         st = render_views(p, cams, n_views, nullptr, row_chunk, rank, n_ranks, bounce != 0, slices[b]);
         if (st == OCH_OK) {
             st = exchange == OCH_EXCHANGE_GATHER
@@ -1930,9 +1966,6 @@ OCH_API int och_gpu_render_sharded_steps_dev(och_gpu_pool *p, och_comm *comm, co
         if (st == OCH_OK && shades)
             st = och_gpu_shade_unshard_views_dev(p, gathered[b], frames[b], W, H, row_chunk, n_ranks, n_views);
     }
-    p->next_ev_start = p->next_ev_stop = nullptr;
-    p->ext_stream = prev;
-    p->use_ext = had_ext;
     if (st != OCH_OK && issued) {
         // The peers' collectives of this window can no longer all complete.
         // Aborting here does not unblock the peers: their callers must abort
@@ -1965,7 +1998,7 @@ OCH_API int och_gpu_shade_unshard_views_dev(och_gpu_pool *p, const uint8_t *gath
     DeviceGuard g(p->device);
     OCH_HIP(och::launch_shade_unshard(gathered, frames, p->d_code_table, width, height, row_chunk, n_shards,
                                       p->slice_rows(height, row_chunk, n_shards), n_views,
-                                      p->deal_for(height, row_chunk, n_shards) ? p->d_owner : nullptr, p->stream()));
+                                      p->deal_for(height, row_chunk, n_shards) ? p->d_owner.d : nullptr, p->stream()));
     return OCH_OK;
 }
 
@@ -1986,7 +2019,7 @@ OCH_API int och_gpu_unshard_views_dev(och_gpu_pool *p, const uint32_t *gathered,
     DeviceGuard g(p->device);
     OCH_HIP(och::launch_unshard(gathered, frames, width, height, row_chunk, n_shards,
                                 p->slice_rows(height, row_chunk, n_shards), n_views,
-                                p->deal_for(height, row_chunk, n_shards) ? p->d_owner : nullptr, p->stream()));
+                                p->deal_for(height, row_chunk, n_shards) ? p->d_owner.d : nullptr, p->stream()));
     return OCH_OK;
 }
 
@@ -2005,9 +2038,9 @@ OCH_API int och_gpu_render(och_gpu_pool *p, const och_camera *cam, uint32_t *rgb
     const size_t bytes = (size_t)cam->width * cam->height * 4;
     int st = ensure_scratch(p, bytes);
     if (st != OCH_OK) return st;
-    st = och_gpu_render_dev(p, cam, static_cast<uint32_t *>(p->d_scratch), cam->height, 0, 1);
+    st = och_gpu_render_dev(p, cam, reinterpret_cast<uint32_t *>(p->scratch.d), cam->height, 0, 1);
     if (st != OCH_OK) return st;
-    OCH_HIP(hipMemcpyAsync(rgba, p->d_scratch, bytes, hipMemcpyDeviceToHost, p->stream()));
+    OCH_HIP(hipMemcpyAsync(rgba, p->scratch.d, bytes, hipMemcpyDeviceToHost, p->stream()));
     OCH_HIP(hipStreamSynchronize(p->stream()));
     return OCH_OK;
 }
