@@ -15,13 +15,33 @@
 #include <utility>
 #include <vector>
 
-#include "och_internal.h"
+#include "och_host.h"
+
+using och::check_views;
+using och::DevBuf;
+using och::DeviceGuard;
+using och::fail;
 
 namespace {
 
 constexpr uint32_t kIdLimit = 1u << 24;   // packed ids are 24 bits
 
 thread_local std::string g_error;
+
+}  // namespace
+
+int och::fail(int status, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    g_error = buf;
+    return status;
+}
+
+namespace {
 
 thread_local const char *t_entry = nullptr;     // outermost C-ABI entry of this thread
 
@@ -39,39 +59,6 @@ Discarded &discarded()
     static Discarded d;
     return d;
 }
-
-int fail(int status, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_error = buf;
-    return status;
-}
-
-#define OCH_HIP(expr)                                                                        \
-    do {                                                                                     \
-        const hipError_t e_ = (expr);                                                        \
-        if (e_ != hipSuccess) return fail(OCH_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-// Keep the caller's current device (torch sets one per rank) across calls.
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (dev >= 0 && dev != prev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard()
-    {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
 
 // ------------------------------------------------------------ RCPPS capture
 
@@ -130,37 +117,6 @@ const HostRcp &host_rcp()
     return cap;
 }
 
-// A device buffer that only grows.  A reallocation that fails leaves it empty,
-// so the pointer never names freed memory.
-template <class T>
-struct DevBuf {
-    T *d = nullptr;
-    size_t n = 0;                   // elements allocated
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { (void)release(); }
-    hipError_t release()
-    {
-        n = 0;
-        return d ? hipFree(std::exchange(d, nullptr)) : hipSuccess;
-    }
-    void swap(DevBuf &o) { std::swap(d, o.d); std::swap(n, o.n); }
-    hipError_t reserve(size_t want)
-    {
-        if (want <= n) return hipSuccess;
-        hipError_t e = release();
-        if (e == hipSuccess) e = hipMalloc(&d, want * sizeof(T));
-        if (e == hipSuccess) n = want;
-        return e;
-    }
-    hipError_t upload(const std::vector<T> &v)
-    {
-        const hipError_t e = reserve(v.size());
-        return e != hipSuccess ? e : hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-    }
-};
-
 // One cost-planned launch order (och_gpu_plan_views, och_gpu_plan_batch_tiled)
 // and the launch it was planned for (frame_key, batch_key).
 struct LaunchPlan {
@@ -190,19 +146,19 @@ struct SplitPlan {
 
 struct och_gpu_pool {
     int device = 0;
-    uint32_t *d_nodes = nullptr;    // with one padding node in front for 1-based pools
+    DevBuf<uint32_t> d_nodes;       // with one padding node in front for 1-based pools
     uint32_t n_nodes = 0;           // nodes in d_nodes
     uint32_t root = 0;
     int depth = 0;
     int index_base = 1;
     float miss_t = INFINITY;
-    uint32_t *d_lut = nullptr;
+    DevBuf<uint32_t> d_lut;         // .d: the pool has an RCPPS table
     int lut_log2 = 0;
     uint32_t rcp_xlo = 0, rcp_xspan = 0;   // DevPool::rcp_xlo / rcp_xspan of the uploaded table
     double lut_error = INFINITY;    // maximum relative error of the table (lut_max_rel_error)
-    uint32_t *d_palette = nullptr;
+    DevBuf<uint32_t> d_palette;
     uint32_t n_voxels = 0;
-    uint32_t *d_code_table = nullptr;   // OCH_CODE_* -> RGBA8 (256 words), when n_voxels <= OCH_CODE_MAX_VOXELS
+    DevBuf<uint32_t> d_code_table;  // .d: OCH_CODE_* -> RGBA8 (256 words), when n_voxels <= OCH_CODE_MAX_VOXELS
     hipStream_t own_stream = nullptr;
     hipStream_t ext_stream = nullptr;
     bool use_ext = false;           // och_gpu_set_stream called: ext_stream (NULL = null stream)
@@ -215,7 +171,7 @@ struct och_gpu_pool {
     // host mirror of the uploaded nodes (user numbering), for validating edits
     std::vector<uint32_t> mirror;
     // packed layout (see och_internal.h DevPool)
-    uint32_t *d_packed = nullptr;
+    DevBuf<uint32_t> d_packed;      // .d: a packed layout exists
     uint32_t packed_root = 0;
     uint32_t packed_nodes = 0;
     bool packed_by_slot = false;    // d_packed numbered like d_nodes (editor flushes)
@@ -260,6 +216,14 @@ struct och_gpu_pool {
 
     hipStream_t stream() const { return use_ext ? ext_stream : own_stream; }
 
+    // No packed layout: launches walk the raw one until a new one is in place.
+    hipError_t drop_packed()
+    {
+        packed_nodes = 0;
+        packed_by_slot = false;
+        return d_packed.release();
+    }
+
     och::Schedule schedule() const
     {
         och::Schedule sc = {};          // no order, no cost output, no split, no events
@@ -274,11 +238,11 @@ struct och_gpu_pool {
     och::DevPool dev() const
     {
         och::DevPool p;
-        const bool pk = opt_layout == 1 && d_packed;
-        p.nodes = pk ? d_packed : d_nodes;
+        const bool pk = opt_layout == 1 && d_packed.d;
+        p.nodes = pk ? d_packed.d : d_nodes.d;
         p.n_slots = 8u * (pk ? packed_nodes : n_nodes);
         p.packed = pk ? 1 : 0;
-        p.lut = d_lut;
+        p.lut = d_lut.d;
         p.rcp_xlo = rcp_xlo;
         p.rcp_xspan = rcp_xspan;
         p.root = pk ? packed_root : root;
@@ -315,7 +279,7 @@ int check_ready(const och_gpu_pool *p)
 {
     if (p->torn)
         return fail(OCH_E_INVALID, "pool left half written by a failed och_editor_flush: flush the editor again");
-    if (!p->d_lut) return fail(OCH_E_RCP_MODEL, "no RCPPS table on this pool (call och_gpu_set_rcp_lut)");
+    if (!p->d_lut.d) return fail(OCH_E_RCP_MODEL, "no RCPPS table on this pool (call och_gpu_set_rcp_lut)");
     return OCH_OK;
 }
 
@@ -493,14 +457,10 @@ int upload_packed(och_gpu_pool *p, const uint32_t *nodes, uint32_t n_nodes)
 {
     std::vector<uint32_t> packed;
     uint32_t proot = 0;
-    if (p->d_packed) OCH_HIP(hipFree(p->d_packed));
-    p->d_packed = nullptr;
-    p->packed_nodes = 0;
-    p->packed_by_slot = false;
+    OCH_HIP(p->drop_packed());
     if (!pack_pool(nodes, n_nodes, p->root, p->depth, p->index_base, packed, proot))
         return OCH_OK;   // raw only
-    OCH_HIP(hipMalloc(&p->d_packed, packed.size() * 4));
-    OCH_HIP(hipMemcpy(p->d_packed, packed.data(), packed.size() * 4, hipMemcpyHostToDevice));
+    OCH_HIP(p->d_packed.upload(packed));
     p->packed_root = proot;
     p->packed_nodes = (uint32_t)(packed.size() / 8);
     return OCH_OK;
@@ -526,9 +486,7 @@ double lut_max_rel_error(const uint32_t *lut, int log2_entries)
 int upload_lut(och_gpu_pool *p, const uint32_t *lut, int log2_entries)
 {
     if (!lut || log2_entries < 1 || log2_entries > 23) return fail(OCH_E_INVALID, "bad RCPPS table");
-    if (p->d_lut) OCH_HIP(hipFree(p->d_lut));
-    p->d_lut = nullptr;
-    const size_t bytes = sizeof(uint32_t) << log2_entries;
+    OCH_HIP(p->d_lut.release());       // no table until the new one is in place
     // The device table holds every entry + (127 << 23): the kernels' RCPPS of
     // x = -|d| is then entry - (x's exponent bits) wherever the model's result
     // exponent ent_e + 127 - e stays in 1..254 and the entry is negative -- for
@@ -549,8 +507,7 @@ int upload_lut(och_gpu_pool *p, const uint32_t *lut, int log2_entries)
     const int e_lo = std::max(1, max_e - 127), e_hi = std::min(254, min_e + 126);
     p->rcp_xlo = (uint32_t)e_lo << 23;
     p->rcp_xspan = negative && e_hi >= e_lo ? (uint32_t)(e_hi - e_lo + 1) << 23 : 0u;
-    OCH_HIP(hipMalloc(&p->d_lut, bytes));
-    OCH_HIP(hipMemcpy(p->d_lut, adj.data(), bytes, hipMemcpyHostToDevice));
+    OCH_HIP(p->d_lut.upload(adj));
     p->lut_log2 = log2_entries;
     // camera_proven_miss budgets the table's error; a coarser table leaves
     // every camera ray to the exact ray_cull
@@ -653,11 +610,11 @@ OCH_API int och_gpu_pool_create(const uint32_t *nodes, uint32_t n_nodes, uint32_
     p->miss_t = miss_t;
     p->root = root;
     p->n_nodes = n_nodes + (uint32_t)index_base;   // padding node 0 for 1-based pools
-    const size_t bytes = (size_t)p->n_nodes * 32;
     auto bail = [&](int s) { och_gpu_pool_destroy(p); return s; };
-    if (hipMalloc(&p->d_nodes, bytes) != hipSuccess) return bail(fail(OCH_E_NOMEM, "hipMalloc(%zu) failed", bytes));
-    if (index_base == 1 && hipMemset(p->d_nodes, 0, 32) != hipSuccess) return bail(fail(OCH_E_HIP, "hipMemset failed"));
-    if (hipMemcpy(p->d_nodes + 8 * index_base, nodes, (size_t)n_nodes * 32, hipMemcpyHostToDevice) != hipSuccess)
+    if (p->d_nodes.reserve((size_t)p->n_nodes * 8) != hipSuccess)
+        return bail(fail(OCH_E_NOMEM, "hipMalloc(%zu) failed", (size_t)p->n_nodes * 32));
+    if (index_base == 1 && hipMemset(p->d_nodes.d, 0, 32) != hipSuccess) return bail(fail(OCH_E_HIP, "hipMemset failed"));
+    if (hipMemcpy(p->d_nodes.d + 8 * index_base, nodes, (size_t)n_nodes * 32, hipMemcpyHostToDevice) != hipSuccess)
         return bail(fail(OCH_E_HIP, "node upload failed"));
     p->mirror.assign(nodes, nodes + (size_t)n_nodes * 8);
     set_box(p, nodes, n_nodes);
@@ -685,13 +642,8 @@ OCH_API int och_gpu_pool_destroy(och_gpu_pool *p)
     DeviceGuard g(p->device);
     if (p->own_stream) (void)hipStreamSynchronize(p->own_stream);
     if (p->use_ext) (void)hipStreamSynchronize(p->ext_stream);
-    if (p->d_nodes) (void)hipFree(p->d_nodes);
-    if (p->d_packed) (void)hipFree(p->d_packed);
-    if (p->d_lut) (void)hipFree(p->d_lut);
-    if (p->d_palette) (void)hipFree(p->d_palette);
-    if (p->d_code_table) (void)hipFree(p->d_code_table);
     if (p->h_stage) (void)hipHostFree(p->h_stage);
-    // the scratch, the editor stage, the plans and the row deal's tables: DevBuf, freed by delete below
+    // all device memory is held in DevBufs, freed by delete below (on the pool's device: g)
     if (p->ev_start) (void)hipEventDestroy(p->ev_start);
     if (p->ev_stop) (void)hipEventDestroy(p->ev_stop);
     if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
@@ -708,7 +660,7 @@ OCH_API int och_gpu_pool_info(const och_gpu_pool *p, och_pool_info *info)
     info->depth = p->depth;
     info->index_base = p->index_base;
     info->miss_t = p->miss_t;
-    info->rcp_log2_entries = p->d_lut ? p->lut_log2 : 0;
+    info->rcp_log2_entries = p->d_lut.d ? p->lut_log2 : 0;
     info->device = p->device;
     return OCH_OK;
 }
@@ -739,7 +691,7 @@ OCH_API int och_gpu_pool_update(och_gpu_pool *p, uint32_t first, uint32_t count,
     if (ds != OCH_OK) return ds;
     DeviceGuard g(p->device);
     if (count)
-        OCH_HIP(hipMemcpyAsync(p->d_nodes + 8 * (size_t)(first - lo + p->index_base), p->mirror.data() + off,
+        OCH_HIP(hipMemcpyAsync(p->d_nodes.d + 8 * (size_t)(first - lo + p->index_base), p->mirror.data() + off,
                                (size_t)count * 32, hipMemcpyHostToDevice, p->stream()));
     OCH_HIP(hipStreamSynchronize(p->stream()));
     p->root = root;
@@ -805,7 +757,7 @@ int och::pool_write_slots(och_gpu_pool *p, uint32_t first, uint32_t count, const
     if ((uint64_t)first + count > p->n_nodes || (full && (first != 0 || count != p->n_nodes)))
         return fail(OCH_E_INVALID, "editor window [%u, +%u) outside the pool", first, count);
     if (packed && p->n_nodes > kIdLimit) return fail(OCH_E_INVALID, "packed ids exceed 24 bits");
-    if (packed && !full && (!p->d_packed || !p->packed_by_slot))
+    if (packed && !full && (!p->d_packed.d || !p->packed_by_slot))
         return fail(OCH_E_INVALID, "packed buffer is not in editor numbering");
     DeviceGuard g(p->device);
     p->last_writer = 0;                 // until pool_commit: a failed flush forces a full rewrite
@@ -815,20 +767,17 @@ int och::pool_write_slots(och_gpu_pool *p, uint32_t first, uint32_t count, const
     if (count > skip) {
         const size_t n = (size_t)(count - skip) * 8;
         std::memcpy(p->mirror.data() + (size_t)(lo - 1) * 8, raw + (size_t)skip * 8, n * 4);
-        OCH_HIP(hipMemcpy(p->d_nodes + (size_t)lo * 8, raw + (size_t)skip * 8, n * 4, hipMemcpyHostToDevice));
+        OCH_HIP(hipMemcpy(p->d_nodes.d + (size_t)lo * 8, raw + (size_t)skip * 8, n * 4, hipMemcpyHostToDevice));
     }
     if (!packed) return OCH_OK;
-    if (full && (!p->d_packed || !p->packed_by_slot || p->packed_nodes != p->n_nodes)) {
-        if (p->d_packed) OCH_HIP(hipFree(p->d_packed));
-        p->d_packed = nullptr;
-        p->packed_nodes = 0;
-        p->packed_by_slot = false;
-        OCH_HIP(hipMalloc(&p->d_packed, (size_t)p->n_nodes * 32));
+    if (full && (!p->d_packed.d || !p->packed_by_slot || p->packed_nodes != p->n_nodes)) {
+        OCH_HIP(p->drop_packed());
+        OCH_HIP(p->d_packed.reserve((size_t)p->n_nodes * 8));
         p->packed_nodes = p->n_nodes;
         p->packed_by_slot = true;
     }
     if (count)
-        OCH_HIP(hipMemcpy(p->d_packed + (size_t)first * 8, packed, (size_t)count * 32, hipMemcpyHostToDevice));
+        OCH_HIP(hipMemcpy(p->d_packed.d + (size_t)first * 8, packed, (size_t)count * 32, hipMemcpyHostToDevice));
     return OCH_OK;
 }
 
@@ -836,7 +785,7 @@ int och::pool_scatter_slots(och_gpu_pool *p, const uint32_t *ids, uint32_t count
                             const uint32_t *packed)
 {
     if (!p || p->index_base != 1 || (count && (!ids || !raw))) return fail(OCH_E_INVALID, "bad editor flush");
-    if (packed && (!p->d_packed || !p->packed_by_slot))
+    if (packed && (!p->d_packed.d || !p->packed_by_slot))
         return fail(OCH_E_INVALID, "packed buffer is not in editor numbering");
     if (count == 0) return OCH_OK;
     for (uint32_t i = 0; i < count; ++i)
@@ -863,7 +812,7 @@ int och::pool_scatter_slots(och_gpu_pool *p, const uint32_t *ids, uint32_t count
     uint32_t *stage = p->d_stage.d;
     OCH_HIP(hipMemcpyAsync(stage, p->h_stage, words * 4, hipMemcpyHostToDevice, s));
     OCH_HIP(och::launch_scatter_slots(stage, stage + count, packed ? stage + 9 * (size_t)count : nullptr,
-                                      count, p->d_nodes, packed ? p->d_packed : nullptr, s));
+                                      count, p->d_nodes.d, packed ? p->d_packed.d : nullptr, s));
     OCH_HIP(hipStreamSynchronize(s));
     return OCH_OK;
 }
@@ -872,15 +821,10 @@ int och::pool_commit(och_gpu_pool *p, uint32_t root, uint32_t packed_root, bool 
                      const int32_t *box_lo, const int32_t *box_hi)
 {
     if (!p || p->index_base != 1) return fail(OCH_E_INVALID, "bad editor flush");
-    if (packed && (!p->d_packed || !p->packed_by_slot))
+    if (packed && (!p->d_packed.d || !p->packed_by_slot))
         return fail(OCH_E_INVALID, "packed buffer is not in editor numbering");
     DeviceGuard g(p->device);
-    if (!packed && p->d_packed) {
-        OCH_HIP(hipFree(p->d_packed));
-        p->d_packed = nullptr;
-        p->packed_nodes = 0;
-        p->packed_by_slot = false;
-    }
+    if (!packed) OCH_HIP(p->drop_packed());
     p->root = root;
     p->packed_root = packed ? packed_root : 0;
     p->box_any = box_lo && box_hi;
@@ -898,10 +842,7 @@ int och::pool_mark_torn(och_gpu_pool *p)
     if (!p) return OCH_E_INVALID;
     DeviceGuard g(p->device);
     (void)hipDeviceSynchronize();
-    if (p->d_packed) (void)hipFree(p->d_packed);
-    p->d_packed = nullptr;
-    p->packed_nodes = 0;
-    p->packed_by_slot = false;
+    (void)p->drop_packed();
     p->packed_root = 0;
     p->root = 0;
     p->box_any = false;
@@ -1085,6 +1026,14 @@ std::vector<float> spread_chunk_costs(const std::vector<uint32_t> &c, int n_view
 }  // namespace plan
 }  // namespace och
 
+int och::check_views(const och_camera *cams, int n_views)
+{
+    for (int v = 0; v < n_views; ++v)
+        if (cams[v].width != cams[0].width || cams[v].height != cams[0].height || cams[v].width <= 0 || cams[v].height <= 0)
+            return fail(OCH_E_INVALID, "views must share one positive width and height");
+    return OCH_OK;
+}
+
 namespace {
 
 int tiled_args(const och_gpu_pool *p, const float *origin, int origin_stride, const float *dirs, uint32_t n,
@@ -1115,14 +1064,6 @@ void frame_key(const och_gpu_pool *p, const och::DevFrame &f, bool bounce, int64
     std::memcpy(key, k, sizeof k);
 }
 
-int check_views(const och_camera *cams, int n_views)
-{
-    for (int v = 0; v < n_views; ++v)
-        if (cams[v].width != cams[0].width || cams[v].height != cams[0].height || cams[v].width <= 0 || cams[v].height <= 0)
-            return fail(OCH_E_INVALID, "views must share one positive width and height");
-    return OCH_OK;
-}
-
 // The frame of n_views checked views (check_views) as the kernels take it,
 // with this shard's slice height and, under a row deal, its chunk map.
 och::DevFrame make_frame(const och_gpu_pool *p, const och_camera *cams, int n_views, uint32_t *out, uint8_t *codes,
@@ -1131,7 +1072,7 @@ och::DevFrame make_frame(const och_gpu_pool *p, const och_camera *cams, int n_vi
     och::DevFrame f;
     for (int v = 0; v < n_views; ++v) f.cams[v] = cams[v];
     f.n_views = n_views;
-    f.palette = p->d_palette;
+    f.palette = p->d_palette.d;
     f.n_voxels = p->n_voxels;
     f.out = out;
     f.codes = codes;
@@ -1177,10 +1118,8 @@ OCH_API int och_gpu_set_palette(och_gpu_pool *p, const uint32_t *rgba, uint32_t 
     if (!p || (n_voxels && !rgba)) return fail(OCH_E_INVALID, "pool/palette is NULL");
     DeviceGuard g(p->device);
     OCH_HIP(hipStreamSynchronize(p->stream()));
-    if (p->d_palette) OCH_HIP(hipFree(p->d_palette));
-    if (p->d_code_table) OCH_HIP(hipFree(p->d_code_table));
-    p->d_palette = nullptr;
-    p->d_code_table = nullptr;
+    OCH_HIP(p->d_palette.release());
+    OCH_HIP(p->d_code_table.release());   // no code table unless this palette fits the codes
     p->n_voxels = 0;
     if (n_voxels <= OCH_CODE_MAX_VOXELS) {
         // Indexed-colour frames: trace_pixel's colour per code
@@ -1191,12 +1130,11 @@ OCH_API int och_gpu_set_palette(och_gpu_pool *p, const uint32_t *rgba, uint32_t 
         t[OCH_CODE_SKY] = 0xFFFEBF00u;
         for (uint32_t c = 0; c < OCH_CODE_BLOCKED; ++c)
             t[c | OCH_CODE_BLOCKED] = ((t[c] >> 1) & 0x007F7F7Fu) | (t[c] & 0xFF000000u);
-        OCH_HIP(hipMalloc(&p->d_code_table, 256 * 4));
-        OCH_HIP(hipMemcpy(p->d_code_table, t.data(), 256 * 4, hipMemcpyHostToDevice));
+        OCH_HIP(p->d_code_table.upload(t));
     }
     if (!n_voxels) return OCH_OK;
-    OCH_HIP(hipMalloc(&p->d_palette, (size_t)n_voxels * 6 * 4));
-    OCH_HIP(hipMemcpy(p->d_palette, rgba, (size_t)n_voxels * 6 * 4, hipMemcpyHostToDevice));
+    OCH_HIP(p->d_palette.reserve((size_t)n_voxels * 6));
+    OCH_HIP(hipMemcpy(p->d_palette.d, rgba, (size_t)n_voxels * 6 * 4, hipMemcpyHostToDevice));
     p->n_voxels = n_voxels;
     return OCH_OK;
 }
@@ -1227,7 +1165,7 @@ OCH_API int och_gpu_set_option(och_gpu_pool *p, int option, int value)
         return OCH_OK;
     case OCH_OPT_LAYOUT:
         if (value != 0 && value != 1) return fail(OCH_E_INVALID, "layout must be 0 or 1");
-        if (value == 1 && !p->d_packed) return fail(OCH_E_INVALID, "pool too large for the packed layout");
+        if (value == 1 && !p->d_packed.d) return fail(OCH_E_INVALID, "pool too large for the packed layout");
         p->opt_layout = value;
         return OCH_OK;
     case OCH_OPT_TILE_ORDER:
@@ -1276,7 +1214,7 @@ OCH_API int och_gpu_get_option(const och_gpu_pool *p, int option, int *value)
     if (!p || !value) return fail(OCH_E_INVALID, "NULL argument");
     switch (option) {
     case OCH_OPT_BLOCK: *value = p->opt_block; return OCH_OK;
-    case OCH_OPT_LAYOUT: *value = (p->opt_layout == 1 && p->d_packed) ? 1 : 0; return OCH_OK;
+    case OCH_OPT_LAYOUT: *value = (p->opt_layout == 1 && p->d_packed.d) ? 1 : 0; return OCH_OK;
     case OCH_OPT_TILE_ORDER: *value = p->opt_tile_order; return OCH_OK;
     case OCH_OPT_BOUNCE_COMPACT: *value = p->opt_bounce_compact; return OCH_OK;
     case OCH_OPT_CULL: *value = p->opt_cull; return OCH_OK;
@@ -1610,7 +1548,7 @@ int render_views(och_gpu_pool *p, const och_camera *cams, int n_views, uint32_t 
                  int n_shards, bool bounce, uint8_t *code_slices = nullptr)
 {
     if (!p || !cams || (!rgba_slices && !code_slices)) return fail(OCH_E_INVALID, "NULL argument");
-    if (code_slices && (p->n_voxels > OCH_CODE_MAX_VOXELS || !p->d_code_table))
+    if (code_slices && (p->n_voxels > OCH_CODE_MAX_VOXELS || !p->d_code_table.d))
         return fail(OCH_E_INVALID, "indexed-colour frames need a palette (och_gpu_set_palette) of at most %d voxel ids",
                     OCH_CODE_MAX_VOXELS);
     if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
@@ -1914,13 +1852,13 @@ OCH_API int och_gpu_render_steps_dev(och_gpu_pool *p, const och_camera *cams, in
     return st;
 }
 
-OCH_API int och_gpu_render_sharded_steps_dev(och_gpu_pool *p, och_comm *comm, const och_camera *cams, int n_views,
-                                             int n_steps, void *const *streams, uint8_t *const *slices,
-                                             uint8_t *const *gathered, uint32_t *const *frames, int n_buffers,
-                                             void *const *start_events, void *const *stop_events, int row_chunk,
-                                             int bounce, int exchange)
+}  // extern "C"
+
+int och::sharded_steps(och_gpu_pool *p, och_comm *comm, const och_camera *cams, int n_views, int n_steps,
+                       void *const *streams, uint8_t *const *slices, uint8_t *const *gathered, uint32_t *const *frames,
+                       int n_buffers, void *const *start_events, void *const *stop_events, int row_chunk, int bounce,
+                       int exchange, bool codes)
 {
-    OCH_ENTRY();
     if (!p || !comm || !cams || !streams || !slices) return fail(OCH_E_INVALID, "NULL argument");
     if (n_steps < 0 || n_buffers < 1) return fail(OCH_E_INVALID, "n_steps %d / n_buffers %d", n_steps, n_buffers);
     if (n_views < 1 || n_views > OCH_MAX_VIEWS || row_chunk <= 0) return fail(OCH_E_INVALID, "bad views / row_chunk");
@@ -1941,10 +1879,10 @@ OCH_API int och_gpu_render_sharded_steps_dev(och_gpu_pool *p, och_comm *comm, co
         if (shades && (!frames || !frames[b])) return fail(OCH_E_INVALID, "rank %d needs frames[%d]", rank, b);
     }
     if (int vs = check_views(cams, n_views)) return vs;
-    if (shades && !p->d_code_table)
+    if (codes && shades && !p->d_code_table.d)
         return fail(OCH_E_INVALID, "no code table: set a palette of at most %d voxel ids", OCH_CODE_MAX_VOXELS);
     const int W = cams[0].width, H = cams[0].height;
-    const size_t count = (size_t)n_views * p->slice_rows(H, row_chunk, n_ranks) * W;
+    const size_t bytes = (size_t)n_views * p->slice_rows(H, row_chunk, n_ranks) * W * (codes ? 1 : 4);
     DeviceGuard g(p->device);
     // Per frame: render -> exchange -> shade, all on the frame's stream, so
     // the three are ordered on the device and the host never waits.  A
@@ -1956,15 +1894,18 @@ OCH_API int och_gpu_render_sharded_steps_dev(och_gpu_pool *p, och_comm *comm, co
         const int b = k % n_buffers;
         const hipStream_t s = static_cast<hipStream_t>(streams[b]);
         loop.frame(streams[b], start_events, stop_events, k);
-        st = render_views(p, cams, n_views, nullptr, row_chunk, rank, n_ranks, bounce != 0, slices[b]);
+        st = render_views(p, cams, n_views, codes ? nullptr : reinterpret_cast<uint32_t *>(slices[b]), row_chunk, rank,
+                          n_ranks, bounce != 0, codes ? slices[b] : nullptr);
         if (st == OCH_OK) {
             st = exchange == OCH_EXCHANGE_GATHER
-                     ? och::comm_gather(comm, slices[b], receives ? gathered[b] : nullptr, count, 0, s)
-                     : och::comm_all_gather(comm, slices[b], gathered[b], count, s);
+                     ? och::comm_gather(comm, slices[b], receives ? gathered[b] : nullptr, bytes, 0, s)
+                     : och::comm_all_gather(comm, slices[b], gathered[b], bytes, s);
             issued = issued || st == OCH_OK;
         }
         if (st == OCH_OK && shades)
-            st = och_gpu_shade_unshard_views_dev(p, gathered[b], frames[b], W, H, row_chunk, n_ranks, n_views);
+            st = codes ? och_gpu_shade_unshard_views_dev(p, gathered[b], frames[b], W, H, row_chunk, n_ranks, n_views)
+                       : och_gpu_unshard_views_dev(p, reinterpret_cast<const uint32_t *>(gathered[b]), frames[b], W, H,
+                                                   row_chunk, n_ranks, n_views);
     }
     if (st != OCH_OK && issued) {
         // The peers' collectives of this window can no longer all complete.
@@ -1972,11 +1913,23 @@ OCH_API int och_gpu_render_sharded_steps_dev(och_gpu_pool *p, och_comm *comm, co
         // theirs (bench.py's watchdog, or the process exiting).  A failure
         // before this rank queued any collective leaves the communicator as
         // it was (every rank failing alike keeps a consistent one).
-        const std::string msg = och_last_error();
-        och::comm_abort(comm);
-        return fail(st, "%s (communicator aborted: the window stopped part way)", msg.c_str());
+        och::comm_abort(comm);               // leaves the error text alone
+        return fail(st, "%s (communicator aborted: the window stopped part way)", och_last_error());
     }
     return st;
+}
+
+extern "C" {
+
+OCH_API int och_gpu_render_sharded_steps_dev(och_gpu_pool *p, och_comm *comm, const och_camera *cams, int n_views,
+                                             int n_steps, void *const *streams, uint8_t *const *slices,
+                                             uint8_t *const *gathered, uint32_t *const *frames, int n_buffers,
+                                             void *const *start_events, void *const *stop_events, int row_chunk,
+                                             int bounce, int exchange)
+{
+    OCH_ENTRY();
+    return och::sharded_steps(p, comm, cams, n_views, n_steps, streams, slices, gathered, frames, n_buffers, start_events,
+                              stop_events, row_chunk, bounce, exchange, true);
 }
 
 OCH_API int och_gpu_render_codes_views_dev(och_gpu_pool *p, const och_camera *cams, int n_views, uint8_t *code_slices,
@@ -1993,10 +1946,10 @@ OCH_API int och_gpu_shade_unshard_views_dev(och_gpu_pool *p, const uint8_t *gath
     OCH_ENTRY();
     if (!p || !gathered || !frames || width <= 0 || height <= 0 || row_chunk <= 0 || n_shards <= 0 || n_views < 1)
         return fail(OCH_E_INVALID, "bad unshard arguments");
-    if (!p->d_code_table)
+    if (!p->d_code_table.d)
         return fail(OCH_E_INVALID, "no code table: set a palette of at most %d voxel ids", OCH_CODE_MAX_VOXELS);
     DeviceGuard g(p->device);
-    OCH_HIP(och::launch_shade_unshard(gathered, frames, p->d_code_table, width, height, row_chunk, n_shards,
+    OCH_HIP(och::launch_shade_unshard(gathered, frames, p->d_code_table.d, width, height, row_chunk, n_shards,
                                       p->slice_rows(height, row_chunk, n_shards), n_views,
                                       p->deal_for(height, row_chunk, n_shards) ? p->d_owner.d : nullptr, p->stream()));
     return OCH_OK;

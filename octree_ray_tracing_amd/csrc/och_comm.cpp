@@ -14,12 +14,16 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstring>
 #include <mutex>
 #include <string>
 
-#include "och_internal.h"
+#include "och_host.h"
 #include "och_rccl.h"
+
+using och::DeviceGuard;
+using och::fail;
 
 namespace och {
 
@@ -66,8 +70,11 @@ const Rccl &rccl()
 
 }  // namespace och
 
+// comm is null once aborted or destroyed.  A watchdog thread may abort while
+// the issuing thread fails, aborts or destroys: whoever takes the handle
+// (och::comm_take) is the one to hand it back to RCCL, and every call loads it once.
 struct och_comm {
-    ncclComm_t comm = nullptr;
+    std::atomic<ncclComm_t> comm{nullptr};
     int n_ranks = 0;
     int rank = 0;
     int device = -1;
@@ -77,33 +84,35 @@ namespace {
 
 static_assert(sizeof(ncclUniqueId) == OCH_COMM_ID_BYTES, "OCH_COMM_ID_BYTES must match ncclUniqueId");
 
-int comm_fail(int status, const std::string &msg) { return och::report(status, msg.c_str()); }
+int rccl_fail(const char *what, ncclResult_t r) { return fail(OCH_E_HIP, "%s: %s", what, och::rccl().error_string(r)); }
 
-int rccl_fail(const char *what, ncclResult_t r)
+// The handle, or null with the error text set.
+ncclComm_t live(const och_comm *c)
 {
-    return comm_fail(OCH_E_HIP, std::string(what) + ": " + och::rccl().error_string(r));
+    const ncclComm_t h = c ? c->comm.load() : nullptr;
+    if (!h) fail(OCH_E_INVALID, "communicator is NULL or destroyed");
+    return h;
 }
-
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(int dev)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (dev >= 0 && dev != prev) (void)hipSetDevice(dev);
-    }
-    ~DevGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 }  // namespace
 
 namespace och {
 
+och_comm *comm_adopt(ncclComm_t comm, int n_ranks, int rank, int device)
+{
+    auto *c = new och_comm;
+    c->comm = comm;
+    c->n_ranks = n_ranks;
+    c->rank = rank;
+    c->device = device;
+    return c;
+}
+
+ncclComm_t comm_take(och_comm *c) { return c ? c->comm.exchange(nullptr) : nullptr; }
+
 int comm_ranks(const och_comm *c, int *n_ranks, int *rank, int *device)
 {
-    if (!c || !c->comm) return comm_fail(OCH_E_INVALID, "communicator is NULL or destroyed");
+    if (!live(c)) return OCH_E_INVALID;
     if (n_ranks) *n_ranks = c->n_ranks;
     if (rank) *rank = c->rank;
     if (device) *device = c->device;
@@ -112,8 +121,9 @@ int comm_ranks(const och_comm *c, int *n_ranks, int *rank, int *device)
 
 int comm_all_gather(och_comm *c, const void *send, void *recv, size_t bytes, hipStream_t stream)
 {
-    if (!c || !c->comm) return comm_fail(OCH_E_INVALID, "communicator is NULL or destroyed");
-    const ncclResult_t r = rccl().all_gather(send, recv, bytes, ncclUint8, c->comm, stream);
+    const ncclComm_t h = live(c);
+    if (!h) return OCH_E_INVALID;
+    const ncclResult_t r = rccl().all_gather(send, recv, bytes, ncclUint8, h, stream);
     return r == ncclSuccess ? OCH_OK : rccl_fail("ncclAllGather", r);
 }
 
@@ -122,26 +132,27 @@ int comm_all_gather(och_comm *c, const void *send, void *recv, size_t bytes, hip
 // but the root spends HBM or CUs on receiving.
 int comm_gather(och_comm *c, const void *send, void *recv, size_t bytes, int root, hipStream_t stream)
 {
-    if (!c || !c->comm) return comm_fail(OCH_E_INVALID, "communicator is NULL or destroyed");
-    if (root < 0 || root >= c->n_ranks) return comm_fail(OCH_E_INVALID, "gather root outside the communicator");
+    const ncclComm_t h = live(c);
+    if (!h) return OCH_E_INVALID;
+    if (root < 0 || root >= c->n_ranks) return fail(OCH_E_INVALID, "gather root outside the communicator");
     const Rccl &R = rccl();
     if (c->rank == root) {
-        if (recv == nullptr) return comm_fail(OCH_E_INVALID, "the gather root needs a receive buffer");
+        if (recv == nullptr) return fail(OCH_E_INVALID, "the gather root needs a receive buffer");
         char *dst = static_cast<char *>(recv);
         // One group: a receive from every rank, the root's own slice included
         // (a send to itself), so the same RCCL calls run at every world size --
         // world size 1, the one a one-GPU box can run, exercises them too.
         ncclResult_t r = R.group_start();
         if (r == ncclSuccess && send != dst + (size_t)root * bytes)
-            r = R.send(send, bytes, ncclUint8, root, c->comm, stream);
+            r = R.send(send, bytes, ncclUint8, root, h, stream);
         for (int p = 0; p < c->n_ranks && r == ncclSuccess; ++p)
             if (p != root || send != dst + (size_t)root * bytes)
-                r = R.recv(dst + (size_t)p * bytes, bytes, ncclUint8, p, c->comm, stream);
+                r = R.recv(dst + (size_t)p * bytes, bytes, ncclUint8, p, h, stream);
         const ncclResult_t e = R.group_end();
         if (r == ncclSuccess) r = e;
         return r == ncclSuccess ? OCH_OK : rccl_fail("ncclSend / ncclRecv group", r);
     }
-    const ncclResult_t r = R.send(send, bytes, ncclUint8, root, c->comm, stream);
+    const ncclResult_t r = R.send(send, bytes, ncclUint8, root, h, stream);
     return r == ncclSuccess ? OCH_OK : rccl_fail("ncclSend", r);
 }
 
@@ -151,10 +162,10 @@ int comm_gather(och_comm *c, const void *send, void *recv, size_t bytes, int roo
 // so every later call on it fails instead of issuing.
 void comm_abort(och_comm *c)
 {
-    if (!c || !c->comm) return;
-    DevGuard g(c->device);
-    (void)rccl().comm_abort(c->comm);
-    c->comm = nullptr;
+    const ncclComm_t h = comm_take(c);
+    if (!h) return;
+    DeviceGuard g(c->device);
+    (void)rccl().comm_abort(h);
 }
 
 }  // namespace och
@@ -163,9 +174,9 @@ extern "C" {
 
 OCH_API int och_comm_unique_id(uint8_t *id)
 {
-    if (!id) return comm_fail(OCH_E_INVALID, "NULL id buffer");
+    if (!id) return fail(OCH_E_INVALID, "NULL id buffer");
     const och::Rccl &R = och::rccl();
-    if (!R.ok) return comm_fail(OCH_E_NODEV, R.error);
+    if (!R.ok) return fail(OCH_E_NODEV, "%s", R.error.c_str());
     ncclUniqueId u;
     const ncclResult_t r = R.get_unique_id(&u);
     if (r != ncclSuccess) return rccl_fail("ncclGetUniqueId", r);
@@ -175,35 +186,30 @@ OCH_API int och_comm_unique_id(uint8_t *id)
 
 OCH_API int och_comm_create(const uint8_t *id, int n_ranks, int rank, int device, och_comm **out)
 {
-    if (!id || !out) return comm_fail(OCH_E_INVALID, "NULL argument");
+    if (!id || !out) return fail(OCH_E_INVALID, "NULL argument");
     *out = nullptr;
     if (n_ranks < 1 || rank < 0 || rank >= n_ranks)
-        return comm_fail(OCH_E_INVALID, "rank " + std::to_string(rank) + " of " + std::to_string(n_ranks));
+        return fail(OCH_E_INVALID, "rank %d of %d", rank, n_ranks);
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return comm_fail(OCH_E_NODEV, "no HIP device visible");
-    if (device < 0 || device >= ndev) return comm_fail(OCH_E_NODEV, "device " + std::to_string(device) + " not visible");
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(OCH_E_NODEV, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(OCH_E_NODEV, "device %d not visible", device);
     const och::Rccl &R = och::rccl();
-    if (!R.ok) return comm_fail(OCH_E_NODEV, R.error);
+    if (!R.ok) return fail(OCH_E_NODEV, "%s", R.error.c_str());
     ncclUniqueId u;
     std::memcpy(&u, id, sizeof u);
-    DevGuard g(device);
+    DeviceGuard g(device);
     ncclComm_t comm = nullptr;
     // Collective over the ranks: returns once every rank has joined.
     const ncclResult_t r = R.comm_init_rank(&comm, n_ranks, u, rank);
     if (r != ncclSuccess) return rccl_fail("ncclCommInitRank", r);
-    auto *c = new och_comm;
-    c->comm = comm;
-    c->n_ranks = n_ranks;
-    c->rank = rank;
-    c->device = device;
-    *out = c;
+    *out = och::comm_adopt(comm, n_ranks, rank, device);
     return OCH_OK;
 }
 
 OCH_API int och_comm_available(void)
 {
     const och::Rccl &R = och::rccl();
-    return R.ok ? OCH_OK : comm_fail(OCH_E_NODEV, R.error);
+    return R.ok ? OCH_OK : fail(OCH_E_NODEV, "%s", R.error.c_str());
 }
 
 // For a watchdog on another thread: a collective that never completes (a peer
@@ -212,7 +218,7 @@ OCH_API int och_comm_available(void)
 // valid for och_comm_destroy; every later call on it fails.
 OCH_API int och_comm_abort(och_comm *c)
 {
-    if (!c) return comm_fail(OCH_E_INVALID, "NULL communicator");
+    if (!c) return fail(OCH_E_INVALID, "NULL communicator");
     och::comm_abort(c);
     return OCH_OK;
 }
@@ -220,9 +226,9 @@ OCH_API int och_comm_abort(och_comm *c)
 OCH_API int och_comm_destroy(och_comm *c)
 {
     if (!c) return OCH_OK;
-    if (c->comm) {
-        DevGuard g(c->device);
-        (void)och::rccl().comm_destroy(c->comm);
+    if (const ncclComm_t h = och::comm_take(c)) {
+        DeviceGuard g(c->device);
+        (void)och::rccl().comm_destroy(h);
     }
     delete c;
     return OCH_OK;
@@ -235,15 +241,15 @@ OCH_API int och_comm_info(const och_comm *c, int *n_ranks, int *rank, int *devic
 
 OCH_API int och_comm_all_gather(och_comm *c, const void *send, void *recv, size_t bytes, void *stream)
 {
-    if (bytes && (!send || !recv)) return comm_fail(OCH_E_INVALID, "NULL buffer");
-    DevGuard g(c ? c->device : -1);
+    if (bytes && (!send || !recv)) return fail(OCH_E_INVALID, "NULL buffer");
+    DeviceGuard g(c ? c->device : -1);
     return och::comm_all_gather(c, send, recv, bytes, static_cast<hipStream_t>(stream));
 }
 
 OCH_API int och_comm_gather(och_comm *c, const void *send, void *recv, size_t bytes, int root, void *stream)
 {
-    if (bytes && !send) return comm_fail(OCH_E_INVALID, "NULL send buffer");
-    DevGuard g(c ? c->device : -1);
+    if (bytes && !send) return fail(OCH_E_INVALID, "NULL send buffer");
+    DeviceGuard g(c ? c->device : -1);
     return och::comm_gather(c, send, recv, bytes, root, static_cast<hipStream_t>(stream));
 }
 

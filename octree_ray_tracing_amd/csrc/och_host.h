@@ -1,0 +1,99 @@
+// och_host.h -- the host layer's shared plumbing (och_api.cpp, och_group.cpp,
+// och_comm.cpp): the error text, the device guard, the device-memory owner
+// and the internal entry points these files call in each other.  Host only,
+// not part of the public ABI.
+//
+// The Makefile's dependency lists do not name this header: after editing it,
+// run `make clean` or touch the .cpp files.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <utility>
+#include <vector>
+
+#include "och_internal.h"
+
+typedef struct ncclComm *ncclComm_t;    // as <rccl/rccl.h> declares it
+
+namespace och {
+
+// Record the formatted text as och_last_error's (this thread's) and return
+// status (och_api.cpp, beside the text; och::report is its one-string form).
+int fail(int status, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+#define OCH_HIP(expr)                                                                             \
+    do {                                                                                          \
+        const hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess) return och::fail(OCH_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+// Keep the caller's current device (torch sets one per rank) across calls.
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int dev)
+    {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (dev >= 0 && dev != prev) ok = hipSetDevice(dev) == hipSuccess;
+    }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+    ~DeviceGuard()
+    {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+// A device buffer that only grows.  A reallocation that fails leaves it empty,
+// so the pointer never names freed memory.
+template <class T>
+struct DevBuf {
+    T *d = nullptr;
+    size_t n = 0;                   // elements allocated
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { (void)release(); }
+    hipError_t release()
+    {
+        n = 0;
+        return d ? hipFree(std::exchange(d, nullptr)) : hipSuccess;
+    }
+    void swap(DevBuf &o) { std::swap(d, o.d); std::swap(n, o.n); }
+    hipError_t reserve(size_t want)
+    {
+        if (want <= n) return hipSuccess;
+        hipError_t e = release();
+        if (e == hipSuccess) e = hipMalloc(&d, want * sizeof(T));
+        if (e == hipSuccess) n = want;
+        return e;
+    }
+    hipError_t upload(const std::vector<T> &v)
+    {
+        const hipError_t e = reserve(v.size());
+        return e != hipSuccess ? e : hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    }
+};
+
+// n_views views of one positive width and height (och_api.cpp).
+int check_views(const och_camera *cams, int n_views);
+
+// och_gpu_render_sharded_steps_dev's window (och_api.cpp), for the frame group
+// too: per frame render this rank's slices, exchange, shade, all on the
+// frame's stream.  codes: the slices travel as 1-byte colour codes and the
+// shade needs the pool's code table; otherwise as RGBA8 words (slices and
+// gathered then hold 4 bytes a pixel) and the frames are only unsharded.
+int sharded_steps(och_gpu_pool *pool, och_comm *comm, const och_camera *cams, int n_views, int n_steps,
+                  void *const *streams, uint8_t *const *slices, uint8_t *const *gathered, uint32_t *const *frames,
+                  int n_buffers, void *const *start_events, void *const *stop_events, int row_chunk, int bounce,
+                  int exchange, bool codes);
+
+// An och_comm around an RCCL communicator the caller made (och_comm.cpp).
+och_comm *comm_adopt(ncclComm_t comm, int n_ranks, int rank, int device);
+// The communicator's handle, leaving null behind: of the threads that ask, one
+// gets it and with it the duty to abort or destroy it; the och_comm then
+// reports itself destroyed.
+ncclComm_t comm_take(och_comm *comm);
+
+}  // namespace och

@@ -452,14 +452,12 @@ def display_weight(world: int, exchange: str = "all_gather") -> float:
     return max(0.5, 1.0 - (0.0625 if exchange == "gather" else 0.05) * world)
 
 
-# The heavy-tile split (OCH_OPT_SPLIT) by world size: a lone
-# launch no longer waits on its longest rays, but the split waves cost
-# throughput, so it pays where a rank's launches are small and end on their
-# tails (tools/split_sweep.sh, profiles/r06/).  World sizes not listed: off.
 # The heavy-tile split by world size (bench.py sweeps): at N = 1
 # the costliest tiles only (T 80: +1.2 % over the 20-step window, -0.4 %
 # sustained, a lone frame 0.19 -> 0.16 ms; profiles/r06/r06ah/), off at N = 2 and
 # 4 (a tie), T 60 from N = 8, whose half-size launches end on their tails.
+# split_defaults takes the entry of the nearest listed world size at or below
+# the asked one (so N = 4 takes N = 2's, N = 16 takes N = 8's).
 SPLIT_DEFAULTS = {1: {"split": 80, "split_segs": 4, "split_level": 6}, 2: {"split": 0},
                   8: {"split": 60, "split_segs": 4, "split_level": 6}}
 

@@ -4,6 +4,8 @@ one process, ncclCommInitAll over the devices, RCCL all-gather of the slices).
 On the one-GPU test box the group has one device: the RCCL communicator, the
 all-gather and the shade + unshard still run, and the frames must equal the
 oracle's (and the single-pool render's) bit for bit."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -95,4 +97,77 @@ def test_group_checks_before_queueing(ort, O, gpu_device):
     for v, p in enumerate(PITCHES):
         r = O.trace_batch(ref_pool, O.Rcp(None), ORIGIN, O.raygen(0.3, p, 1.25, 64, 40))
         assert np.array_equal(got[v], O.shade(r["dir"], r["voxel"], pal).reshape(40, 64))
+    g.close()
+
+
+@pytest.fixture(scope="module")
+def small_scene(ort, O):
+    """Depth 6, two 64x40 views: the tree, the cameras and the oracle's hit records (dir, voxel) per view."""
+    tree = ort.build_terrain(6)
+    cams = [ort.camera(tuple(ORIGIN), 0.3, p, 1.25, 64, 40) for p in PITCHES]
+    ref_pool = O.OraclePool(tree.nodes, tree.root, 6, 1)
+    hits = []
+    for p in PITCHES:
+        r = O.trace_batch(ref_pool, O.Rcp(None), ORIGIN, O.raygen(0.3, p, 1.25, 64, 40))
+        hits.append((r["dir"].copy(), r["voxel"].copy()))
+    return tree, cams, hits
+
+
+@pytest.mark.gpu
+def test_palette_regrow(ort, O, gpu_device, small_scene):
+    """The palette and the code table are released, not shrunk, when a palette
+    no longer fits the colour codes: a 24-id palette leaves no code table (the
+    codes path refuses), the RGBA8 path shades with it, and the small palette
+    brings the codes path back, each frame equal to the oracle's."""
+    import torch
+    from octree_ray_tracing_amd.frame import ShardedFrame
+    tree, cams, hits = small_scene
+    pal = ort.VoxelData().get_colours()
+    big = np.resize(pal[::-1], 6 * 24)           # other colours than pal's for the ids the scene holds
+    assert pal.size // 6 <= 20 < big.size // 6   # OCH_CODE_MAX_VOXELS
+    want = {name: [O.shade(d, v, colours).reshape(40, 64) for d, v in hits] for name, colours in (("pal", pal), ("big", big))}
+    assert not np.array_equal(want["pal"][1], want["big"][1])
+
+    def codes_frames(pool):
+        frames = ShardedFrame(pool, 64, 40, 8, n_views=2, indexed=True).render(cams)
+        torch.cuda.synchronize()
+        return frames.cpu().numpy().view(np.uint32)
+
+    with ort.HOctree(tree.nodes, tree.root, 6, device=0) as pool:
+        pool.set_palette(pal)
+        got = codes_frames(pool)
+        for v in range(2):
+            assert np.array_equal(got[v], want["pal"][v]), ("codes", v)
+        pool.set_palette(big)
+        codes = torch.empty((2, 40, 64), dtype=torch.uint8, device="cuda")
+        with pytest.raises(ort.OchError):
+            pool.render_codes_views_dev(cams, codes, 8, 0, 1)
+        for v in range(2):
+            assert np.array_equal(pool.render(cams[v]), want["big"][v]), ("rgba", v)
+        pool.set_palette(pal)
+        got = codes_frames(pool)
+        for v in range(2):
+            assert np.array_equal(got[v], want["pal"][v]), ("codes again", v)
+
+
+@pytest.mark.gpu
+def test_group_restores_pool_stream(ort, O, gpu_device, small_scene):
+    """After a window of group frames each replica enqueues on the stream it
+    had before, not on one of the group's: a plain render on the replica and
+    the group's last frame both equal the oracle's, and the group closes."""
+    tree, cams, hits = small_scene
+    pal = ort.VoxelData().get_colours()
+    want = [O.shade(d, v, pal).reshape(40, 64) for d, v in hits]
+    g = ort.FrameGroup(tree.nodes, tree.root, 6, devices=[0])
+    g.set_palette(pal)
+    g.render_steps(cams, 3, n_buffers=2)
+    g.synchronize()
+    replica = C.c_void_p()
+    ort._lib.call("och_frame_group_pool", g._h, 0, C.byref(replica))
+    out = np.empty((40, 64), np.uint32)
+    ort._lib.call("och_gpu_render", replica, C.byref(cams[1]), out.ctypes.data)
+    assert np.array_equal(out, want[1])
+    got = g.download(0)
+    for v in range(2):
+        assert np.array_equal(got[v], want[v]), v
     g.close()
