@@ -4,10 +4,14 @@
 // Also traces the reference's per-frame pick ray (ORT/test_och_h_octree.cpp:527-536)
 // through the reference signature, tree.sse_trace(o, d, dir&, voxel&, t&).
 //
-//   make -C examples && ./examples/render_frame 10 out.ppm [width height yaw pitch]
+//   make -C examples && ./examples/render_frame 10 out.ppm [width height yaw pitch] [--ssaa S]
+//
+// --ssaa S (2, 4 or 8, anywhere on the line): the same width x height frame
+// from S x S samples per pixel, resolved in the render kernel (tree.render_ssaa).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "och_gpu.hpp"
@@ -15,6 +19,14 @@
 
 int main(int argc, char **argv)
 {
+    int ssaa = 0;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (std::strcmp(argv[i], "--ssaa") == 0) {      // taken out of the positional arguments
+            ssaa = std::atoi(argv[i + 1]);
+            for (int k = i; k + 2 < argc; ++k) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     const int depth = argc > 1 ? std::atoi(argv[1]) : 10;
     const char *path = argc > 2 ? argv[2] : "frame.ppm";
     och::gpu::camera cam;
@@ -29,9 +41,16 @@ int main(int argc, char **argv)
     try {
         och::gpu::tree tree(hp.nodes, hp.n_nodes, hp.root, hp.depth);
         tree.set_palette(examples::reference_palette());
-        const och_camera c = cam.update_position();
         std::vector<uint32_t> rgba((size_t)cam.width * cam.height);
-        tree.render(c, rgba.data());
+        if (ssaa) {
+            och::gpu::camera samples = cam;             // the sample grid's camera
+            samples.width *= ssaa;
+            samples.height *= ssaa;
+            tree.render_ssaa(samples.update_position(), ssaa, rgba);
+            std::printf("%d x %d samples per pixel\n", ssaa, ssaa);
+        } else {
+            tree.render(cam.update_position(), rgba.data());
+        }
         // pick ray along the view direction (the demo traces camera.pos along its look vector)
         const float dx = cosf(cam.yaw) * cosf(cam.pitch), dy = sinf(cam.yaw) * cosf(cam.pitch), dz = sinf(cam.pitch);
         och::gpu::direction dir;

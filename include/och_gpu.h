@@ -316,6 +316,25 @@ OCH_API int och_gpu_plan_views(och_gpu_pool *pool, const och_camera *cams, int n
  * halved (RGB >> 1, alpha kept) when the secondary ray is blocked. */
 OCH_API int och_gpu_render_bounce_views_dev(och_gpu_pool *pool, const och_camera *cams, int n_views,
                                             uint32_t *rgba_slices, int row_chunk, int shard, int n_shards);
+/* Supersampled frames, s x s samples per pixel (s = 2, 4 or 8), resolved in
+ * the render kernel: cams are the cameras of the sample grid (equal width and
+ * height, both multiples of s), and view v's frame of (width / s) x (height / s)
+ * RGBA8 words goes to rgba + v * (width / s) * (height / s).  With F the frame
+ * och_gpu_render_views_dev writes for the same cameras (one shard), each byte is
+ *   out[Y][X].c = (sum over j, i < s of F[s Y + j][s X + i].c + s * s / 2) >> (2 log2 s):
+ * the box mean of the stored 8-bit channels, rounded half up; no gamma, no
+ * jitter, alpha 0xFF.  capacity_pixels is what rgba holds, in pixels; a smaller
+ * buffer, another s, a size that is no multiple of s, views of unequal size
+ * and a pool left torn by a failed flush are refused (OCH_E_INVALID) before
+ * anything is written.  One shard, whole frames; launch options change the
+ * dispatch only (OCH_OPT_TILE_ORDER 2 uses och_gpu_plan_views' plan for these
+ * cameras with row_chunk = height, never its split form).
+ * _views_dev: device buffer, asynchronous on the pool's stream;
+ * och_gpu_render_ssaa: one camera into a host buffer, synchronous. */
+OCH_API int och_gpu_render_ssaa_views_dev(och_gpu_pool *pool, const och_camera *cams, int n_views, int s,
+                                          uint32_t *rgba, size_t capacity_pixels);
+OCH_API int och_gpu_render_ssaa(och_gpu_pool *pool, const och_camera *cam, int s, uint32_t *rgba,
+                                size_t capacity_pixels);
 /* The frame loop (update_image once per frame, ORT/test_och_h_octree.cpp:
  * 437-457) issued natively: n_steps whole frames of the same cameras
  * (och_gpu_render_views_dev, or _bounce_views_dev with bounce = 1; one shard),

@@ -104,6 +104,20 @@ public:
     // (memcpy it into GetDrawTarget()->GetData(), olcPixelGameEngine.h:945).
     void render(const och_camera &cam, uint32_t *rgba) const { check(och_gpu_render(pool_, &cam, rgba), "och_gpu_render"); }
 
+    // The same frame supersampled: cam is the camera of the sample grid (width
+    // and height multiples of s = 2, 4 or 8), rgba takes (width / s) x
+    // (height / s) pixels, each the rounded mean of its s x s samples
+    // (och_gpu_render_ssaa).
+    void render_ssaa(const och_camera &cam, int s, std::vector<uint32_t> &rgba) const
+    {
+        rgba.resize(static_cast<size_t>(cam.width / (s > 0 ? s : 1)) * static_cast<size_t>(cam.height / (s > 0 ? s : 1)));
+        check(och_gpu_render_ssaa(pool_, &cam, s, rgba.data(), rgba.size()), "och_gpu_render_ssaa");
+    }
+    void render_ssaa(const och_camera &cam, int s, uint32_t *rgba, size_t capacity_pixels) const
+    {
+        check(och_gpu_render_ssaa(pool_, &cam, s, rgba, capacity_pixels), "och_gpu_render_ssaa");
+    }
+
     och_gpu_pool *handle() const { return pool_; }
 
 private:

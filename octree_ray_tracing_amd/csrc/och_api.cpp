@@ -1544,6 +1544,31 @@ OCH_API int och_shard_rows(int height, int row_chunk, int n_shards)
 
 namespace {
 
+// The launch order of frame f under OCH_OPT_TILE_ORDER 2 / 3: the pool's plan
+// (och_gpu_plan_views) when it was made for this geometry, else none (natural
+// order).  split: the launch can run the plan's split form (the grid kernel);
+// without it the order stays an unsplit permutation of the frame's grid.
+void use_plan(const och_gpu_pool *p, const och::DevFrame &f, bool bounce, bool split, och::Schedule &sc)
+{
+    const LaunchPlan &plan = p->plans[bounce ? 1 : 0];
+    if (p->opt_tile_order < 2 || !plan.order.d) return;
+    int64_t key[9];
+    frame_key(p, f, bounce, key);
+    if (!plan.matches(key)) return;
+    sc.order = p->opt_tile_order == 3 ? plan.order_xcd.d : plan.order.d;
+    sc.order_n = plan.blocks;
+    // the plan's split form, while the options it was made with hold
+    const SplitPlan &sp = p->split;
+    if (split && !bounce && p->opt_tile_order == 2 && sp.n && p->dev().packed && p->opt_split == sp.params[0] &&
+        p->opt_split_segs == sp.params[1] && p->opt_split_level == sp.params[2]) {
+        sc.order = sp.order.d;
+        sc.order_n = sp.n;
+        sc.split_extra = sp.extra;
+        sc.split_tasks = sp.tasks.d;
+        sc.split_level = (uint32_t)p->opt_split_level;
+    }
+}
+
 int render_views(och_gpu_pool *p, const och_camera *cams, int n_views, uint32_t *rgba_slices, int row_chunk, int shard,
                  int n_shards, bool bounce, uint8_t *code_slices = nullptr)
 {
@@ -1563,25 +1588,7 @@ int render_views(och_gpu_pool *p, const och_camera *cams, int n_views, uint32_t 
     int ts;
     och::Schedule sc = timed_schedule(p, ts);
     if (ts) return ts;
-    const LaunchPlan &plan = p->plans[bounce ? 1 : 0];
-    if (p->opt_tile_order >= 2 && plan.order.d) {
-        int64_t key[9];
-        frame_key(p, f, bounce, key);
-        if (plan.matches(key)) {
-            sc.order = p->opt_tile_order == 3 ? plan.order_xcd.d : plan.order.d;
-            sc.order_n = plan.blocks;
-            // the plan's split form, while the options it was made with hold
-            const SplitPlan &sp = p->split;
-            if (!bounce && p->opt_tile_order == 2 && sp.n && p->dev().packed && p->opt_split == sp.params[0] &&
-                p->opt_split_segs == sp.params[1] && p->opt_split_level == sp.params[2]) {
-                sc.order = sp.order.d;
-                sc.order_n = sp.n;
-                sc.split_extra = sp.extra;
-                sc.split_tasks = sp.tasks.d;
-                sc.split_level = (uint32_t)p->opt_split_level;
-            }
-        }
-    }
+    use_plan(p, f, bounce, true, sc);
     if (code_slices)
         OCH_HIP(och::launch_render_codes(p->dev(), f, sc, bounce, p->stream()));
     else if (bounce)
@@ -1828,6 +1835,34 @@ OCH_API int och_gpu_render_bounce_views_dev(och_gpu_pool *p, const och_camera *c
     return render_views(p, cams, n_views, rgba_slices, row_chunk, shard, n_shards, true);
 }
 
+OCH_API int och_gpu_render_ssaa_views_dev(och_gpu_pool *p, const och_camera *cams, int n_views, int s, uint32_t *rgba,
+                                          size_t capacity_pixels)
+{
+    OCH_ENTRY();
+    // every refusal comes before anything is written or launched
+    if (!p || !cams || !rgba) return fail(OCH_E_INVALID, "NULL argument");
+    if (s != 2 && s != 4 && s != 8) return fail(OCH_E_INVALID, "samples per axis %d: must be 2, 4 or 8", s);
+    if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
+    if (int vs = check_views(cams, n_views)) return vs;
+    const int Ws = cams[0].width, Hs = cams[0].height;
+    if (Ws % s || Hs % s) return fail(OCH_E_INVALID, "sample grid %d x %d is not a multiple of %d", Ws, Hs, s);
+    if ((uint64_t)Ws * Hs * n_views >= (1ull << 32)) return fail(OCH_E_INVALID, "frame too large");
+    const size_t pixels = (size_t)n_views * (Ws / s) * (Hs / s);
+    if (capacity_pixels < pixels)
+        return fail(OCH_E_INVALID, "rgba holds %zu pixels, %d views of %d x %d need %zu", capacity_pixels, n_views, Ws / s,
+                    Hs / s, pixels);
+    if (int rs = check_ready(p)) return rs;
+    DeviceGuard g(p->device);
+    // the sample grid as the 1-sample render's whole frame: its plan, never the split form
+    const och::DevFrame f = make_frame(p, cams, n_views, rgba, nullptr, Hs, 0, 1);
+    int ts;
+    och::Schedule sc = timed_schedule(p, ts);
+    if (ts) return ts;
+    use_plan(p, f, false, false, sc);
+    OCH_HIP(och::launch_render_ssaa(p->dev(), f, sc, s == 2 ? 1 : s == 4 ? 2 : 3, p->stream()));
+    return timed_done(p, sc, true);
+}
+
 OCH_API int och_gpu_render_steps_dev(och_gpu_pool *p, const och_camera *cams, int n_views, int n_steps,
                                      void *const *streams, uint32_t *const *frames, int n_buffers,
                                      void *const *start_events, void *const *stop_events, int row_chunk, int bounce)
@@ -1994,6 +2029,30 @@ OCH_API int och_gpu_render(och_gpu_pool *p, const och_camera *cam, uint32_t *rgb
     st = och_gpu_render_dev(p, cam, reinterpret_cast<uint32_t *>(p->scratch.d), cam->height, 0, 1);
     if (st != OCH_OK) return st;
     OCH_HIP(hipMemcpyAsync(rgba, p->scratch.d, bytes, hipMemcpyDeviceToHost, p->stream()));
+    OCH_HIP(hipStreamSynchronize(p->stream()));
+    return OCH_OK;
+}
+
+OCH_API int och_gpu_render_ssaa(och_gpu_pool *p, const och_camera *cam, int s, uint32_t *rgba, size_t capacity_pixels)
+{
+    OCH_ENTRY();
+    if (!p || !cam || !rgba) return fail(OCH_E_INVALID, "NULL argument");
+    if (s != 2 && s != 4 && s != 8) return fail(OCH_E_INVALID, "samples per axis %d: must be 2, 4 or 8", s);
+    if (int vs = check_views(cam, 1)) return vs;
+    if (cam->width % s || cam->height % s)
+        return fail(OCH_E_INVALID, "sample grid %d x %d is not a multiple of %d", cam->width, cam->height, s);
+    if (int rs = check_ready(p)) return rs;
+    // refused before the staging buffer is sized; the device form checks again
+    const size_t pixels = (size_t)(cam->width / s) * (size_t)(cam->height / s);
+    if (capacity_pixels < pixels)
+        return fail(OCH_E_INVALID, "rgba holds %zu pixels, %d x %d need %zu", capacity_pixels, cam->width / s,
+                    cam->height / s, pixels);
+    DeviceGuard g(p->device);
+    int st = ensure_scratch(p, pixels * 4 + 4);
+    if (st != OCH_OK) return st;
+    st = och_gpu_render_ssaa_views_dev(p, cam, 1, s, reinterpret_cast<uint32_t *>(p->scratch.d), pixels);
+    if (st != OCH_OK) return st;
+    OCH_HIP(hipMemcpyAsync(rgba, p->scratch.d, pixels * 4, hipMemcpyDeviceToHost, p->stream()));
     OCH_HIP(hipStreamSynchronize(p->stream()));
     return OCH_OK;
 }

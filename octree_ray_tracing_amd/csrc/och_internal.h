@@ -189,6 +189,12 @@ hipError_t launch_trace_bounce_batch(const DevPool &p, const float *origin, int 
 hipError_t launch_render_bounce(const DevPool &p, const DevFrame &f, const Schedule &sc, hipStream_t stream);
 hipError_t launch_raygen(const och_camera &cam, float *dirs, hipStream_t stream);
 hipError_t launch_render(const DevPool &p, const DevFrame &f, const Schedule &sc, hipStream_t stream);
+// Supersampled frames (k_trace_ssaa): f's cameras are the sample grid, one
+// shard's whole frame (row_chunk = height), width and height multiples of
+// s = 1 << log2_s (1..3); f.out holds n_views * (width / s) * (height / s)
+// words, each the rounded mean of its s x s samples.  Uses sc.order only when
+// it is an unsplit permutation of the 1-sample render's grid.
+hipError_t launch_render_ssaa(const DevPool &p, const DevFrame &f, const Schedule &sc, int log2_s, hipStream_t stream);
 // The split planner's counting render: each pixel's walked PUSH count (16 bits)
 // into push, indexed as the frame's slices.
 hipError_t launch_render_push(const DevPool &p, const DevFrame &f, const Schedule &sc, uint16_t *push, hipStream_t stream);

@@ -1205,6 +1205,96 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_grid(DevPool P, Src
     if (stamps) stamp(stamps, stamp_cap, t0, 64);
 }
 
+// Lane `lane ^ kBit`'s value of v, all 64 lanes active: DPP inside a quad
+// (bits 0, 1) and inside a row of 16 lanes (bit 3: row_ror:8), the swizzle
+// crossbar inside 32 lanes (bits 2, 4: ds_swizzle's bit mode, no LDS memory),
+// v_permlane32_swap across the halves (bit 5; only lanes 0..31 get their
+// partner's value, which is all the reduction below reads).
+template <uint32_t kBit>
+__device__ __forceinline__ uint32_t lane_xor(uint32_t v)
+{
+    if constexpr (kBit == 1u)
+        return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);      // quad_perm:[1,0,3,2]
+    else if constexpr (kBit == 2u)
+        return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);      // quad_perm:[2,3,0,1]
+    else if constexpr (kBit == 8u)
+        return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, true);     // row_ror:8
+    else if constexpr (kBit == 4u || kBit == 16u)
+        return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (int)(0x1Fu | (kBit << 10)));  // and 0x1F, xor kBit
+    else {
+        static_assert(kBit == 32u, "a lane bit");
+        return __builtin_amdgcn_permlane32_swap(v, v, false, false)[1];
+    }
+}
+
+// Sum of v over the lanes of this lane's s x s sample block, s = 1 << kLog2S:
+// lane = 8 * tile row + tile column, so the block's lanes differ in the low
+// kLog2S bits of each 3-bit half -- butterfly adds over those bits.  v holds
+// two 16-bit sums (64 * 255 < 2^16), so the halves never carry into each other.
+template <int kLog2S>
+__device__ __forceinline__ uint32_t block_sum(uint32_t v)
+{
+    v += lane_xor<1u>(v);
+    v += lane_xor<8u>(v);
+    if constexpr (kLog2S >= 2) {
+        v += lane_xor<2u>(v);
+        v += lane_xor<16u>(v);
+    }
+    if constexpr (kLog2S >= 3) {
+        v += lane_xor<4u>(v);
+        v += lane_xor<32u>(v);
+    }
+    return v;
+}
+
+// Supersampled frames (och_gpu_render_ssaa_views_dev): the
+// cameras are the sample grid, s x s samples (s = 1 << kLog2S = 2, 4, 8) per
+// output pixel, each the colour k_trace_grid's FrameSink would store; the
+// output word is their per-channel mean, rounded half up.  A wave's 8x8 tile
+// holds (8 / s)^2 whole sample blocks, so the samples stay in registers: the
+// block's lanes add up their unpacked colours across lanes and its top-left
+// lane stores the one word.  Whole frames of one shard only (slice row = row).
+// The sample grid's width and height are multiples of s and tile origins are
+// multiples of 8, so an s x s block lies wholly inside the frame or wholly
+// outside it: lanes without a pixel add 0 to blocks nobody stores.
+template <int kPacked, int kLog2S>
+__global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_ssaa(DevPool P, CameraSource S, FrameSink K, uint32_t xcd_group,
+                                                                  const uint32_t *__restrict__ order, uint64_t *stamps,
+                                                                  uint32_t stamp_cap)
+{
+    extern __shared__ uint32_t lds_stack[];
+    constexpr uint32_t kS = 1u << kLog2S;
+    const uint64_t t0 = stamps ? realtime() : 0;
+    const uint32_t blk = order ? order[blockIdx.x] : xcd_block(blockIdx.x, gridDim.x, xcd_group);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave_base = blk * blockDim.x + (threadIdx.x & ~63u);
+    float o[3], d[3];
+    uint32_t out, word = ~0u, colour = 0;
+    bool miss;
+    if (wave_base + lane < S.count() && S.get_wave_culled(wave_base, lane, P, P.cull != 0, o, d, out, miss)) {
+        // this sample's output word: view * W * H + Y * W + X
+        uint32_t view, tx, ty;
+        S.tile_of(__builtin_amdgcn_readfirstlane(wave_base), view, tx, ty);
+        const uint32_t w = (uint32_t)S.width >> kLog2S, h = (uint32_t)S.height >> kLog2S;
+        word = (view * h + ((ty * kTileH + lane / kTileW) >> kLog2S)) * w + ((tx * kTileW + lane % kTileW) >> kLog2S);
+        if (miss) {                                 // proven before setup: the sky
+            colour = pixel_colour(Hit{OCH_EXIT, 0u, P.miss_bits, 0u}, K.palette, K.n_voxels);
+        } else {
+            Ray r;
+            ray_trace<kPacked, false, true, kAsmLoad>(r, P, o, d, stack_column(lds_stack, P.depth), blockDim.x,
+                                                     !P.cam_cull);
+            colour = pixel_colour(ray_result<kPacked, kAsmLoad>(r, P), K.palette, K.n_voxels);
+        }
+    }
+    // every lane is back: R | B and G | A as 16-bit sums over the block
+    const uint32_t rb = block_sum<kLog2S>(colour & 0x00FF00FFu), ga = block_sum<kLog2S>((colour >> 8) & 0x00FF00FFu);
+    if (word != ~0u && (lane & (kS - 1u)) == 0 && ((lane >> 3) & (kS - 1u)) == 0) {
+        constexpr uint32_t half = (kS * kS / 2u) * 0x00010001u;
+        K.out[word] = (((rb + half) >> (2 * kLog2S)) & 0x00FF00FFu) | ((((ga + half) >> (2 * kLog2S)) & 0x00FF00FFu) << 8);
+    }
+    if (stamps) stamp(stamps, stamp_cap, t0, 64);
+}
+
 // Config 5: primary rays, then wavefront compaction -- the block's hit
 // lanes (ballot + popcount per wave, wave offsets through LDS) write their
 // secondary rays into an LDS queue, and the first lanes of the block trace
@@ -1578,6 +1668,52 @@ hipError_t launch_render(const DevPool &p, const DevFrame &f, const Schedule &sc
     const CameraSource src = camera_source(p, f, sc);
     return launch<CameraSource, FrameSink, false>(p, src, FrameSink{f.out, f.palette, f.n_voxels}, src.count(), sc,
                                                   stream, sc.tile_order == 1 ? 64u * 64u : 0u);
+}
+
+namespace {
+
+template <int kPacked, int kLog2S>
+hipError_t launch_ssaa_as(const DevPool &p, const CameraSource &s, const FrameSink &k, const Schedule &sc,
+                          hipStream_t stream)
+{
+    const uint32_t block = (uint32_t)sc.block, n = s.count();
+    const uint32_t grid = (n + block - 1) / block;
+    const uint32_t xcd_group = sc.tile_order == 1 && 64u * 64u >= block ? 64u * 64u / block : 0u;
+    // a plan is a permutation of exactly this grid's workgroups (launch_as); a
+    // split plan never reaches this kernel (split_tile maps lanes to rays differently)
+    const uint32_t *order = sc.order_n == grid && !sc.split_tasks ? sc.order : nullptr;
+    OCH_LAUNCH_TIMED(sc, (k_trace_ssaa<kPacked, kLog2S>), dim3(grid), dim3(block), stack_bytes(p.depth, (int)block),
+                     stream, p, s, k, xcd_group, order, sc.stamps, sc.stamp_cap);
+    return hipGetLastError();
+}
+
+template <int kPacked>
+hipError_t launch_ssaa_layout(const DevPool &p, const CameraSource &s, const FrameSink &k, const Schedule &sc, int log2_s,
+                              hipStream_t stream)
+{
+    switch (log2_s) {
+    case 1: return launch_ssaa_as<kPacked, 1>(p, s, k, sc, stream);
+    case 2: return launch_ssaa_as<kPacked, 2>(p, s, k, sc, stream);
+    case 3: return launch_ssaa_as<kPacked, 3>(p, s, k, sc, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_render_ssaa(const DevPool &p, const DevFrame &f, const Schedule &sc, int log2_s, hipStream_t stream)
+{
+    if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
+    // the sample grid as one shard's whole frame: the kernel takes slice rows for rows
+    if (f.n_shards != 1 || f.shard != 0 || f.row_chunk != f.cams[0].height || f.slice_rows != f.cams[0].height)
+        return hipErrorInvalidValue;
+    const int s = 1 << log2_s;
+    if (f.cams[0].width % s || f.cams[0].height % s) return hipErrorInvalidValue;
+    const CameraSource src = camera_source(p, f, sc);
+    if (src.count() == 0) return hipSuccess;
+    const FrameSink k{f.out, f.palette, f.n_voxels};
+    return p.packed ? launch_ssaa_layout<1>(p, src, k, sc, log2_s, stream)
+                    : launch_ssaa_layout<0>(p, src, k, sc, log2_s, stream);
 }
 
 hipError_t launch_render_push(const DevPool &p, const DevFrame &f, const Schedule &sc, uint16_t *push, hipStream_t stream)

@@ -53,6 +53,24 @@ def unshard_host(gathered: np.ndarray, height: int, row_chunk: int, deal=None) -
     return frame
 
 
+def box_downsample(rgba: np.ndarray, s: int) -> np.ndarray:
+    """The supersampled frame's definition (och_gpu_render_ssaa_views_dev) on the
+    host: (..., Hs, Ws) RGBA8 words -> (..., Hs / s, Ws / s), every byte the mean
+    of its s x s block's bytes, rounded half up: (sum + s * s / 2) // (s * s)."""
+    if s not in (2, 4, 8):
+        raise ValueError("samples per axis must be 2, 4 or 8")
+    rgba = np.ascontiguousarray(rgba, np.uint32)
+    if rgba.ndim < 2 or rgba.shape[-2] % s or rgba.shape[-1] % s:
+        raise ValueError(f"frame of shape {rgba.shape} is not a multiple of {s}")
+    lead, (hs, ws) = rgba.shape[:-2], rgba.shape[-2:]
+    blocks = rgba.reshape(*lead, hs // s, s, ws // s, s)
+    out = np.zeros((*lead, hs // s, ws // s), np.uint32)
+    for shift in (0, 8, 16, 24):
+        total = ((blocks >> np.uint32(shift)) & np.uint32(0xFF)).sum(axis=(-3, -1), dtype=np.uint32)
+        out |= ((total + np.uint32(s * s // 2)) // np.uint32(s * s)) << np.uint32(shift)
+    return out
+
+
 class RcclComm:
     """The library's own RCCL communicator (och_comm_*): one rank per process
     and GPU, as the driver's torch.distributed launch runs them.  Rank 0 makes

@@ -321,6 +321,30 @@ class GpuPool:
         call("och_gpu_render_views_dev", self._h, C.cast(arr, C.c_void_p), len(cams), _dev_ptr(rgba_slices),
              int(row_chunk), int(shard), int(n_shards))
 
+    def render_ssaa(self, cam: Camera, s: int) -> np.ndarray:
+        """The frame of `cam` (the sample grid's camera: width and height multiples of s = 2, 4 or 8)
+        supersampled s x s: (H / s, W / s) uint32, each byte the rounded mean of its block's samples
+        (och_gpu_render_ssaa; frame.box_downsample states the definition on the host)."""
+        s = int(s)
+        out = np.empty((cam.height // s, cam.width // s) if s > 0 else (0, 0), np.uint32)
+        call("och_gpu_render_ssaa", self._h, C.byref(cam), s, _np_ptr(out), out.size)
+        return out
+
+    def render_ssaa_views_dev(self, cams, s: int, rgba, capacity_pixels: int | None = None):
+        """Several equal-size sample-grid cameras supersampled s x s in one launch (och_gpu_render_ssaa_views_dev):
+        rgba (a device tensor of 4-byte words, or a raw pointer with capacity_pixels) receives the views'
+        (H / s) x (W / s) frames back to back.  Asynchronous on the pool's stream."""
+        arr = (Camera * len(cams))(*cams)
+        s = int(s)
+        if s in (2, 4, 8) and cams:              # any other s the library refuses before it touches rgba
+            _need(rgba, 4 * len(cams) * (cams[0].width // s) * (cams[0].height // s), "rgba")
+        if capacity_pixels is None:
+            if not (hasattr(rgba, "numel") and hasattr(rgba, "element_size")):
+                raise ValueError("a raw pointer needs capacity_pixels")
+            capacity_pixels = rgba.numel() * rgba.element_size() // 4
+        call("och_gpu_render_ssaa_views_dev", self._h, C.cast(arr, C.c_void_p), len(cams), s, _dev_ptr(rgba),
+             int(capacity_pixels))
+
     def render_steps_dev(self, cams, frames, streams, n_steps: int, events=None, row_chunk: int | None = None,
                          bounce: bool = False):
         """n_steps whole frames of these cameras issued by the library's own loop

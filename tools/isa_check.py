@@ -23,11 +23,11 @@ with the product's flags and checks, in every function that issues the load
      this hazard).  The compiler keeps that distance in
      its own code (its minimum over these kernels is 2); the check holds the
      hand-placed VALU of the descent's child index (ray_push_descend) to it.
-  4. every traversal kernel (k_trace_grid, k_trace_bounce) admits 8 waves per
-     SIMD by its SGPR and VGPR counts (above 80 SGPRs a SIMD takes 7, although
+  4. every traversal kernel (k_trace_grid, k_trace_ssaa, k_trace_bounce) admits
+     8 waves per SIMD by its SGPR and VGPR counts (above 80 SGPRs a SIMD takes 7, although
      the compiler's occupancy note still says 8).
-  5. no grid kernel spills SGPRs to VGPR lanes (the config-5 kernels' spills are
-     counted in the summary).
+  5. no grid or supersampling kernel spills SGPRs to VGPR lanes (the config-5
+     kernels' spills are counted in the summary).
 Exit status 0 and a one-line summary when every kernel passes; 1 with the
 offending instruction otherwise.  Run by the csrc Makefile (`make isa-check`),
 __graft_entry__.build() and tests/test_isa_check.py.
@@ -226,6 +226,8 @@ def check_mask_hazards(name: str, lines: list[str]) -> list[str]:
     return problems
 
 
+TRAVERSAL = ("k_trace_grid", "k_trace_ssaa", "k_trace_bounce")   # every kernel that walks the DAG
+NO_SPILL = ("k_trace_grid", "k_trace_ssaa")                       # check 5
 RENDER_KERNEL = "k_trace_gridINS0_12CameraSourceENS0_9FrameSinkELi1ELb0"   # the bench's render launch
 
 
@@ -292,7 +294,7 @@ def main(argv=None) -> int:
             loads += n
         problems += p
         problems += check_mask_hazards(name, lines)
-    want = ("k_trace_grid", "k_trace_bounce")
+    want = TRAVERSAL
     missing = [w for w in want if not any(w in c for c in checked)]
     asm_on = "och_cur_load" in asm
     summary = {"functions": len(fns), "checked": len(checked), "asm_loads": loads, "problems": len(problems),
@@ -310,7 +312,7 @@ def main(argv=None) -> int:
     # 4. the traversal kernels keep 8 waves per SIMD (82 SGPRs admitted 7 and cost
     #    5 % sustained); the compiler's own occupancy note says 8 there
     res = kernel_resources(asm)
-    occ = {n: waves_per_simd(*r) for n, r in res.items() if "k_trace_grid" in n or "k_trace_bounce" in n}
+    occ = {n: waves_per_simd(*r) for n, r in res.items() if any(k in n for k in TRAVERSAL)}
     if render and render[0] in res:
         summary["render_sgpr"], summary["render_vgpr"] = res[render[0]]
     summary["traversal_waves_per_simd"] = min(occ.values()) if occ else None
@@ -322,11 +324,16 @@ def main(argv=None) -> int:
     #    wave cost the split kernel 2 %.  The config-5 kernels
     #    spill in their per-ray setup (counted, not refused).
     spills = {n: sum(1 for l in lines if re.match(r"\s*v_(writelane|readlane)_b32", l))
-              for n, lines in fns.items() if "k_trace_grid" in n or "k_trace_bounce" in n}
+              for n, lines in fns.items() if any(k in n for k in TRAVERSAL)}
     summary["grid_spill_lanes"] = sum(v for n, v in spills.items() if "k_trace_grid" in n)
+    summary["ssaa_spill_lanes"] = sum(v for n, v in spills.items() if "k_trace_ssaa" in n)
+    # the supersampling kernels' registers (packed layout, s = 2, 4, 8), beside the render's
+    ssaa = sorted(n for n in res if "k_trace_ssaaILi1E" in n)
+    if ssaa:
+        summary["ssaa_sgpr"], summary["ssaa_vgpr"] = [res[n][0] for n in ssaa], [res[n][1] for n in ssaa]
     summary["bounce_spill_lanes"] = sum(v for n, v in spills.items() if "k_trace_bounce" in n)
     for n, v in spills.items():
-        if v and "k_trace_grid" in n:
+        if v and any(k in n for k in NO_SPILL):
             problems.append(f"{n}: {v} SGPR spill lanes (v_writelane / v_readlane)")
     if problems:
         print("isa_check: FAILED " + json.dumps(summary))
