@@ -4,10 +4,12 @@
 // Also traces the reference's per-frame pick ray (ORT/test_och_h_octree.cpp:527-536)
 // through the reference signature, tree.sse_trace(o, d, dir&, voxel&, t&).
 //
-//   make -C examples && ./examples/render_frame 10 out.ppm [width height yaw pitch] [--ssaa S]
+//   make -C examples && ./examples/render_frame 10 out.ppm [width height yaw pitch] [--ssaa S | --lit]
 //
 // --ssaa S (2, 4 or 8, anywhere on the line): the same width x height frame
 // from S x S samples per pixel, resolved in the render kernel (tree.render_ssaa).
+// --lit (anywhere on the line): the frame with sun shadows and ambient
+// occlusion, secondary rays traced in the render's launch (tree.render_lit).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +22,14 @@
 int main(int argc, char **argv)
 {
     int ssaa = 0;
+    bool lit = false;
+    for (int i = 1; i < argc; ++i)
+        if (std::strcmp(argv[i], "--lit") == 0) {       // taken out of the positional arguments
+            lit = true;
+            for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+            argc -= 1;
+            break;
+        }
     for (int i = 1; i + 1 < argc; ++i)
         if (std::strcmp(argv[i], "--ssaa") == 0) {      // taken out of the positional arguments
             ssaa = std::atoi(argv[i + 1]);
@@ -48,6 +58,12 @@ int main(int argc, char **argv)
             samples.height *= ssaa;
             tree.render_ssaa(samples.update_position(), ssaa, rgba);
             std::printf("%d x %d samples per pixel\n", ssaa, ssaa);
+        } else if (lit) {
+            // the sun over the camera's left shoulder; AO rays reach eight voxels along each axis
+            const och_light light = {{0.8F, 0.35F, 0.25F}, std::ldexp(8.0F, -depth), 96, 24, OCH_LIGHT_SUN | OCH_LIGHT_AO};
+            tree.render_lit(cam.update_position(), light, rgba);
+            std::printf("lit: sun (%g, %g, %g), ao reach %g\n", light.sun_dir[0], light.sun_dir[1], light.sun_dir[2],
+                        light.ao_reach);
         } else {
             tree.render(cam.update_position(), rgba.data());
         }

@@ -172,7 +172,9 @@ typedef enum och_option {
     OCH_OPT_BOUNCE_COMPACT = 6,/* config 5: 1 (default) = compact each block's secondary rays into its first lanes
                                   (wave ballot/popcount + LDS queue) before tracing them; 0 = trace each in place;
                                   2 = per block, compact when that packs the block's secondary rays into fewer
-                                  waves than hold them, else in place */
+                                  waves than hold them, else in place.  Lit frames (och_gpu_render_lit_views_dev):
+                                  0 = every hit lane walks its own pixel's secondary rays, 1 or 2 = the block's
+                                  hit pixels are compacted and their rays dealt over its lanes; same bytes */
     OCH_OPT_CULL = 8,          /* 1 (default) = a ray whose walk provably never enters the bounding box of the
                                   pool's voxels (och_pool_occupied_box) is recorded as the miss it would end in,
                                   without walking (camera rays: a cheaper conservative test first, before the
@@ -335,6 +337,70 @@ OCH_API int och_gpu_render_ssaa_views_dev(och_gpu_pool *pool, const och_camera *
                                           uint32_t *rgba, size_t capacity_pixels);
 OCH_API int och_gpu_render_ssaa(och_gpu_pool *pool, const och_camera *cam, int s, uint32_t *rgba,
                                 size_t capacity_pixels);
+/* Lit frames: och_gpu_render_views_dev's frame with every face hit shaded by
+ * sun shadow and ambient occlusion, primary and secondary rays in one launch.
+ * Build-defined, like config 5: the reference renders primary rays only.
+ *
+ * A pixel is lit only when its primary record is a face hit (direction <
+ * OCH_EXIT, an id without a palette entry included); sky and INSIDE pixels
+ * are the plain render's.  All secondary rays start at config 5's secondary
+ * origin p: per axis q = o + d * t (product rounded, then the sum), and on the
+ * hit axis a = direction % 3, p = q -+ voxel_dim / 2 (- for direction < 3).
+ *   Sun ray (OCH_LIGHT_SUN): from p along sun_dir, the direction towards the
+ *     sun, as given (not normalised).  The face is turned towards the sun iff
+ *     sun_dir[a] < 0 for direction < 3, sun_dir[a] > 0 otherwise (the record's
+ *     direction is the ray's travel sign; the normal opposes it).  A face
+ *     turned away is self-shadowed: no ray, shadowed.  Otherwise the pixel is
+ *     shadowed iff the sun ray's record is not OCH_EXIT (INSIDE blocks).
+ *   AO rays (OCH_LIGHT_AO), k = 0..3: with b = (a + 1) % 3, c = (a + 2) % 3,
+ *     d[a] = -1 for direction < 3 else +1, d[b] = k & 1 ? -1 : +1,
+ *     d[c] = k & 2 ? -1 : +1 (length sqrt 3 each, so one bound on t is one
+ *     distance).  Ray k is occluded iff its record is not OCH_EXIT and is
+ *     OCH_INSIDE or has t < ao_reach (float compare).
+ * Mask byte of a pixel: bits 0..3 AO ray k occluded, bit 4 shadowed, bit 5
+ * self-shadowed (bit 4 set too); 0x80 for a pixel that is not a face hit; the
+ * bits of a ray kind that was not requested are 0.  Shade: with
+ * w = 256 - sun_shade * [bit 4] - ao_shade * popcount(bits 0..3), each of R, G,
+ * B becomes (c * w + 128) >> 8 and alpha is kept; w = 256 is the identity, so
+ * flags = 0 gives och_gpu_render_views_dev's frame word for word.
+ *
+ * och_light_check (host only): OCH_E_INVALID for unknown flags, OCH_LIGHT_SUN
+ * with a non-finite or all-zero sun_dir, OCH_LIGHT_AO with ao_reach not finite
+ * or not > 0, sun_shade outside 0..256, ao_shade outside 0..64, or
+ * sun_shade + 4 * ao_shade > 256.
+ *
+ * och_gpu_render_lit_views_dev writes RGBA8 slices, _lit_masks_views_dev the
+ * mask bytes (1 B per pixel), both laid out as och_gpu_render_views_dev lays
+ * out its slices (view v at v * och_gpu_slice_rows(...) * W pixels; the pool's
+ * row deal honoured), so they compose with och_gpu_unshard_views_dev.
+ * capacity_pixels is what the buffer holds, in pixels: a smaller buffer, a
+ * light och_light_check refuses, views of unequal size and a pool left torn by
+ * a failed flush are refused (OCH_E_INVALID) before anything is written.
+ * Launch options change the dispatch only (OCH_OPT_TILE_ORDER 2 uses
+ * och_gpu_plan_views' plan of exactly this grid, never its split form;
+ * OCH_OPT_BOUNCE_COMPACT picks how the secondary rays are dealt over lanes).
+ * _views_dev: device buffers, asynchronous on the pool's stream;
+ * och_gpu_render_lit: one camera, whole frame, host buffer, synchronous.
+ * Out of scope: colour-code slices and the RCCL exchange paths, frame groups,
+ * lit and supersampled frames together, lit and bounce together, more than
+ * four AO rays. */
+enum { OCH_LIGHT_SUN = 1, OCH_LIGHT_AO = 2 };
+typedef struct och_light {
+    float sun_dir[3];    /* towards the sun; traced as given */
+    float ao_reach;      /* an AO ray is occluded by a hit with t < ao_reach */
+    int32_t sun_shade;   /* 0..256 */
+    int32_t ao_shade;    /* 0..64, per occluded AO ray */
+    int32_t flags;       /* OCH_LIGHT_SUN | OCH_LIGHT_AO */
+} och_light;
+OCH_API int och_light_check(const och_light *light);
+OCH_API int och_gpu_render_lit_views_dev(och_gpu_pool *pool, const och_camera *cams, int n_views, const och_light *light,
+                                         uint32_t *rgba_slices, size_t capacity_pixels, int row_chunk, int shard,
+                                         int n_shards);
+OCH_API int och_gpu_render_lit_masks_views_dev(och_gpu_pool *pool, const och_camera *cams, int n_views,
+                                               const och_light *light, uint8_t *mask_slices, size_t capacity_pixels,
+                                               int row_chunk, int shard, int n_shards);
+OCH_API int och_gpu_render_lit(och_gpu_pool *pool, const och_camera *cam, const och_light *light, uint32_t *rgba,
+                               size_t capacity_pixels);
 /* The frame loop (update_image once per frame, ORT/test_och_h_octree.cpp:
  * 437-457) issued natively: n_steps whole frames of the same cameras
  * (och_gpu_render_views_dev, or _bounce_views_dev with bounce = 1; one shard),

@@ -118,6 +118,19 @@ public:
         check(och_gpu_render_ssaa(pool_, &cam, s, rgba, capacity_pixels), "och_gpu_render_ssaa");
     }
 
+    // The same frame with every face hit shaded by sun shadow and ambient
+    // occlusion, primary and secondary rays in one launch (och_gpu_render_lit;
+    // och_gpu.h has the definition of every bit).
+    void render_lit(const och_camera &cam, const och_light &light, std::vector<uint32_t> &rgba) const
+    {
+        rgba.resize(static_cast<size_t>(cam.width > 0 ? cam.width : 0) * static_cast<size_t>(cam.height > 0 ? cam.height : 0));
+        check(och_gpu_render_lit(pool_, &cam, &light, rgba.data(), rgba.size()), "och_gpu_render_lit");
+    }
+    void render_lit(const och_camera &cam, const och_light &light, uint32_t *rgba, size_t capacity_pixels) const
+    {
+        check(och_gpu_render_lit(pool_, &cam, &light, rgba, capacity_pixels), "och_gpu_render_lit");
+    }
+
     och_gpu_pool *handle() const { return pool_; }
 
 private:

@@ -32,6 +32,23 @@ class Camera(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class Light(C.Structure):
+    """och_light: the sun and ambient-occlusion terms of a lit frame (och_gpu_render_lit_views_dev)."""
+    _fields_ = [("sun_dir", C.c_float * 3), ("ao_reach", C.c_float), ("sun_shade", C.c_int32),
+                ("ao_shade", C.c_int32), ("flags", C.c_int32)]
+
+    def __init__(self, sun_dir=None, ao_reach=None, sun_shade: int = 96, ao_shade: int = 24, flags=None):
+        """The sun term when sun_dir is given (the direction towards the sun, traced as given), the
+        ambient-occlusion term when ao_reach is given, or exactly the terms `flags` names.  Nothing
+        is checked here: och_light_check and the lit renders refuse a bad light."""
+        super().__init__()
+        self.sun_dir[:] = [float(x) for x in (sun_dir if sun_dir is not None else (0.0, 0.0, 0.0))]
+        self.ao_reach = float(ao_reach) if ao_reach is not None else 0.0
+        self.sun_shade, self.ao_shade = int(sun_shade), int(ao_shade)
+        self.flags = int(flags) if flags is not None else ((LIGHT_SUN if sun_dir is not None else 0) |
+                                                            (LIGHT_AO if ao_reach is not None else 0))
+
+
 class PoolInfo(C.Structure):
     _fields_ = [("device_bytes", C.c_uint64), ("n_nodes", C.c_uint32), ("root", C.c_uint32),
                 ("depth", C.c_int32), ("index_base", C.c_int32), ("miss_t", C.c_float),
@@ -98,6 +115,12 @@ PROTOTYPES = {
     "och_gpu_render_bounce_views_dev": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
     "och_gpu_render_ssaa_views_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_size_t]),
     "och_gpu_render_ssaa": (C.c_int, [_P, C.POINTER(Camera), C.c_int, _P, C.c_size_t]),
+    "och_light_check": (C.c_int, [C.POINTER(Light)]),
+    "och_gpu_render_lit_views_dev": (C.c_int, [_P, _P, C.c_int, C.POINTER(Light), _P, C.c_size_t, C.c_int, C.c_int,
+                                               C.c_int]),
+    "och_gpu_render_lit_masks_views_dev": (C.c_int, [_P, _P, C.c_int, C.POINTER(Light), _P, C.c_size_t, C.c_int,
+                                                     C.c_int, C.c_int]),
+    "och_gpu_render_lit": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Light), _P, C.c_size_t]),
     "och_gpu_render_steps_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int]),
     "och_gpu_set_row_deal": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "och_gpu_slice_rows": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
@@ -142,6 +165,9 @@ PROTOTYPES = {
     "och_gpu_render_sharded_steps_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P,
                                                    C.c_int, C.c_int, C.c_int]),
 }
+
+# och_light.flags (include/och_gpu.h OCH_LIGHT_*)
+LIGHT_SUN, LIGHT_AO = 1, 2
 
 # och_gpu_render_sharded_steps_dev's exchange (include/och_gpu.h OCH_EXCHANGE_*)
 EXCHANGE = {"all_gather": 0, "display": 1, "gather": 2}

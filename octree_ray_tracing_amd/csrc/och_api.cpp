@@ -1863,6 +1863,102 @@ OCH_API int och_gpu_render_ssaa_views_dev(och_gpu_pool *p, const och_camera *cam
     return timed_done(p, sc, true);
 }
 
+OCH_API int och_light_check(const och_light *l)
+{
+    if (!l) return fail(OCH_E_INVALID, "light is NULL");
+    if (l->flags & ~(OCH_LIGHT_SUN | OCH_LIGHT_AO)) return fail(OCH_E_INVALID, "unknown light flags 0x%x", l->flags);
+    if (l->flags & OCH_LIGHT_SUN) {
+        const float *s = l->sun_dir;
+        if (!std::isfinite(s[0]) || !std::isfinite(s[1]) || !std::isfinite(s[2]))
+            return fail(OCH_E_INVALID, "sun_dir is not finite");
+        if (s[0] == 0.0F && s[1] == 0.0F && s[2] == 0.0F) return fail(OCH_E_INVALID, "sun_dir is zero");
+    }
+    if ((l->flags & OCH_LIGHT_AO) && !(std::isfinite(l->ao_reach) && l->ao_reach > 0.0F))
+        return fail(OCH_E_INVALID, "ao_reach %g: must be finite and > 0", (double)l->ao_reach);
+    if (l->sun_shade < 0 || l->sun_shade > 256) return fail(OCH_E_INVALID, "sun_shade %d outside 0..256", l->sun_shade);
+    if (l->ao_shade < 0 || l->ao_shade > 64) return fail(OCH_E_INVALID, "ao_shade %d outside 0..64", l->ao_shade);
+    if (l->sun_shade + 4 * l->ao_shade > 256)
+        return fail(OCH_E_INVALID, "sun_shade %d + 4 * ao_shade %d exceeds 256", l->sun_shade, l->ao_shade);
+    return OCH_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// och_gpu_render_lit_views_dev / _lit_masks_views_dev: exactly one of rgba and masks.
+int render_lit_views(och_gpu_pool *p, const och_camera *cams, int n_views, const och_light *light, uint32_t *rgba,
+                     uint8_t *masks, size_t capacity_pixels, int row_chunk, int shard, int n_shards)
+{
+    // every refusal comes before anything is written or launched
+    if (!p || !cams || !light || (!rgba && !masks)) return fail(OCH_E_INVALID, "NULL argument");
+    if (int ls = och_light_check(light)) return ls;
+    if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
+    if (row_chunk <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards)
+        return fail(OCH_E_INVALID, "bad sharding (%d, %d, %d)", row_chunk, shard, n_shards);
+    if (int vs = och::check_views(cams, n_views)) return vs;
+    const int W = cams[0].width, H = cams[0].height;
+    if ((uint64_t)W * H * n_views >= (1ull << 32)) return fail(OCH_E_INVALID, "frame too large");
+    const size_t pixels = (size_t)n_views * p->slice_rows(H, row_chunk, n_shards) * W;
+    if (capacity_pixels < pixels)
+        return fail(OCH_E_INVALID, "the buffer holds %zu pixels, %d slices of %d x %d need %zu", capacity_pixels, n_views,
+                    W, p->slice_rows(H, row_chunk, n_shards), pixels);
+    if (int rs = check_ready(p)) return rs;
+    DeviceGuard g(p->device);
+    const och::DevFrame f = make_frame(p, cams, n_views, rgba, nullptr, row_chunk, shard, n_shards);
+    int ts;
+    och::Schedule sc = timed_schedule(p, ts);
+    if (ts) return ts;
+    use_plan(p, f, false, false, sc);            // the primary render's plan of this grid, never its split form
+    OCH_HIP(och::launch_render_lit(p->dev(), f, sc, *light, masks, p->stream()));
+    return timed_done(p, sc, true);
+}
+
+}  // namespace
+
+extern "C" {
+
+OCH_API int och_gpu_render_lit_views_dev(och_gpu_pool *p, const och_camera *cams, int n_views, const och_light *light,
+                                         uint32_t *rgba_slices, size_t capacity_pixels, int row_chunk, int shard,
+                                         int n_shards)
+{
+    OCH_ENTRY();
+    if (!rgba_slices) return fail(OCH_E_INVALID, "NULL argument");
+    return render_lit_views(p, cams, n_views, light, rgba_slices, nullptr, capacity_pixels, row_chunk, shard, n_shards);
+}
+
+OCH_API int och_gpu_render_lit_masks_views_dev(och_gpu_pool *p, const och_camera *cams, int n_views,
+                                               const och_light *light, uint8_t *mask_slices, size_t capacity_pixels,
+                                               int row_chunk, int shard, int n_shards)
+{
+    OCH_ENTRY();
+    if (!mask_slices) return fail(OCH_E_INVALID, "NULL argument");
+    return render_lit_views(p, cams, n_views, light, nullptr, mask_slices, capacity_pixels, row_chunk, shard, n_shards);
+}
+
+OCH_API int och_gpu_render_lit(och_gpu_pool *p, const och_camera *cam, const och_light *light, uint32_t *rgba,
+                               size_t capacity_pixels)
+{
+    OCH_ENTRY();
+    if (!p || !cam || !light || !rgba) return fail(OCH_E_INVALID, "NULL argument");
+    if (int ls = och_light_check(light)) return ls;
+    if (int vs = och::check_views(cam, 1)) return vs;
+    if (int rs = check_ready(p)) return rs;
+    // refused before the staging buffer is sized; the device form checks again
+    const size_t pixels = (size_t)cam->width * (size_t)cam->height;
+    if (capacity_pixels < pixels)
+        return fail(OCH_E_INVALID, "rgba holds %zu pixels, %d x %d need %zu", capacity_pixels, cam->width, cam->height,
+                    pixels);
+    DeviceGuard g(p->device);
+    int st = ensure_scratch(p, pixels * 4 + 4);
+    if (st != OCH_OK) return st;
+    st = och_gpu_render_lit_views_dev(p, cam, 1, light, reinterpret_cast<uint32_t *>(p->scratch.d), pixels, cam->height, 0, 1);
+    if (st != OCH_OK) return st;
+    OCH_HIP(hipMemcpyAsync(rgba, p->scratch.d, pixels * 4, hipMemcpyDeviceToHost, p->stream()));
+    OCH_HIP(hipStreamSynchronize(p->stream()));
+    return OCH_OK;
+}
+
 OCH_API int och_gpu_render_steps_dev(och_gpu_pool *p, const och_camera *cams, int n_views, int n_steps,
                                      void *const *streams, uint32_t *const *frames, int n_buffers,
                                      void *const *start_events, void *const *stop_events, int row_chunk, int bounce)

@@ -195,6 +195,14 @@ hipError_t launch_render(const DevPool &p, const DevFrame &f, const Schedule &sc
 // words, each the rounded mean of its s x s samples.  Uses sc.order only when
 // it is an unsplit permutation of the 1-sample render's grid.
 hipError_t launch_render_ssaa(const DevPool &p, const DevFrame &f, const Schedule &sc, int log2_s, hipStream_t stream);
+// Lit frames (k_trace_lit): f's slices as launch_render writes them, every
+// face hit shaded by its sun and ambient-occlusion rays (light: checked by
+// och_light_check), into f.out -- or, with masks, the pixels' mask bytes into
+// masks, laid out as f.out's words.  sc.bounce_compact 0 walks the secondary
+// rays in place, else through the block's pixel queue.  Uses sc.order only
+// when it is an unsplit permutation of this grid.
+hipError_t launch_render_lit(const DevPool &p, const DevFrame &f, const Schedule &sc, const och_light &light,
+                             uint8_t *masks, hipStream_t stream);
 // The split planner's counting render: each pixel's walked PUSH count (16 bits)
 // into push, indexed as the frame's slices.
 hipError_t launch_render_push(const DevPool &p, const DevFrame &f, const Schedule &sc, uint16_t *push, hipStream_t stream);

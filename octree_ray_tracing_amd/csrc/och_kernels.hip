@@ -16,7 +16,9 @@
 // wave) and the sinks (hit records, the shaded RGBA8 framebuffer of
 // update_image, or 1-byte colour codes for the multi-GPU exchange) make up
 // trace_batch and render.  Config 5 (secondary rays) compacts each block's
-// bounced rays through an LDS queue (ballot + popcount).
+// bounced rays through an LDS queue (ballot + popcount).  Lit frames
+// (k_trace_lit) queue each block's hit pixels beside the stacks and deal their
+// sun and ambient-occlusion rays over the block's lanes, ray kind major.
 //
 // Arms measured and retired (persistent and refill schedules, in-block wave
 // merging, the per-node voxel-box skip, the column cull, LDS-resident top
@@ -1403,6 +1405,192 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_bounce(DevPool P, S
     if (stamps) stamp(stamps, stamp_cap, t0, total);
 }
 
+// Lit frames (och_gpu_render_lit_views_dev): a face hit's
+// secondary rays -- one towards the sun, four ambient-occlusion rays -- all
+// from config 5's secondary origin (bounce_ray: half a voxel in front of the
+// hit face), each reduced to one bit of the pixel's mask byte:
+//   bits 0..3  AO ray k occluded: its record is not the MISS and is INSIDE or
+//              has t < ao_reach (the rays are (+-1, +-1, +-1), so one bound on
+//              t is one distance);
+//   bit 4      shadowed: the sun ray's record is not the MISS, or
+//   bit 5      (with bit 4) the face is turned away from the sun: no ray;
+//   0x80       not a face hit (sky, INSIDE): the plain render's pixel.
+// Ray kinds: 0 the sun ray, 1 + k AO ray k.
+
+// Direction of secondary ray `kind` of a hit on face `dir`.  The record's
+// direction is the ray's travel sign on the hit axis a, so the face normal is
+// -1 on a for dir < 3 and +1 otherwise; AO ray k leaves along the normal and
+// the two diagonals of the other axes b = a + 1, c = a + 2 (mod 3).
+__device__ __forceinline__ void lit_ray_dir(const och_light &L, uint32_t kind, uint32_t dir, float *d)
+{
+    const uint32_t a = dir >= 3u ? dir - 3u : dir, k = kind - 1u;
+#pragma unroll
+    for (uint32_t x = 0; x < 3; ++x) {
+        const uint32_t rel = x >= a ? x - a : x + 3u - a;                   // 0: a, 1: b, 2: c
+        const bool neg = rel == 0 ? dir < 3u : ((k >> (rel - 1u)) & 1u) != 0;
+        d[x] = kind == 0 ? L.sun_dir[x] : (neg ? -1.0F : 1.0F);
+    }
+}
+
+// The face `dir` is turned towards the sun (a sun ray is worth tracing).
+__device__ __forceinline__ bool lit_faces_sun(const och_light &L, uint32_t dir)
+{
+    const uint32_t a = dir >= 3u ? dir - 3u : dir;
+    const float s = a == 0 ? L.sun_dir[0] : a == 1 ? L.sun_dir[1] : L.sun_dir[2];
+    return dir < 3u ? s < 0.0F : s > 0.0F;
+}
+
+// The mask bit of secondary ray `kind` with record h2 (0 when the ray is free).
+__device__ __forceinline__ uint32_t lit_ray_bit(const och_light &L, uint32_t kind, const Hit &h2)
+{
+    if (h2.dir == OCH_EXIT) return 0u;          // the direction decides: an octree pool's miss has t = 0
+    if (kind == 0) return 0x10u;
+    return (h2.dir == OCH_INSIDE || ffrom(h2.t) < L.ao_reach) ? 1u << (kind - 1u) : 0u;
+}
+
+// The shade of a lit pixel: every colour channel scaled by w / 256, rounded
+// half up, w = 256 - sun_shade [shadowed] - ao_shade * (occluded AO rays);
+// alpha kept.  och_light_check bounds w to 0..256, so no channel carries into
+// its neighbour (255 * 256 + 128 < 2^16) and w = 256 is the identity.
+__device__ __forceinline__ uint32_t lit_shade(uint32_t c, uint32_t mask, const och_light &L)
+{
+    const uint32_t w = 256u - (uint32_t)L.sun_shade * ((mask >> 4) & 1u) - (uint32_t)L.ao_shade * (uint32_t)__popc(mask & 15u);
+    const uint32_t rb = (((c & 0x00FF00FFu) * w + 0x00800080u) >> 8) & 0x00FF00FFu;
+    const uint32_t g = ((((c >> 8) & 0xFFu) * w + 0x80u) >> 8) & 0xFFu;
+    return (c & 0xFF000000u) | rb | (g << 8);
+}
+
+// Lit sinks.  payload: what a hit pixel carries to its last pass; put_plain: a
+// pixel that is not a face hit; put_lit: a face hit with its finished mask.
+struct LitFrameSink {
+    FrameSink f;
+    __device__ __forceinline__ uint32_t payload(const Hit &h) const { return pixel_colour(h, f.palette, f.n_voxels); }
+    __device__ __forceinline__ void put_plain(uint32_t i, uint32_t c) const { f.out[i] = c; }
+    __device__ __forceinline__ void put_lit(uint32_t i, uint32_t c, uint32_t mask, const och_light &L) const
+    {
+        f.out[i] = lit_shade(c, mask, L);
+    }
+};
+
+struct LitMaskSink {
+    uint8_t *out;
+    __device__ __forceinline__ uint32_t payload(const Hit &) const { return 0u; }
+    __device__ __forceinline__ void put_plain(uint32_t i, uint32_t) const { out[i] = 0x80u; }
+    __device__ __forceinline__ void put_lit(uint32_t i, uint32_t, uint32_t mask, const och_light &) const
+    {
+        out[i] = (uint8_t)mask;
+    }
+};
+
+// Words per thread of k_trace_lit's pixel queue: the secondary origin (3), the
+// output index, the payload, and the state word (hit direction | mask << 8).
+constexpr uint32_t kLitQueueWords = 6;
+constexpr uint32_t kLitNoPixel = 0xFFu;        // state of a slot without a hit pixel (in-place form)
+
+// The primary pass is k_trace_bounce's.  Then the block's hit pixels go into an
+// LDS queue (SoA, kLitQueueWords per thread) that lies behind the parent
+// stacks, not in them: it is read again after the secondary walks, which use
+// the stacks.  The block's secondary rays are one flat list, ray kind major
+// (every queued pixel's sun ray, then every pixel's AO ray 0, ...), dealt over
+// the block's lanes in rounds of blockDim.x: a tile with 20 hit pixels walks
+// its 100 rays in two rounds of one wave, and a wave's lanes walk one kind
+// (similar directions).  A ray's bit is ORed into its pixel's state word (an LDS
+// atomic); after a barrier the first lanes write the pixels.
+// compact (OCH_OPT_BOUNCE_COMPACT): nonzero = the hit pixels are compacted
+// (ballot + popcount, wave offsets through LDS) as config 5 compacts its
+// secondary rays; 0 = in place: every lane queues into its own slot and walks
+// its own pixel's rays one after the other -- the same list with the slots of
+// the lanes without a hit left idle.  Both forms write the same bytes.
+template <class Sink, int kPacked>
+__global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_lit(DevPool P, CameraSource S, Sink K, och_light L, int compact,
+                                                                 uint32_t xcd_group, const uint32_t *__restrict__ order,
+                                                                 uint64_t *stamps, uint32_t stamp_cap)
+{
+    extern __shared__ uint32_t lds_stack[];
+    __shared__ uint32_t wave_count[16];
+    const uint64_t t0 = stamps ? realtime() : 0;
+    const uint32_t blk = order ? order[blockIdx.x] : xcd_block(blockIdx.x, gridDim.x, xcd_group);
+    const uint32_t nb = blockDim.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t stack = stack_column(lds_stack, P.depth);
+    // the queue starts where the stacks' word plane ends (launch_lit sizes both)
+    uint32_t *queue = lds_stack + (stack - 4u * threadIdx.x - (uint32_t)(uintptr_t)(const lds_word *)lds_stack) / 4u +
+                      ((uint32_t)P.depth + 1u) * nb;
+    const uint32_t wave_base = blk * nb + (threadIdx.x & ~63u);
+    const uint32_t first = (L.flags & OCH_LIGHT_SUN) ? 0u : 1u;
+    const uint32_t kinds = ((L.flags & OCH_LIGHT_SUN) ? 1u : 0u) + ((L.flags & OCH_LIGHT_AO) ? 4u : 0u);
+    float o[3], d[3], p[3], d2[3];
+    uint32_t out = 0, payload = 0, state = kLitNoPixel;
+    bool want = false;
+    bool miss;
+    if (wave_base + lane < S.count() && S.get_wave_culled(wave_base, lane, P, P.cull != 0, o, d, out, miss)) {
+        if (miss) {                                 // proven before setup: the sky
+            K.put_plain(out, K.payload(Hit{OCH_EXIT, 0u, P.miss_bits, 0u}));
+        } else {
+            Ray r;
+            ray_trace<kPacked, false, true, kAsmLoad>(r, P, o, d, stack, nb, !P.cam_cull);
+            const Hit h1 = ray_result<kPacked, kAsmLoad>(r, P);
+            want = h1.dir < OCH_EXIT;
+            payload = K.payload(h1);
+            if (want) {
+                bounce_ray(o, d, h1, P.half_voxel, p, d2);
+                state = (uint32_t)h1.dir;
+                if ((L.flags & OCH_LIGHT_SUN) && !lit_faces_sun(L, state)) state |= 0x30u << 8;   // self-shadowed
+            } else {
+                K.put_plain(out, payload);
+            }
+        }
+    }
+    uint32_t q = threadIdx.x, total = nb;
+    if (compact) {
+        const uint64_t bal = __ballot(want);
+        if (lane == 0) wave_count[wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t base = 0;
+        total = 0;
+        for (uint32_t w = 0; w < (nb >> 6); ++w) {
+            const uint32_t cnt = wave_count[w];
+            base += w < wave ? cnt : 0u;
+            total += cnt;
+        }
+        q = base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    }
+    if (want) {
+        queue[0 * nb + q] = fbits(p[0]);
+        queue[1 * nb + q] = fbits(p[1]);
+        queue[2 * nb + q] = fbits(p[2]);
+        queue[3 * nb + q] = out;
+        queue[4 * nb + q] = payload;
+    }
+    if (want || !compact) queue[5 * nb + q] = state;
+    __syncthreads();
+    // ray j of the list: kind first + j / total of queued pixel j % total
+    for (uint32_t j = threadIdx.x; j < kinds * total; j += nb) {
+        uint32_t pix = j, kind = first;
+        while (pix >= total) {
+            pix -= total;
+            ++kind;
+        }
+        const uint32_t st = queue[5 * nb + pix];    // the direction and bit 5 are final; other lanes OR bits 0..4
+        if ((st & 0xFFu) == kLitNoPixel || (kind == 0 && (st & (0x20u << 8)) != 0)) continue;   // self-shadowed: no ray
+        float so[3], sd[3];
+        so[0] = ffrom(queue[0 * nb + pix]);
+        so[1] = ffrom(queue[1 * nb + pix]);
+        so[2] = ffrom(queue[2 * nb + pix]);
+        lit_ray_dir(L, kind, st & 0xFFu, sd);
+        Ray r;
+        ray_trace<kPacked, false, true, kAsmLoad>(r, P, so, sd, stack, nb);
+        const uint32_t bit = lit_ray_bit(L, kind, ray_result<kPacked, kAsmLoad>(r, P));
+        if (bit) atomicOr(&queue[5 * nb + pix], bit << 8);
+    }
+    __syncthreads();
+    if (threadIdx.x < total) {
+        const uint32_t st = queue[5 * nb + threadIdx.x];
+        if ((st & 0xFFu) != kLitNoPixel)
+            K.put_lit(queue[3 * nb + threadIdx.x], queue[4 * nb + threadIdx.x], (st >> 8) & 0xFFu, L);
+    }
+    if (stamps) stamp(stamps, stamp_cap, t0, kinds * total);
+}
+
 __global__ __launch_bounds__(256) void k_raygen(och_camera C, float *__restrict__ dirs)
 {
     const int col = blockIdx.x * 16 + (threadIdx.x & 15);
@@ -1731,6 +1919,43 @@ hipError_t launch_render_bounce(const DevPool &p, const DevFrame &f, const Sched
     const CameraSource src = camera_source(p, f, sc);
     return launch_bounce<CameraSource, BounceFrameSink, false>(
         p, src, BounceFrameSink{FrameSink{f.out, f.palette, f.n_voxels}}, src.count(), sc, stream);
+}
+
+namespace {
+
+// LDS of a lit launch: the parent stacks and, behind them, the pixel queue
+// (k_trace_lit), which must outlive the secondary walks.
+template <class Sink>
+hipError_t launch_lit(const DevPool &p, const CameraSource &s, const Sink &k, const och_light &light, const Schedule &sc,
+                      hipStream_t stream)
+{
+    const uint32_t block = (uint32_t)sc.block, n = s.count();
+    if (n == 0) return hipSuccess;
+    const uint32_t grid = (n + block - 1) / block;
+    const size_t lds = stack_bytes(p.depth, (int)block) + (size_t)kLitQueueWords * block * sizeof(uint32_t);
+    const uint32_t xcd_group = sc.tile_order == 1 && 64u * 64u >= block ? 64u * 64u / block : 0u;
+    // a plan is a permutation of exactly this grid's workgroups (launch_as); a
+    // split plan never reaches this kernel (split_tile maps lanes to rays differently)
+    const uint32_t *order = sc.order_n == grid && !sc.split_tasks ? sc.order : nullptr;
+    if (p.packed)
+        OCH_LAUNCH_TIMED(sc, (k_trace_lit<Sink, 1>), dim3(grid), dim3(block), lds, stream, p, s, k, light,
+                         sc.bounce_compact, xcd_group, order, sc.stamps, sc.stamp_cap);
+    else
+        OCH_LAUNCH_TIMED(sc, (k_trace_lit<Sink, 0>), dim3(grid), dim3(block), lds, stream, p, s, k, light,
+                         sc.bounce_compact, xcd_group, order, sc.stamps, sc.stamp_cap);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_render_lit(const DevPool &p, const DevFrame &f, const Schedule &sc, const och_light &light,
+                             uint8_t *masks, hipStream_t stream)
+{
+    if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
+    if ((uint32_t)sc.block > 1024u) return hipErrorInvalidValue;          // wave_count holds 16 waves
+    const CameraSource src = camera_source(p, f, sc);
+    if (masks) return launch_lit(p, src, LitMaskSink{masks}, light, sc, stream);
+    return launch_lit(p, src, LitFrameSink{FrameSink{f.out, f.palette, f.n_voxels}}, light, sc, stream);
 }
 
 hipError_t launch_render_codes(const DevPool &p, const DevFrame &f, const Schedule &sc, bool bounce, hipStream_t stream)

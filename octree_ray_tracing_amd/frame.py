@@ -71,6 +71,27 @@ def box_downsample(rgba: np.ndarray, s: int) -> np.ndarray:
     return out
 
 
+def shade_lit(frame: np.ndarray, masks: np.ndarray, light) -> np.ndarray:
+    """The lit frame's shade (och_gpu_render_lit_views_dev) on the host: RGBA8
+    words of the plain frame and the pixels' mask bytes -> the lit words.  With
+    w = 256 - sun_shade [bit 4] - ao_shade popcount(bits 0..3), each of R, G, B
+    becomes (c * w + 128) >> 8; alpha is kept, and a pixel whose mask is 0x80
+    (not a face hit) is left as it is."""
+    frame = np.ascontiguousarray(frame, np.uint32)
+    masks = np.ascontiguousarray(masks, np.uint8)
+    if frame.shape != masks.shape:
+        raise ValueError(f"frame {frame.shape} and masks {masks.shape} differ in shape")
+    m = masks.astype(np.uint32)
+    count = (m & 1) + ((m >> 1) & 1) + ((m >> 2) & 1) + ((m >> 3) & 1)
+    w = np.uint32(256) - np.uint32(light.sun_shade) * ((m >> 4) & 1) - np.uint32(light.ao_shade) * count
+    w = np.where(m == 0x80, np.uint32(256), w).astype(np.uint32)
+    out = frame & np.uint32(0xFF000000)
+    for shift in (0, 8, 16):
+        c = (frame >> np.uint32(shift)) & np.uint32(0xFF)
+        out = out | (((c * w + np.uint32(128)) >> np.uint32(8)) << np.uint32(shift))
+    return out
+
+
 class RcclComm:
     """The library's own RCCL communicator (och_comm_*): one rank per process
     and GPU, as the driver's torch.distributed launch runs them.  Rank 0 makes

@@ -19,7 +19,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Camera, OchError, call
+from ._lib import Camera, Light, OchError, call
 
 
 class Direction(enum.IntEnum):
@@ -112,6 +112,11 @@ def camera(pos=(1.5, 1.5, 1.5), yaw: float = 0.0, pitch: float = 0.0, fov: float
     call("och_camera_setup", float(pos[0]), float(pos[1]), float(pos[2]), float(yaw), float(pitch),
          float(fov), int(width), int(height), C.byref(cam))
     return cam
+
+
+def light_check(light: Light) -> None:
+    """Raises OchError (OCH_E_INVALID) for a light a lit render would refuse (och_light_check, host only)."""
+    call("och_light_check", C.byref(light))
 
 
 class GpuPool:
@@ -344,6 +349,40 @@ class GpuPool:
             capacity_pixels = rgba.numel() * rgba.element_size() // 4
         call("och_gpu_render_ssaa_views_dev", self._h, C.cast(arr, C.c_void_p), len(cams), s, _dev_ptr(rgba),
              int(capacity_pixels))
+
+    def render_lit(self, cam: Camera, light: Light) -> np.ndarray:
+        """The frame of `cam` with every face hit shaded by sun shadow and ambient occlusion
+        (och_gpu_render_lit; frame.shade_lit states the shade on the host): H x W uint32."""
+        out = np.empty((cam.height, cam.width), np.uint32)
+        call("och_gpu_render_lit", self._h, C.byref(cam), C.byref(light), _np_ptr(out), out.size)
+        return out
+
+    def _lit_views(self, name, cams, light, buf, bytes_per_pixel, capacity_pixels, row_chunk, shard, n_shards):
+        arr = (Camera * len(cams))(*cams)
+        if row_chunk is None:
+            row_chunk = cams[0].height
+        self._need_frames(buf, list(cams), row_chunk, shard, n_shards, bytes_per_pixel, name)
+        if capacity_pixels is None:
+            if not (hasattr(buf, "numel") and hasattr(buf, "element_size")):
+                raise ValueError("a raw pointer needs capacity_pixels")
+            capacity_pixels = buf.numel() * buf.element_size() // bytes_per_pixel
+        call(name, self._h, C.cast(arr, C.c_void_p), len(cams), C.byref(light), _dev_ptr(buf), int(capacity_pixels),
+             int(row_chunk), int(shard), int(n_shards))
+
+    def render_lit_views_dev(self, cams, light: Light, rgba_slices, capacity_pixels: int | None = None,
+                             row_chunk: int | None = None, shard: int = 0, n_shards: int = 1):
+        """render_views_dev's slices, lit (och_gpu_render_lit_views_dev): rgba_slices is a device tensor of
+        4-byte words, or a raw pointer with capacity_pixels.  Asynchronous on the pool's stream."""
+        self._lit_views("och_gpu_render_lit_views_dev", cams, light, rgba_slices, 4, capacity_pixels, row_chunk, shard,
+                        n_shards)
+
+    def render_lit_masks_views_dev(self, cams, light: Light, mask_slices, capacity_pixels: int | None = None,
+                                   row_chunk: int | None = None, shard: int = 0, n_shards: int = 1):
+        """The lit frame's mask bytes, one per pixel, laid out as the RGBA8 slices
+        (och_gpu_render_lit_masks_views_dev): bits 0..3 AO ray k occluded, bit 4 shadowed, bit 5
+        self-shadowed, 0x80 not a face hit."""
+        self._lit_views("och_gpu_render_lit_masks_views_dev", cams, light, mask_slices, 1, capacity_pixels, row_chunk,
+                        shard, n_shards)
 
     def render_steps_dev(self, cams, frames, streams, n_steps: int, events=None, row_chunk: int | None = None,
                          bounce: bool = False):

@@ -20,6 +20,9 @@ corners and edges); then one launch path with random options:
             weighted row deals, primary or config 5; each shard planned, with
             the split, as each rank of the N = 8 bench) + shade_unshard
   bounce_frames  config 5 RGBA8 frames, every compaction mode
+  lit       lit RGBA8 frames and mask bytes (och_gpu_render_lit_views_dev / _lit_masks_views_dev):
+            random suns (zero components now and then), reaches, shades and flags, both
+            compaction forms; only with --paths (the default campaign keeps its paths)
   image     och_gpu_trace_batch_image (host rays, x + y * W, 8x8 tiles)
   editor    h_octree::set edits flushed to the device pool in 1-3 windows
   steps     the N = 1 frame loop issued by the library (och_gpu_render_steps_dev)
@@ -259,6 +262,50 @@ def bounce_frames_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, sce
     return compare_frames(O, ref_pool, got, views, W, H, pal, True)
 
 
+def lit_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, scene, o, d):
+    """Lit frames and their mask bytes against the oracle's primary and secondary
+    records (tests/test_gpu_lit.py's Expected states the definition in numpy)."""
+    from test_gpu_lit import Expected, shade
+    W, H, nv = int(rng.integers(1, 193)), int(rng.integers(1, 121)), int(rng.integers(1, 4))
+    rc = int(rng.choice([1, 4, 8, 16]))
+    views, cams = random_views(rng, ort, depth, W, H, nv)
+    pal = rng.integers(0, 2 ** 32, 6 * int(rng.integers(1, 300)), dtype=np.uint64).astype(np.uint32)
+    pool.set_palette(pal)
+    sun = rng.uniform(-1, 1, 3)
+    sun[rng.random(3) < 0.2] = 0.0
+    if not sun.any():
+        sun[int(rng.integers(0, 3))] = 1.0
+    sun = tuple(float(np.float32(x)) for x in sun)
+    reach = float(np.float32(rng.choice([1, 2, 8, 64]) * 2.0 ** -depth * rng.choice([1.0, float(rng.uniform(0.5, 2))])))
+    ao_shade = int(rng.integers(0, 65))
+    sun_shade = int(rng.integers(0, 257 - 4 * ao_shade))
+    flags = int(rng.choice([3, 3, 1, 2, 0]))
+    light = ort.Light(sun, reach, sun_shade, ao_shade, flags=flags)
+    pool.set_option("bounce_compact", int(rng.integers(0, 3)))
+    plan = rng.random() < 0.4
+    pool.set_option("tile_order", 2 if plan else int(rng.integers(0, 2)))
+    if plan:
+        pool.plan_views(cams, rc)
+    opts.update({"W": W, "H": H, "views": nv, "row_chunk": rc, "plan": plan, "flags": flags, "sun": sun})
+    rows = pool.slice_rows(H, rc, 1)
+    out = torch.full((nv * rows * W,), 7, dtype=torch.int32, device=dev)
+    out8 = torch.full((nv * rows * W,), 7, dtype=torch.uint8, device=dev)
+    pool.set_stream(torch.cuda.current_stream())
+    pool.render_lit_views_dev(cams, light, out, row_chunk=rc)
+    pool.render_lit_masks_views_dev(cams, light, out8, row_chunk=rc)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy().view(np.uint32).reshape(nv, rows * W)[:, :H * W]
+    got8 = out8.cpu().numpy().reshape(nv, rows * W)[:, :H * W]
+    miss = hits = 0
+    for v, (pos, fov, y, p) in enumerate(views):
+        e = Expected(O, ref_pool, pal, depth, pos, y, p, W, H, sun=sun, check_origins=False, fov=fov)
+        m = e.masks(flags, sun, reach)
+        miss += int((got8[v] != m.reshape(-1)).sum())
+        miss += int((got[v] != shade(e.plain.reshape(H, W), m, sun_shade, ao_shade).reshape(-1)).sum())
+        hits += len(e.hit)
+    return miss, nv * W * H, hits
+
+
 FORCE_SPLIT = [False]
 
 
@@ -423,7 +470,7 @@ def editor_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, scene, o, 
     return miss, n, int((r["dir"] < 6).sum())
 
 
-CASES = {"render": render_case, "codes": codes_case, "bounce_frames": bounce_frames_case, "image": image_case,
+CASES = {"render": render_case, "codes": codes_case, "bounce_frames": bounce_frames_case, "lit": lit_case, "image": image_case,
          "editor": editor_case, "steps": steps_case, "sharded_steps": sharded_steps_case}
 
 
