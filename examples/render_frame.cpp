@@ -4,12 +4,14 @@
 // Also traces the reference's per-frame pick ray (ORT/test_och_h_octree.cpp:527-536)
 // through the reference signature, tree.sse_trace(o, d, dir&, voxel&, t&).
 //
-//   make -C examples && ./examples/render_frame 10 out.ppm [width height yaw pitch] [--ssaa S | --lit]
+//   make -C examples && ./examples/render_frame 10 out.ppm [width height yaw pitch] [--ssaa S] [--lit]
 //
 // --ssaa S (2, 4 or 8, anywhere on the line): the same width x height frame
 // from S x S samples per pixel, resolved in the render kernel (tree.render_ssaa).
 // --lit (anywhere on the line): the frame with sun shadows and ambient
 // occlusion, secondary rays traced in the render's launch (tree.render_lit).
+// Both flags, in either order: S x S lit samples per pixel, shaded and then
+// averaged in one launch (tree.render_lit_ssaa).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -52,21 +54,25 @@ int main(int argc, char **argv)
         och::gpu::tree tree(hp.nodes, hp.n_nodes, hp.root, hp.depth);
         tree.set_palette(examples::reference_palette());
         std::vector<uint32_t> rgba((size_t)cam.width * cam.height);
+        // the sun over the camera's left shoulder; AO rays reach eight voxels along each axis
+        const och_light light = {{0.8F, 0.35F, 0.25F}, std::ldexp(8.0F, -depth), 96, 24, OCH_LIGHT_SUN | OCH_LIGHT_AO};
         if (ssaa) {
             och::gpu::camera samples = cam;             // the sample grid's camera
             samples.width *= ssaa;
             samples.height *= ssaa;
-            tree.render_ssaa(samples.update_position(), ssaa, rgba);
+            if (lit)
+                tree.render_lit_ssaa(samples.update_position(), light, ssaa, rgba);
+            else
+                tree.render_ssaa(samples.update_position(), ssaa, rgba);
             std::printf("%d x %d samples per pixel\n", ssaa, ssaa);
         } else if (lit) {
-            // the sun over the camera's left shoulder; AO rays reach eight voxels along each axis
-            const och_light light = {{0.8F, 0.35F, 0.25F}, std::ldexp(8.0F, -depth), 96, 24, OCH_LIGHT_SUN | OCH_LIGHT_AO};
             tree.render_lit(cam.update_position(), light, rgba);
-            std::printf("lit: sun (%g, %g, %g), ao reach %g\n", light.sun_dir[0], light.sun_dir[1], light.sun_dir[2],
-                        light.ao_reach);
         } else {
             tree.render(cam.update_position(), rgba.data());
         }
+        if (lit)
+            std::printf("lit: sun (%g, %g, %g), ao reach %g\n", light.sun_dir[0], light.sun_dir[1], light.sun_dir[2],
+                        light.ao_reach);
         // pick ray along the view direction (the demo traces camera.pos along its look vector)
         const float dx = cosf(cam.yaw) * cosf(cam.pitch), dy = sinf(cam.yaw) * cosf(cam.pitch), dz = sinf(cam.pitch);
         och::gpu::direction dir;

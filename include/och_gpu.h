@@ -172,7 +172,7 @@ typedef enum och_option {
     OCH_OPT_BOUNCE_COMPACT = 6,/* config 5: 1 (default) = compact each block's secondary rays into its first lanes
                                   (wave ballot/popcount + LDS queue) before tracing them; 0 = trace each in place;
                                   2 = per block, compact when that packs the block's secondary rays into fewer
-                                  waves than hold them, else in place.  Lit frames (och_gpu_render_lit_views_dev):
+                                  waves than hold them, else in place.  Lit frames (och_gpu_render_lit_views_dev, _lit_ssaa_views_dev):
                                   0 = every hit lane walks its own pixel's secondary rays, 1 or 2 = the block's
                                   hit pixels are compacted and their rays dealt over its lanes; same bytes */
     OCH_OPT_CULL = 8,          /* 1 (default) = a ray whose walk provably never enters the bounding box of the
@@ -382,8 +382,8 @@ OCH_API int och_gpu_render_ssaa(och_gpu_pool *pool, const och_camera *cam, int s
  * _views_dev: device buffers, asynchronous on the pool's stream;
  * och_gpu_render_lit: one camera, whole frame, host buffer, synchronous.
  * Out of scope: colour-code slices and the RCCL exchange paths, frame groups,
- * lit and supersampled frames together, lit and bounce together, more than
- * four AO rays. */
+ * lit and bounce together, more than four AO rays.  Lit and supersampled
+ * frames together: och_gpu_render_lit_ssaa_views_dev below. */
 enum { OCH_LIGHT_SUN = 1, OCH_LIGHT_AO = 2 };
 typedef struct och_light {
     float sun_dir[3];    /* towards the sun; traced as given */
@@ -401,6 +401,35 @@ OCH_API int och_gpu_render_lit_masks_views_dev(och_gpu_pool *pool, const och_cam
                                                int row_chunk, int shard, int n_shards);
 OCH_API int och_gpu_render_lit(och_gpu_pool *pool, const och_camera *cam, const och_light *light, uint32_t *rgba,
                                size_t capacity_pixels);
+/* Supersampled lit frames, s x s lit samples per pixel (s = 2, 4 or 8),
+ * traced, shaded and resolved in one launch; the sample-resolution frame is
+ * never stored.  cams are the cameras of the sample grid (equal width and
+ * height, both multiples of s), and view v's frame of (width / s) x
+ * (height / s) RGBA8 words goes to rgba + v * (width / s) * (height / s).
+ * With F the frames och_gpu_render_lit_views_dev writes for the same cameras
+ * and the same light as one shard with row_chunk = height, each byte is
+ *   out[Y][X].c = (sum over j, i < s of F[s Y + j][s X + i].c + s * s / 2) >> (2 log2 s):
+ * och_gpu_render_ssaa_views_dev's rule on the lit frame -- shade first, then
+ * the mean.  Everything else is the lit definition's: sky and INSIDE samples
+ * enter with the plain render's colour, alpha is 0xFF, no gamma, no jitter;
+ * the secondary origin, the ray directions, the mask rules, ao_reach (in
+ * units of t, not of output pixels) and the shade are unchanged.  So
+ * light.flags = 0 gives och_gpu_render_ssaa_views_dev's frame word for word.
+ * capacity_pixels is what rgba holds, in pixels.  Refused (OCH_E_INVALID)
+ * before anything is written: another s, a size that is no multiple of s,
+ * views of unequal size, n_views outside 1..OCH_MAX_VIEWS, a smaller buffer, a
+ * light och_light_check refuses, NULL pointers and a pool left torn by a
+ * failed flush.  Launch options change the dispatch only (OCH_OPT_TILE_ORDER 2
+ * uses och_gpu_plan_views' plan for these cameras with row_chunk = height,
+ * never its split form; OCH_OPT_BOUNCE_COMPACT as for lit frames).
+ * _views_dev: device buffer, asynchronous on the pool's stream;
+ * och_gpu_render_lit_ssaa: one camera into a host buffer, synchronous.
+ * Out of scope: a mask output, shards and row deals, colour-code slices and
+ * the RCCL exchange paths, frame groups, lit and bounce together. */
+OCH_API int och_gpu_render_lit_ssaa_views_dev(och_gpu_pool *pool, const och_camera *cams, int n_views,
+                                              const och_light *light, int s, uint32_t *rgba, size_t capacity_pixels);
+OCH_API int och_gpu_render_lit_ssaa(och_gpu_pool *pool, const och_camera *cam, const och_light *light, int s,
+                                    uint32_t *rgba, size_t capacity_pixels);
 /* The frame loop (update_image once per frame, ORT/test_och_h_octree.cpp:
  * 437-457) issued natively: n_steps whole frames of the same cameras
  * (och_gpu_render_views_dev, or _bounce_views_dev with bounce = 1; one shard),

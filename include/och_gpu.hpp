@@ -131,6 +131,19 @@ public:
         check(och_gpu_render_lit(pool_, &cam, &light, rgba, capacity_pixels), "och_gpu_render_lit");
     }
 
+    // The lit frame supersampled: cam is the camera of the sample grid, as for
+    // render_ssaa; every sample is render_lit's colour, shaded before the mean,
+    // all in one launch (och_gpu_render_lit_ssaa).
+    void render_lit_ssaa(const och_camera &cam, const och_light &light, int s, std::vector<uint32_t> &rgba) const
+    {
+        rgba.resize(static_cast<size_t>(cam.width / (s > 0 ? s : 1)) * static_cast<size_t>(cam.height / (s > 0 ? s : 1)));
+        check(och_gpu_render_lit_ssaa(pool_, &cam, &light, s, rgba.data(), rgba.size()), "och_gpu_render_lit_ssaa");
+    }
+    void render_lit_ssaa(const och_camera &cam, const och_light &light, int s, uint32_t *rgba, size_t capacity_pixels) const
+    {
+        check(och_gpu_render_lit_ssaa(pool_, &cam, &light, s, rgba, capacity_pixels), "och_gpu_render_lit_ssaa");
+    }
+
     och_gpu_pool *handle() const { return pool_; }
 
 private:

@@ -121,6 +121,8 @@ PROTOTYPES = {
     "och_gpu_render_lit_masks_views_dev": (C.c_int, [_P, _P, C.c_int, C.POINTER(Light), _P, C.c_size_t, C.c_int,
                                                      C.c_int, C.c_int]),
     "och_gpu_render_lit": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Light), _P, C.c_size_t]),
+    "och_gpu_render_lit_ssaa_views_dev": (C.c_int, [_P, _P, C.c_int, C.POINTER(Light), C.c_int, _P, C.c_size_t]),
+    "och_gpu_render_lit_ssaa": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Light), C.c_int, _P, C.c_size_t]),
     "och_gpu_render_steps_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int]),
     "och_gpu_set_row_deal": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "och_gpu_slice_rows": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),

@@ -1959,6 +1959,61 @@ OCH_API int och_gpu_render_lit(och_gpu_pool *p, const och_camera *cam, const och
     return OCH_OK;
 }
 
+OCH_API int och_gpu_render_lit_ssaa_views_dev(och_gpu_pool *p, const och_camera *cams, int n_views, const och_light *light,
+                                              int s, uint32_t *rgba, size_t capacity_pixels)
+{
+    OCH_ENTRY();
+    // every refusal comes before anything is written or launched
+    if (!p || !cams || !light || !rgba) return fail(OCH_E_INVALID, "NULL argument");
+    if (int ls = och_light_check(light)) return ls;
+    if (s != 2 && s != 4 && s != 8) return fail(OCH_E_INVALID, "samples per axis %d: must be 2, 4 or 8", s);
+    if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
+    if (int vs = och::check_views(cams, n_views)) return vs;
+    const int Ws = cams[0].width, Hs = cams[0].height;
+    if (Ws % s || Hs % s) return fail(OCH_E_INVALID, "sample grid %d x %d is not a multiple of %d", Ws, Hs, s);
+    if ((uint64_t)Ws * Hs * n_views >= (1ull << 32)) return fail(OCH_E_INVALID, "frame too large");
+    const size_t pixels = (size_t)n_views * (Ws / s) * (Hs / s);
+    if (capacity_pixels < pixels)
+        return fail(OCH_E_INVALID, "rgba holds %zu pixels, %d views of %d x %d need %zu", capacity_pixels, n_views, Ws / s,
+                    Hs / s, pixels);
+    if (int rs = check_ready(p)) return rs;
+    DeviceGuard g(p->device);
+    // the sample grid as the 1-sample render's whole frame: its plan, never the split form
+    const och::DevFrame f = make_frame(p, cams, n_views, rgba, nullptr, Hs, 0, 1);
+    int ts;
+    och::Schedule sc = timed_schedule(p, ts);
+    if (ts) return ts;
+    use_plan(p, f, false, false, sc);
+    OCH_HIP(och::launch_render_lit_ssaa(p->dev(), f, sc, *light, s == 2 ? 1 : s == 4 ? 2 : 3, p->stream()));
+    return timed_done(p, sc, true);
+}
+
+OCH_API int och_gpu_render_lit_ssaa(och_gpu_pool *p, const och_camera *cam, const och_light *light, int s, uint32_t *rgba,
+                                    size_t capacity_pixels)
+{
+    OCH_ENTRY();
+    if (!p || !cam || !light || !rgba) return fail(OCH_E_INVALID, "NULL argument");
+    if (int ls = och_light_check(light)) return ls;
+    if (s != 2 && s != 4 && s != 8) return fail(OCH_E_INVALID, "samples per axis %d: must be 2, 4 or 8", s);
+    if (int vs = och::check_views(cam, 1)) return vs;
+    if (cam->width % s || cam->height % s)
+        return fail(OCH_E_INVALID, "sample grid %d x %d is not a multiple of %d", cam->width, cam->height, s);
+    if (int rs = check_ready(p)) return rs;
+    // refused before the staging buffer is sized; the device form checks again
+    const size_t pixels = (size_t)(cam->width / s) * (size_t)(cam->height / s);
+    if (capacity_pixels < pixels)
+        return fail(OCH_E_INVALID, "rgba holds %zu pixels, %d x %d need %zu", capacity_pixels, cam->width / s,
+                    cam->height / s, pixels);
+    DeviceGuard g(p->device);
+    int st = ensure_scratch(p, pixels * 4 + 4);
+    if (st != OCH_OK) return st;
+    st = och_gpu_render_lit_ssaa_views_dev(p, cam, 1, light, s, reinterpret_cast<uint32_t *>(p->scratch.d), pixels);
+    if (st != OCH_OK) return st;
+    OCH_HIP(hipMemcpyAsync(rgba, p->scratch.d, pixels * 4, hipMemcpyDeviceToHost, p->stream()));
+    OCH_HIP(hipStreamSynchronize(p->stream()));
+    return OCH_OK;
+}
+
 OCH_API int och_gpu_render_steps_dev(och_gpu_pool *p, const och_camera *cams, int n_views, int n_steps,
                                      void *const *streams, uint32_t *const *frames, int n_buffers,
                                      void *const *start_events, void *const *stop_events, int row_chunk, int bounce)

@@ -203,6 +203,12 @@ hipError_t launch_render_ssaa(const DevPool &p, const DevFrame &f, const Schedul
 // when it is an unsplit permutation of this grid.
 hipError_t launch_render_lit(const DevPool &p, const DevFrame &f, const Schedule &sc, const och_light &light,
                              uint8_t *masks, hipStream_t stream);
+// Supersampled lit frames (k_trace_lit_ssaa): launch_render_ssaa's sample grid
+// and output, every sample launch_render_lit's frame colour under light.  One
+// shard's whole frame, width and height multiples of s, block <= 1024;
+// sc.bounce_compact and sc.order as for launch_render_lit.
+hipError_t launch_render_lit_ssaa(const DevPool &p, const DevFrame &f, const Schedule &sc, const och_light &light,
+                                  int log2_s, hipStream_t stream);
 // The split planner's counting render: each pixel's walked PUSH count (16 bits)
 // into push, indexed as the frame's slices.
 hipError_t launch_render_push(const DevPool &p, const DevFrame &f, const Schedule &sc, uint16_t *push, hipStream_t stream);

@@ -1591,6 +1591,117 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_lit(DevPool P, Came
     if (stamps) stamp(stamps, stamp_cap, t0, kinds * total);
 }
 
+// Words per thread of k_trace_lit_ssaa's sample queue: the secondary origin (3)
+// and the state word.  The colour and the output word stay with the sample's lane.
+constexpr uint32_t kLitSsaaQueueWords = 4;
+
+// Supersampled lit frames (och_gpu_render_lit_ssaa_views_dev):
+// the cameras are the sample grid as for k_trace_ssaa, every sample the colour
+// k_trace_lit's frame sink would store, the output word their per-channel mean.
+// The primary pass, the queue behind the stacks, the kind-major ray list and
+// the OR into the state word are k_trace_lit's.  What differs is the way back:
+// a sample's lane keeps its plain colour and its queue slot q in registers, and
+// after the last barrier reads its finished mask from slot q and shades its own
+// colour -- so the queue carries neither the colour nor an output index, and
+// every lane holds its sample's final colour when the wave reaches block_sum,
+// which runs behind the barrier, outside the secondary loop (lane_xor needs all
+// 64 lanes).  Lanes without a sample add 0; blocks are whole (k_trace_ssaa).
+// compact as in k_trace_lit; both forms write the same bytes.
+template <int kPacked, int kLog2S>
+__global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_lit_ssaa(DevPool P, CameraSource S, FrameSink K, och_light L, int compact,
+                                                                      uint32_t xcd_group, const uint32_t *__restrict__ order,
+                                                                      uint64_t *stamps, uint32_t stamp_cap)
+{
+    extern __shared__ uint32_t lds_stack[];
+    __shared__ uint32_t wave_count[16];
+    constexpr uint32_t kS = 1u << kLog2S;
+    const uint64_t t0 = stamps ? realtime() : 0;
+    const uint32_t blk = order ? order[blockIdx.x] : xcd_block(blockIdx.x, gridDim.x, xcd_group);
+    const uint32_t nb = blockDim.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t stack = stack_column(lds_stack, P.depth);
+    // the queue starts where the stacks' word plane ends (launch_lit_ssaa_as sizes both)
+    uint32_t *queue = lds_stack + (stack - 4u * threadIdx.x - (uint32_t)(uintptr_t)(const lds_word *)lds_stack) / 4u +
+                      ((uint32_t)P.depth + 1u) * nb;
+    const uint32_t wave_base = blk * nb + (threadIdx.x & ~63u);
+    const uint32_t first = (L.flags & OCH_LIGHT_SUN) ? 0u : 1u;
+    const uint32_t kinds = ((L.flags & OCH_LIGHT_SUN) ? 1u : 0u) + ((L.flags & OCH_LIGHT_AO) ? 4u : 0u);
+    float o[3], d[3], p[3], d2[3];
+    uint32_t out, word = ~0u, colour = 0, state = kLitNoPixel;
+    bool want = false;
+    bool miss;
+    if (wave_base + lane < S.count() && S.get_wave_culled(wave_base, lane, P, P.cull != 0, o, d, out, miss)) {
+        // this sample's output word: view * W * H + Y * W + X
+        uint32_t view, tx, ty;
+        S.tile_of(__builtin_amdgcn_readfirstlane(wave_base), view, tx, ty);
+        const uint32_t w = (uint32_t)S.width >> kLog2S, h = (uint32_t)S.height >> kLog2S;
+        word = (view * h + ((ty * kTileH + lane / kTileW) >> kLog2S)) * w + ((tx * kTileW + lane % kTileW) >> kLog2S);
+        if (miss) {                                 // proven before setup: the sky
+            colour = pixel_colour(Hit{OCH_EXIT, 0u, P.miss_bits, 0u}, K.palette, K.n_voxels);
+        } else {
+            Ray r;
+            ray_trace<kPacked, false, true, kAsmLoad>(r, P, o, d, stack, nb, !P.cam_cull);
+            const Hit h1 = ray_result<kPacked, kAsmLoad>(r, P);
+            want = h1.dir < OCH_EXIT;
+            colour = pixel_colour(h1, K.palette, K.n_voxels);
+            if (want) {
+                bounce_ray(o, d, h1, P.half_voxel, p, d2);
+                state = (uint32_t)h1.dir;
+                if ((L.flags & OCH_LIGHT_SUN) && !lit_faces_sun(L, state)) state |= 0x30u << 8;   // self-shadowed
+            }
+        }
+    }
+    uint32_t q = threadIdx.x, total = nb;
+    if (compact) {
+        const uint64_t bal = __ballot(want);
+        if (lane == 0) wave_count[wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t base = 0;
+        total = 0;
+        for (uint32_t w = 0; w < (nb >> 6); ++w) {
+            const uint32_t cnt = wave_count[w];
+            base += w < wave ? cnt : 0u;
+            total += cnt;
+        }
+        q = base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    }
+    if (want) {
+        queue[0 * nb + q] = fbits(p[0]);
+        queue[1 * nb + q] = fbits(p[1]);
+        queue[2 * nb + q] = fbits(p[2]);
+    }
+    if (want || !compact) queue[3 * nb + q] = state;
+    __syncthreads();
+    // ray j of the list: kind first + j / total of queued sample j % total
+    for (uint32_t j = threadIdx.x; j < kinds * total; j += nb) {
+        uint32_t pix = j, kind = first;
+        while (pix >= total) {
+            pix -= total;
+            ++kind;
+        }
+        const uint32_t st = queue[3 * nb + pix];    // the direction and bit 5 are final; other lanes OR bits 0..4
+        if ((st & 0xFFu) == kLitNoPixel || (kind == 0 && (st & (0x20u << 8)) != 0)) continue;   // self-shadowed: no ray
+        float so[3], sd[3];
+        so[0] = ffrom(queue[0 * nb + pix]);
+        so[1] = ffrom(queue[1 * nb + pix]);
+        so[2] = ffrom(queue[2 * nb + pix]);
+        lit_ray_dir(L, kind, st & 0xFFu, sd);
+        Ray r;
+        ray_trace<kPacked, false, true, kAsmLoad>(r, P, so, sd, stack, nb);
+        const uint32_t bit = lit_ray_bit(L, kind, ray_result<kPacked, kAsmLoad>(r, P));
+        if (bit) atomicOr(&queue[3 * nb + pix], bit << 8);
+    }
+    __syncthreads();
+    // the masks are final: a hit sample's lane takes its own from its slot
+    if (want) colour = lit_shade(colour, (queue[3 * nb + q] >> 8) & 0xFFu, L);
+    // every lane is here: R | B and G | A as 16-bit sums over the block
+    const uint32_t rb = block_sum<kLog2S>(colour & 0x00FF00FFu), ga = block_sum<kLog2S>((colour >> 8) & 0x00FF00FFu);
+    if (word != ~0u && (lane & (kS - 1u)) == 0 && ((lane >> 3) & (kS - 1u)) == 0) {
+        constexpr uint32_t half = (kS * kS / 2u) * 0x00010001u;
+        K.out[word] = (((rb + half) >> (2 * kLog2S)) & 0x00FF00FFu) | ((((ga + half) >> (2 * kLog2S)) & 0x00FF00FFu) << 8);
+    }
+    if (stamps) stamp(stamps, stamp_cap, t0, kinds * total);
+}
+
 __global__ __launch_bounds__(256) void k_raygen(och_camera C, float *__restrict__ dirs)
 {
     const int col = blockIdx.x * 16 + (threadIdx.x & 15);
@@ -1902,6 +2013,57 @@ hipError_t launch_render_ssaa(const DevPool &p, const DevFrame &f, const Schedul
     const FrameSink k{f.out, f.palette, f.n_voxels};
     return p.packed ? launch_ssaa_layout<1>(p, src, k, sc, log2_s, stream)
                     : launch_ssaa_layout<0>(p, src, k, sc, log2_s, stream);
+}
+
+namespace {
+
+// LDS of a supersampled lit launch: the parent stacks and, behind them, the
+// sample queue (k_trace_lit_ssaa), which must outlive the secondary walks.
+template <int kPacked, int kLog2S>
+hipError_t launch_lit_ssaa_as(const DevPool &p, const CameraSource &s, const FrameSink &k, const och_light &light,
+                              const Schedule &sc, hipStream_t stream)
+{
+    const uint32_t block = (uint32_t)sc.block, n = s.count();
+    const uint32_t grid = (n + block - 1) / block;
+    const size_t lds = stack_bytes(p.depth, (int)block) + (size_t)kLitSsaaQueueWords * block * sizeof(uint32_t);
+    const uint32_t xcd_group = sc.tile_order == 1 && 64u * 64u >= block ? 64u * 64u / block : 0u;
+    // a plan is a permutation of exactly this grid's workgroups (launch_as); a
+    // split plan never reaches this kernel (split_tile maps lanes to rays differently)
+    const uint32_t *order = sc.order_n == grid && !sc.split_tasks ? sc.order : nullptr;
+    OCH_LAUNCH_TIMED(sc, (k_trace_lit_ssaa<kPacked, kLog2S>), dim3(grid), dim3(block), lds, stream, p, s, k, light,
+                     sc.bounce_compact, xcd_group, order, sc.stamps, sc.stamp_cap);
+    return hipGetLastError();
+}
+
+template <int kPacked>
+hipError_t launch_lit_ssaa_layout(const DevPool &p, const CameraSource &s, const FrameSink &k, const och_light &light,
+                                  const Schedule &sc, int log2_s, hipStream_t stream)
+{
+    switch (log2_s) {
+    case 1: return launch_lit_ssaa_as<kPacked, 1>(p, s, k, light, sc, stream);
+    case 2: return launch_lit_ssaa_as<kPacked, 2>(p, s, k, light, sc, stream);
+    case 3: return launch_lit_ssaa_as<kPacked, 3>(p, s, k, light, sc, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_render_lit_ssaa(const DevPool &p, const DevFrame &f, const Schedule &sc, const och_light &light,
+                                  int log2_s, hipStream_t stream)
+{
+    if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
+    if ((uint32_t)sc.block > 1024u) return hipErrorInvalidValue;          // wave_count holds 16 waves
+    // the sample grid as one shard's whole frame: the kernel takes slice rows for rows
+    if (f.n_shards != 1 || f.shard != 0 || f.row_chunk != f.cams[0].height || f.slice_rows != f.cams[0].height)
+        return hipErrorInvalidValue;
+    const int s = 1 << log2_s;
+    if (f.cams[0].width % s || f.cams[0].height % s) return hipErrorInvalidValue;
+    const CameraSource src = camera_source(p, f, sc);
+    if (src.count() == 0) return hipSuccess;
+    const FrameSink k{f.out, f.palette, f.n_voxels};
+    return p.packed ? launch_lit_ssaa_layout<1>(p, src, k, light, sc, log2_s, stream)
+                    : launch_lit_ssaa_layout<0>(p, src, k, light, sc, log2_s, stream);
 }
 
 hipError_t launch_render_push(const DevPool &p, const DevFrame &f, const Schedule &sc, uint16_t *push, hipStream_t stream)

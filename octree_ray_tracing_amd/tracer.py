@@ -384,6 +384,31 @@ class GpuPool:
         self._lit_views("och_gpu_render_lit_masks_views_dev", cams, light, mask_slices, 1, capacity_pixels, row_chunk,
                         shard, n_shards)
 
+    def render_lit_ssaa(self, cam: Camera, light: Light, s: int) -> np.ndarray:
+        """The lit frame of `cam` (the sample grid's camera, as for render_ssaa) supersampled s x s:
+        (H / s, W / s) uint32, every sample shaded as render_lit shades it, then the rounded mean
+        (och_gpu_render_lit_ssaa; box_downsample(shade_lit(...)) states it on the host)."""
+        s = int(s)
+        out = np.empty((cam.height // s, cam.width // s) if s > 0 else (0, 0), np.uint32)
+        call("och_gpu_render_lit_ssaa", self._h, C.byref(cam), C.byref(light), s, _np_ptr(out), out.size)
+        return out
+
+    def render_lit_ssaa_views_dev(self, cams, light: Light, s: int, rgba, capacity_pixels: int | None = None):
+        """Several equal-size sample-grid cameras, lit and supersampled s x s in one launch
+        (och_gpu_render_lit_ssaa_views_dev): rgba (a device tensor of 4-byte words, or a raw pointer with
+        capacity_pixels) receives the views' (H / s) x (W / s) frames back to back.  Asynchronous on the
+        pool's stream."""
+        arr = (Camera * len(cams))(*cams)
+        s = int(s)
+        if s in (2, 4, 8) and cams:              # any other s the library refuses before it touches rgba
+            _need(rgba, 4 * len(cams) * (cams[0].width // s) * (cams[0].height // s), "rgba")
+        if capacity_pixels is None:
+            if not (hasattr(rgba, "numel") and hasattr(rgba, "element_size")):
+                raise ValueError("a raw pointer needs capacity_pixels")
+            capacity_pixels = rgba.numel() * rgba.element_size() // 4
+        call("och_gpu_render_lit_ssaa_views_dev", self._h, C.cast(arr, C.c_void_p), len(cams), C.byref(light), s,
+             _dev_ptr(rgba), int(capacity_pixels))
+
     def render_steps_dev(self, cams, frames, streams, n_steps: int, events=None, row_chunk: int | None = None,
                          bounce: bool = False):
         """n_steps whole frames of these cameras issued by the library's own loop

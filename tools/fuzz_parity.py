@@ -23,6 +23,9 @@ corners and edges); then one launch path with random options:
   lit       lit RGBA8 frames and mask bytes (och_gpu_render_lit_views_dev / _lit_masks_views_dev):
             random suns (zero components now and then), reaches, shades and flags, both
             compaction forms; only with --paths (the default campaign keeps its paths)
+  lit_ssaa  supersampled lit frames (och_gpu_render_lit_ssaa_views_dev), s = 2, 4, 8: the lit path's
+            lights and options, the expected frame the box mean of the oracle's lit sample grid;
+            only with --paths
   image     och_gpu_trace_batch_image (host rays, x + y * W, 8x8 tiles)
   editor    h_octree::set edits flushed to the device pool in 1-3 windows
   steps     the N = 1 frame loop issued by the library (och_gpu_render_steps_dev)
@@ -262,15 +265,9 @@ def bounce_frames_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, sce
     return compare_frames(O, ref_pool, got, views, W, H, pal, True)
 
 
-def lit_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, scene, o, d):
-    """Lit frames and their mask bytes against the oracle's primary and secondary
-    records (tests/test_gpu_lit.py's Expected states the definition in numpy)."""
-    from test_gpu_lit import Expected, shade
-    W, H, nv = int(rng.integers(1, 193)), int(rng.integers(1, 121)), int(rng.integers(1, 4))
-    rc = int(rng.choice([1, 4, 8, 16]))
-    views, cams = random_views(rng, ort, depth, W, H, nv)
-    pal = rng.integers(0, 2 ** 32, 6 * int(rng.integers(1, 300)), dtype=np.uint64).astype(np.uint32)
-    pool.set_palette(pal)
+def random_light(rng, ort, depth):
+    """A random light: a sun with zero components now and then, a reach of 1 to 64 voxels (sometimes
+    off the voxel grid), shades within och_light_check's bound, any flags."""
     sun = rng.uniform(-1, 1, 3)
     sun[rng.random(3) < 0.2] = 0.0
     if not sun.any():
@@ -281,6 +278,19 @@ def lit_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, scene, o, d):
     sun_shade = int(rng.integers(0, 257 - 4 * ao_shade))
     flags = int(rng.choice([3, 3, 1, 2, 0]))
     light = ort.Light(sun, reach, sun_shade, ao_shade, flags=flags)
+    return light, sun, reach, sun_shade, ao_shade, flags
+
+
+def lit_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, scene, o, d):
+    """Lit frames and their mask bytes against the oracle's primary and secondary
+    records (tests/test_gpu_lit.py's Expected states the definition in numpy)."""
+    from test_gpu_lit import Expected, shade
+    W, H, nv = int(rng.integers(1, 193)), int(rng.integers(1, 121)), int(rng.integers(1, 4))
+    rc = int(rng.choice([1, 4, 8, 16]))
+    views, cams = random_views(rng, ort, depth, W, H, nv)
+    pal = rng.integers(0, 2 ** 32, 6 * int(rng.integers(1, 300)), dtype=np.uint64).astype(np.uint32)
+    pool.set_palette(pal)
+    light, sun, reach, sun_shade, ao_shade, flags = random_light(rng, ort, depth)
     pool.set_option("bounce_compact", int(rng.integers(0, 3)))
     plan = rng.random() < 0.4
     pool.set_option("tile_order", 2 if plan else int(rng.integers(0, 2)))
@@ -304,6 +314,38 @@ def lit_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, scene, o, d):
         miss += int((got[v] != shade(e.plain.reshape(H, W), m, sun_shade, ao_shade).reshape(-1)).sum())
         hits += len(e.hit)
     return miss, nv * W * H, hits
+
+
+def lit_ssaa_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, scene, o, d):
+    """Supersampled lit frames against the oracle's records of the sample grid, built as lit_case
+    builds them, then the box mean (tests/test_gpu_lit_ssaa.py's Expected, shade and downsample)."""
+    from test_gpu_lit_ssaa import Expected, downsample, shade
+    s = int(rng.choice([2, 4, 8]))
+    W, H, nv = int(rng.integers(1, 192 // s + 1)), int(rng.integers(1, 120 // s + 1)), int(rng.integers(1, 4))
+    Ws, Hs = W * s, H * s
+    views, cams = random_views(rng, ort, depth, Ws, Hs, nv)
+    pal = rng.integers(0, 2 ** 32, 6 * int(rng.integers(1, 300)), dtype=np.uint64).astype(np.uint32)
+    pool.set_palette(pal)
+    light, sun, reach, sun_shade, ao_shade, flags = random_light(rng, ort, depth)
+    compact = int(rng.integers(0, 3))
+    pool.set_option("bounce_compact", compact)
+    plan = rng.random() < 0.4
+    pool.set_option("tile_order", 2 if plan else int(rng.integers(0, 2)))
+    if plan:
+        pool.plan_views(cams)
+    opts.update({"s": s, "W": W, "H": H, "views": nv, "bounce_compact": compact, "plan": plan, "flags": flags, "sun": sun})
+    out = torch.full((nv * H * W,), 7, dtype=torch.int32, device=dev)
+    pool.set_stream(torch.cuda.current_stream())
+    pool.render_lit_ssaa_views_dev(cams, light, s, out)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy().view(np.uint32).reshape(nv, H * W)
+    miss = hits = 0
+    for v, (pos, fov, y, p) in enumerate(views):
+        e = Expected(O, ref_pool, pal, depth, pos, y, p, Ws, Hs, sun=sun, check_origins=False, fov=fov)
+        lit = shade(e.plain.reshape(Hs, Ws), e.masks(flags, sun, reach), sun_shade, ao_shade)
+        miss += int((got[v] != downsample(lit, s).reshape(-1)).sum())
+        hits += len(e.hit)
+    return miss, nv * Ws * Hs, hits
 
 
 FORCE_SPLIT = [False]
@@ -470,7 +512,8 @@ def editor_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, scene, o, 
     return miss, n, int((r["dir"] < 6).sum())
 
 
-CASES = {"render": render_case, "codes": codes_case, "bounce_frames": bounce_frames_case, "lit": lit_case, "image": image_case,
+CASES = {"render": render_case, "codes": codes_case, "bounce_frames": bounce_frames_case, "lit": lit_case, "lit_ssaa": lit_ssaa_case,
+         "image": image_case,
          "editor": editor_case, "steps": steps_case, "sharded_steps": sharded_steps_case}
 
 

@@ -23,7 +23,8 @@ with the product's flags and checks, in every function that issues the load
      this hazard).  The compiler keeps that distance in
      its own code (its minimum over these kernels is 2); the check holds the
      hand-placed VALU of the descent's child index (ray_push_descend) to it.
-  4. every traversal kernel (k_trace_grid, k_trace_ssaa, k_trace_bounce, k_trace_lit) admits
+  4. every traversal kernel (k_trace_grid, k_trace_ssaa, k_trace_bounce, k_trace_lit and, by
+     that substring, k_trace_lit_ssaa) admits
      8 waves per SIMD by its SGPR and VGPR counts (above 80 SGPRs a SIMD takes 7, although
      the compiler's occupancy note still says 8).
   5. no grid or supersampling kernel spills SGPRs to VGPR lanes (the config-5
@@ -228,6 +229,7 @@ def check_mask_hazards(name: str, lines: list[str]) -> list[str]:
 
 TRAVERSAL = ("k_trace_grid", "k_trace_ssaa", "k_trace_bounce", "k_trace_lit")   # every kernel that walks the DAG
 NO_SPILL = ("k_trace_grid", "k_trace_ssaa")                       # check 5
+LIT_SSAA = "k_trace_lit_ssaa"                                     # in TRAVERSAL through "k_trace_lit", not in NO_SPILL
 RENDER_KERNEL = "k_trace_gridINS0_12CameraSourceENS0_9FrameSinkELi1ELb0"   # the bench's render launch
 
 
@@ -333,10 +335,15 @@ def main(argv=None) -> int:
         summary["ssaa_sgpr"], summary["ssaa_vgpr"] = [res[n][0] for n in ssaa], [res[n][1] for n in ssaa]
     summary["bounce_spill_lanes"] = sum(v for n, v in spills.items() if "k_trace_bounce" in n)
     # the lit kernels' registers (both sinks, both layouts) and their spills (counted, like config 5's)
-    lit = sorted(n for n in res if "k_trace_lit" in n)
+    lit = sorted(n for n in res if "k_trace_lit" in n and LIT_SSAA not in n)
     if lit:
         summary["lit_sgpr"], summary["lit_vgpr"] = [res[n][0] for n in lit], [res[n][1] for n in lit]
-    summary["lit_spill_lanes"] = sum(v for n, v in spills.items() if "k_trace_lit" in n)
+    summary["lit_spill_lanes"] = sum(v for n, v in spills.items() if "k_trace_lit" in n and LIT_SSAA not in n)
+    # the supersampled lit kernels' (both layouts, s = 2, 4, 8): traversal kernels under "k_trace_lit", spills counted
+    lit_ssaa = sorted(n for n in res if LIT_SSAA in n)
+    if lit_ssaa:
+        summary["lit_ssaa_sgpr"], summary["lit_ssaa_vgpr"] = [res[n][0] for n in lit_ssaa], [res[n][1] for n in lit_ssaa]
+    summary["lit_ssaa_spill_lanes"] = sum(v for n, v in spills.items() if LIT_SSAA in n)
     for n, v in spills.items():
         if v and any(k in n for k in NO_SPILL):
             problems.append(f"{n}: {v} SGPR spill lanes (v_writelane / v_readlane)")
