@@ -5,10 +5,15 @@
 // frames of two views (pitch 0 and -0.6), reports the frame time, writes
 // view `view` of the last device's copy as a PPM.
 //
-//   ./examples/multi_gpu_frame 12 3840 2160 out.ppm [n_devices] [frames] [view]
+//   ./examples/multi_gpu_frame 12 3840 2160 out.ppm [n_devices] [frames] [view] [--lit]
+//
+// --lit (anywhere on the line): lit frames, render_frame --lit's light; the
+// devices exchange 2-byte lit codes (frame_group::render_lit).
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "och_gpu.hpp"
@@ -16,6 +21,14 @@
 
 int main(int argc, char **argv)
 {
+    bool lit = false;
+    for (int i = 1; i < argc; ++i)
+        if (std::strcmp(argv[i], "--lit") == 0) {       // taken out of the positional arguments
+            lit = true;
+            for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+            argc -= 1;
+            break;
+        }
     const int depth = argc > 1 ? std::atoi(argv[1]) : 12;
     const int W = argc > 2 ? std::atoi(argv[2]) : 3840, H = argc > 3 ? std::atoi(argv[3]) : 2160;
     const char *path = argc > 4 ? argv[4] : "multi_gpu_frame.ppm";
@@ -46,15 +59,21 @@ int main(int argc, char **argv)
             cam.height = H;
             cams.push_back(cam.update_position());
         }
+        // the sun over the camera's left shoulder; AO rays reach eight voxels along each axis
+        const och_light light = {{0.8F, 0.35F, 0.25F}, std::ldexp(8.0F, -depth), 96, 24, OCH_LIGHT_SUN | OCH_LIGHT_AO};
+        auto render = [&] {
+            if (lit) group.render_lit(cams, light);
+            else group.render(cams);
+        };
         group.plan(cams);                         // costliest tiles first (one timed render per device)
-        group.render(cams);                       // warm-up
+        render();                                 // warm-up
         group.synchronize();
         const auto t0 = std::chrono::steady_clock::now();
-        for (int f = 0; f < frames; ++f) group.render(cams);
+        for (int f = 0; f < frames; ++f) render();
         group.synchronize();
         const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        std::printf("%d devices, %dx%d x2 views, depth %d: %.4f ms per frame pair, %.1f Mrays/s\n", n, W, H, depth,
-                    s / frames * 1e3, 2.0 * W * H * frames / s / 1e6);
+        std::printf("%d devices, %dx%d x2 views, depth %d%s: %.4f ms per frame pair, %.1f Mrays/s\n", n, W, H, depth,
+                    lit ? ", lit" : "", s / frames * 1e3, 2.0 * W * H * frames / s / 1e6);
         std::vector<uint32_t> rgba((size_t)2 * W * H);
         group.download(n - 1, rgba.data());
         if (!examples::write_ppm(path, rgba.data() + (size_t)view * W * H, W, H)) rc = 1;

@@ -13,12 +13,17 @@
 // Rank 0 reports the frame time and writes view `view` of its last frame as
 // a PPM.
 //
-//   ./examples/sharded_frame depth W H out.ppm rank n_ranks id_file [frames] [view]
+//   ./examples/sharded_frame depth W H out.ppm rank n_ranks id_file [frames] [view] [--lit]
+//
+// --lit (anywhere on the line): lit frames, render_frame --lit's light, through
+// och_gpu_render_lit_sharded_steps_dev: the ranks send 2-byte lit codes.
 #include <hip/hip_runtime_api.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <string>
 #include <thread>
@@ -58,8 +63,16 @@ och::gpu::comm::id_t share_id(int rank, const std::string &path)
 
 int main(int argc, char **argv)
 {
+    bool lit = false;
+    for (int i = 1; i < argc; ++i)
+        if (std::strcmp(argv[i], "--lit") == 0) {       // taken out of the positional arguments
+            lit = true;
+            for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1];
+            argc -= 1;
+            break;
+        }
     if (argc < 8) {
-        std::fprintf(stderr, "usage: sharded_frame depth W H out.ppm rank n_ranks id_file [frames] [view]\n");
+        std::fprintf(stderr, "usage: sharded_frame depth W H out.ppm rank n_ranks id_file [frames] [view] [--lit]\n");
         return 2;
     }
     const int depth = std::atoi(argv[1]), W = std::atoi(argv[2]), H = std::atoi(argv[3]);
@@ -108,7 +121,9 @@ int main(int argc, char **argv)
         och::gpu::check(och_gpu_set_option(tree.handle(), OCH_OPT_TILE_ORDER, 2), "och_gpu_set_option");
         int rows = 0;
         och::gpu::check(och_gpu_slice_rows(tree.handle(), H, kChunk, n_ranks, &rows), "och_gpu_slice_rows");
-        const size_t slice = (size_t)kViews * rows * W;
+        const size_t slice = (size_t)kViews * rows * W * (lit ? 2 : 1);   // bytes: lit codes hold two per pixel
+        // the sun over the camera's left shoulder; AO rays reach eight voxels along each axis
+        const och_light light = {{0.8F, 0.35F, 0.25F}, std::ldexp(8.0F, -depth), 96, 24, OCH_LIGHT_SUN | OCH_LIGHT_AO};
         std::vector<void *> st(kBuffers);
         std::vector<uint8_t *> slices(kBuffers), gathered(kBuffers, nullptr);
         std::vector<uint32_t *> frames_dev(kBuffers, nullptr);
@@ -130,11 +145,18 @@ int main(int argc, char **argv)
             }
         }
         auto run = [&](int n) {
-            och::gpu::check(och_gpu_render_sharded_steps_dev(tree.handle(), comm.handle(), cams.data(), kViews, n,
-                                                             st.data(), slices.data(), gathered.data(),
-                                                             frames_dev.data(), kBuffers, nullptr, nullptr, kChunk,
-                                                             /*bounce*/ 0, OCH_EXCHANGE_GATHER),
-                            "och_gpu_render_sharded_steps_dev");
+            if (lit)
+                och::gpu::check(och_gpu_render_lit_sharded_steps_dev(tree.handle(), comm.handle(), cams.data(), kViews, n,
+                                                                     st.data(), slices.data(), gathered.data(),
+                                                                     frames_dev.data(), kBuffers, nullptr, nullptr,
+                                                                     kChunk, &light, OCH_EXCHANGE_GATHER),
+                                "och_gpu_render_lit_sharded_steps_dev");
+            else
+                och::gpu::check(och_gpu_render_sharded_steps_dev(tree.handle(), comm.handle(), cams.data(), kViews, n,
+                                                                 st.data(), slices.data(), gathered.data(),
+                                                                 frames_dev.data(), kBuffers, nullptr, nullptr, kChunk,
+                                                                 /*bounce*/ 0, OCH_EXCHANGE_GATHER),
+                                "och_gpu_render_sharded_steps_dev");
             for (hipStream_t s : streams) hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
         };
         run(kBuffers);                                           // warm-up

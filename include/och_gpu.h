@@ -381,9 +381,13 @@ OCH_API int och_gpu_render_ssaa(och_gpu_pool *pool, const och_camera *cam, int s
  * OCH_OPT_BOUNCE_COMPACT picks how the secondary rays are dealt over lanes).
  * _views_dev: device buffers, asynchronous on the pool's stream;
  * och_gpu_render_lit: one camera, whole frame, host buffer, synchronous.
- * Out of scope: colour-code slices and the RCCL exchange paths, frame groups,
- * lit and bounce together, more than four AO rays.  Lit and supersampled
- * frames together: och_gpu_render_lit_ssaa_views_dev below. */
+ * Across GPUs a lit frame travels as lit codes (below): och_gpu_render_lit_
+ * codes_views_dev, och_gpu_shade_lit_unshard_views_dev, the windows
+ * och_gpu_render_lit_steps_dev / _lit_sharded_steps_dev and
+ * och_frame_group_render_lit.
+ * Out of scope: lit and bounce together, more than four AO rays, supersampled
+ * lit frames through the sharded paths.  Lit and supersampled frames together
+ * on one GPU: och_gpu_render_lit_ssaa_views_dev below. */
 enum { OCH_LIGHT_SUN = 1, OCH_LIGHT_AO = 2 };
 typedef struct och_light {
     float sun_dir[3];    /* towards the sun; traced as given */
@@ -401,6 +405,31 @@ OCH_API int och_gpu_render_lit_masks_views_dev(och_gpu_pool *pool, const och_cam
                                                int row_chunk, int shard, int n_shards);
 OCH_API int och_gpu_render_lit(och_gpu_pool *pool, const och_camera *cam, const och_light *light, uint32_t *rgba,
                                size_t capacity_pixels);
+/* Lit codes: the lit frame's exchange format between GPUs, one little-endian
+ * uint16 per pixel, code | mask << 8.  code is the OCH_CODE_* byte
+ * och_gpu_render_codes_views_dev (bounce = 0) writes for the pixel (a palette
+ * index, OCH_CODE_MAGENTA, _INSIDE or _SKY; never | OCH_CODE_BLOCKED); mask is
+ * the byte och_gpu_render_lit_masks_views_dev writes for it under the same
+ * light.  The lit word of a pixel is the code table's word shaded by the mask
+ * as above; a mask of 0x80 has w = 256, so one formula serves every pixel and
+ * flags = 0 gives the plain sharded frame word for word.  The whole mask
+ * travels, not the shade level: the shading rank may use other weights than
+ * the rendering ranks were given.  2 B per pixel, half of RGBA8; a lossless
+ * single byte does not exist (some 123 codes x 10 shade levels > 256).
+ * och_gpu_render_lit_codes_views_dev: slices laid out as the mask slices, 2 B
+ * per pixel; och_gpu_render_lit_views_dev's refusals, and a palette of more
+ * than OCH_CODE_MAX_VOXELS ids (or none), all before anything is written; the
+ * same plan rule.  och_gpu_shade_lit_unshard_views_dev: gathered lit codes
+ * [n_shards][n_views][rows][W] -> RGBA8 frames [n_views][H][W], every word the
+ * one och_gpu_render_lit_views_dev writes under light (only its sun_shade and
+ * ao_shade are read); refuses a light och_light_check refuses and a pool
+ * without a code table. */
+OCH_API int och_gpu_render_lit_codes_views_dev(och_gpu_pool *pool, const och_camera *cams, int n_views,
+                                               const och_light *light, uint16_t *code_slices, size_t capacity_pixels,
+                                               int row_chunk, int shard, int n_shards);
+OCH_API int och_gpu_shade_lit_unshard_views_dev(och_gpu_pool *pool, const uint16_t *gathered, uint32_t *frames,
+                                                int width, int height, int row_chunk, int n_shards, int n_views,
+                                                const och_light *light);
 /* Supersampled lit frames, s x s lit samples per pixel (s = 2, 4 or 8),
  * traced, shaded and resolved in one launch; the sample-resolution frame is
  * never stored.  cams are the cameras of the sample grid (equal width and
@@ -443,6 +472,12 @@ OCH_API int och_gpu_render_steps_dev(och_gpu_pool *pool, const och_camera *cams,
                                      void *const *streams, uint32_t *const *frames, int n_buffers,
                                      void *const *start_events, void *const *stop_events, int row_chunk,
                                      int bounce);
+/* The same loop with every frame a lit frame (och_gpu_render_lit_views_dev as
+ * one shard); the light is checked before the first frame is queued. */
+OCH_API int och_gpu_render_lit_steps_dev(och_gpu_pool *pool, const och_camera *cams, int n_views,
+                                         const och_light *light, int n_steps, void *const *streams,
+                                         uint32_t *const *frames, int n_buffers, void *const *start_events,
+                                         void *const *stop_events, int row_chunk);
 /* Row deal: instead of round-robin, row chunk g of frames `height` rows tall
  * (chunks of row_chunk rows over n_shards) belongs to shard chunk_shard[g],
  * for ceil(height / row_chunk) chunks; each shard's chunks keep their order.
@@ -527,6 +562,15 @@ OCH_API int och_frame_group_synchronize(och_frame_group *group);
  * buffer set (n_steps - 1) % n_buffers: the last frame. */
 OCH_API int och_frame_group_render_steps(och_frame_group *group, const och_camera *cams, int n_views, int n_steps,
                                          int n_buffers, int row_chunk, int bounce);
+/* The two render calls with a light: lit frames, the words
+ * och_gpu_render_lit_views_dev writes.  Slices travel as 2-byte lit codes when
+ * the palette has at most OCH_CODE_MAX_VOXELS ids, as lit RGBA8 words
+ * otherwise.  A light och_light_check refuses is refused before anything is
+ * queued. */
+OCH_API int och_frame_group_render_lit(och_frame_group *group, const och_camera *cams, int n_views, int row_chunk,
+                                       const och_light *light);
+OCH_API int och_frame_group_render_lit_steps(och_frame_group *group, const och_camera *cams, int n_views, int n_steps,
+                                             int n_buffers, int row_chunk, const och_light *light);
 
 /* ------------------------------------------------------------ multi-GPU frames, one process per GPU */
 /* SURVEY §8(e) with one process per GPU (the driver's torch.distributed
@@ -581,6 +625,18 @@ OCH_API int och_gpu_render_sharded_steps_dev(och_gpu_pool *pool, och_comm *comm,
                                              uint8_t *const *gathered, uint32_t *const *frames, int n_buffers,
                                              void *const *start_events, void *const *stop_events, int row_chunk,
                                              int bounce, int exchange);
+/* The same window for lit frames: step 1 writes lit codes
+ * (och_gpu_render_lit_codes_views_dev; slices[b] holds 2 B per pixel), step 2
+ * moves 2 * n_views * rows * W bytes per rank in any of the three exchanges,
+ * step 3 is och_gpu_shade_lit_unshard_views_dev -- the frames
+ * och_gpu_render_lit_views_dev writes.  The light, the buffers, the palette
+ * and the code table are checked before the first frame is queued. */
+OCH_API int och_gpu_render_lit_sharded_steps_dev(och_gpu_pool *pool, och_comm *comm, const och_camera *cams,
+                                                 int n_views, int n_steps, void *const *streams,
+                                                 uint8_t *const *slices, uint8_t *const *gathered,
+                                                 uint32_t *const *frames, int n_buffers, void *const *start_events,
+                                                 void *const *stop_events, int row_chunk, const och_light *light,
+                                                 int exchange);
 
 /* ------------------------------------------------------------ builder */
 /* The demo terrain (ORT/test_och_h_octree.cpp:561-787) built in parallel

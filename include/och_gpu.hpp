@@ -144,6 +144,26 @@ public:
         check(och_gpu_render_lit_ssaa(pool_, &cam, &light, s, rgba, capacity_pixels), "och_gpu_render_lit_ssaa");
     }
 
+    // Lit codes, the lit frame's exchange format between GPUs (device buffers,
+    // asynchronous on the pool's stream): this shard's slices as one uint16 per
+    // pixel, code | mask << 8 (och_gpu_render_lit_codes_views_dev) ...
+    void render_lit_codes(const std::vector<och_camera> &cams, const och_light &light, uint16_t *code_slices,
+                          size_t capacity_pixels, int row_chunk, int shard = 0, int n_shards = 1) const
+    {
+        check(och_gpu_render_lit_codes_views_dev(pool_, cams.data(), static_cast<int>(cams.size()), &light, code_slices,
+                                                 capacity_pixels, row_chunk, shard, n_shards),
+              "och_gpu_render_lit_codes_views_dev");
+    }
+    // ... and every shard's gathered slices shaded into [views][H][W] RGBA8
+    // frames, the words render_lit writes (och_gpu_shade_lit_unshard_views_dev).
+    void shade_lit_unshard(const uint16_t *gathered, uint32_t *frames, int width, int height, int row_chunk,
+                           int n_shards, int n_views, const och_light &light) const
+    {
+        check(och_gpu_shade_lit_unshard_views_dev(pool_, gathered, frames, width, height, row_chunk, n_shards, n_views,
+                                                  &light),
+              "och_gpu_shade_lit_unshard_views_dev");
+    }
+
     och_gpu_pool *handle() const { return pool_; }
 
 private:
@@ -239,6 +259,20 @@ public:
         check(och_frame_group_render_steps(g_, cams.data(), static_cast<int>(cams.size()), n_steps, n_buffers,
                                            row_chunk, bounce ? 1 : 0),
               "och_frame_group_render_steps");
+    }
+    // The two render calls with a light: lit frames (tree::render_lit's words),
+    // exchanged as 2-byte lit codes when the palette fits the codes.
+    void render_lit(const std::vector<och_camera> &cams, const och_light &light, int row_chunk = 8)
+    {
+        check(och_frame_group_render_lit(g_, cams.data(), static_cast<int>(cams.size()), row_chunk, &light),
+              "och_frame_group_render_lit");
+    }
+    void render_lit_steps(const std::vector<och_camera> &cams, const och_light &light, int n_steps, int n_buffers = 3,
+                          int row_chunk = 8)
+    {
+        check(och_frame_group_render_lit_steps(g_, cams.data(), static_cast<int>(cams.size()), n_steps, n_buffers,
+                                               row_chunk, &light),
+              "och_frame_group_render_lit_steps");
     }
     uint32_t *frames(int rank) const
     {

@@ -121,6 +121,16 @@ PROTOTYPES = {
     "och_gpu_render_lit_masks_views_dev": (C.c_int, [_P, _P, C.c_int, C.POINTER(Light), _P, C.c_size_t, C.c_int,
                                                      C.c_int, C.c_int]),
     "och_gpu_render_lit": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Light), _P, C.c_size_t]),
+    "och_gpu_render_lit_codes_views_dev": (C.c_int, [_P, _P, C.c_int, C.POINTER(Light), _P, C.c_size_t, C.c_int,
+                                                     C.c_int, C.c_int]),
+    "och_gpu_shade_lit_unshard_views_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      C.POINTER(Light)]),
+    "och_gpu_render_lit_steps_dev": (C.c_int, [_P, _P, C.c_int, C.POINTER(Light), C.c_int, _P, _P, C.c_int, _P, _P,
+                                               C.c_int]),
+    "och_gpu_render_lit_sharded_steps_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P,
+                                                       C.c_int, C.POINTER(Light), C.c_int]),
+    "och_frame_group_render_lit": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(Light)]),
+    "och_frame_group_render_lit_steps": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Light)]),
     "och_gpu_render_lit_ssaa_views_dev": (C.c_int, [_P, _P, C.c_int, C.POINTER(Light), C.c_int, _P, C.c_size_t]),
     "och_gpu_render_lit_ssaa": (C.c_int, [_P, C.POINTER(Camera), C.POINTER(Light), C.c_int, _P, C.c_size_t]),
     "och_gpu_render_steps_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int]),

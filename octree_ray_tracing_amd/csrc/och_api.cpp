@@ -1886,13 +1886,18 @@ OCH_API int och_light_check(const och_light *l)
 
 namespace {
 
-// och_gpu_render_lit_views_dev / _lit_masks_views_dev: exactly one of rgba and masks.
+// och_gpu_render_lit_views_dev / _lit_masks_views_dev / _lit_codes_views_dev:
+// exactly one of rgba, masks and codes.
 int render_lit_views(och_gpu_pool *p, const och_camera *cams, int n_views, const och_light *light, uint32_t *rgba,
-                     uint8_t *masks, size_t capacity_pixels, int row_chunk, int shard, int n_shards)
+                     uint8_t *masks, size_t capacity_pixels, int row_chunk, int shard, int n_shards,
+                     uint16_t *codes = nullptr)
 {
     // every refusal comes before anything is written or launched
-    if (!p || !cams || !light || (!rgba && !masks)) return fail(OCH_E_INVALID, "NULL argument");
+    if (!p || !cams || !light || (!rgba && !masks && !codes)) return fail(OCH_E_INVALID, "NULL argument");
     if (int ls = och_light_check(light)) return ls;
+    if (codes && (p->n_voxels > OCH_CODE_MAX_VOXELS || !p->d_code_table.d))
+        return fail(OCH_E_INVALID, "lit codes need a palette (och_gpu_set_palette) of at most %d voxel ids",
+                    OCH_CODE_MAX_VOXELS);
     if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
     if (row_chunk <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards)
         return fail(OCH_E_INVALID, "bad sharding (%d, %d, %d)", row_chunk, shard, n_shards);
@@ -1910,7 +1915,10 @@ int render_lit_views(och_gpu_pool *p, const och_camera *cams, int n_views, const
     och::Schedule sc = timed_schedule(p, ts);
     if (ts) return ts;
     use_plan(p, f, false, false, sc);            // the primary render's plan of this grid, never its split form
-    OCH_HIP(och::launch_render_lit(p->dev(), f, sc, *light, masks, p->stream()));
+    if (codes)
+        OCH_HIP(och::launch_render_lit_codes(p->dev(), f, sc, *light, codes, p->stream()));
+    else
+        OCH_HIP(och::launch_render_lit(p->dev(), f, sc, *light, masks, p->stream()));
     return timed_done(p, sc, true);
 }
 
@@ -1934,6 +1942,34 @@ OCH_API int och_gpu_render_lit_masks_views_dev(och_gpu_pool *p, const och_camera
     OCH_ENTRY();
     if (!mask_slices) return fail(OCH_E_INVALID, "NULL argument");
     return render_lit_views(p, cams, n_views, light, nullptr, mask_slices, capacity_pixels, row_chunk, shard, n_shards);
+}
+
+OCH_API int och_gpu_render_lit_codes_views_dev(och_gpu_pool *p, const och_camera *cams, int n_views,
+                                               const och_light *light, uint16_t *code_slices, size_t capacity_pixels,
+                                               int row_chunk, int shard, int n_shards)
+{
+    OCH_ENTRY();
+    if (!code_slices) return fail(OCH_E_INVALID, "NULL argument");
+    return render_lit_views(p, cams, n_views, light, nullptr, nullptr, capacity_pixels, row_chunk, shard, n_shards,
+                            code_slices);
+}
+
+OCH_API int och_gpu_shade_lit_unshard_views_dev(och_gpu_pool *p, const uint16_t *gathered, uint32_t *frames, int width,
+                                                int height, int row_chunk, int n_shards, int n_views,
+                                                const och_light *light)
+{
+    OCH_ENTRY();
+    if (int ls = och_light_check(light)) return ls;
+    if (!p || !gathered || !frames || width <= 0 || height <= 0 || row_chunk <= 0 || n_shards <= 0 || n_views < 1)
+        return fail(OCH_E_INVALID, "bad unshard arguments");
+    if (!p->d_code_table.d)
+        return fail(OCH_E_INVALID, "no code table: set a palette of at most %d voxel ids", OCH_CODE_MAX_VOXELS);
+    DeviceGuard g(p->device);
+    OCH_HIP(och::launch_shade_lit_unshard(gathered, frames, p->d_code_table.d, width, height, row_chunk, n_shards,
+                                          p->slice_rows(height, row_chunk, n_shards), n_views,
+                                          p->deal_for(height, row_chunk, n_shards) ? p->d_owner.d : nullptr,
+                                          light->sun_shade, light->ao_shade, p->stream()));
+    return OCH_OK;
 }
 
 OCH_API int och_gpu_render_lit(och_gpu_pool *p, const och_camera *cam, const och_light *light, uint32_t *rgba,
@@ -2038,14 +2074,42 @@ OCH_API int och_gpu_render_steps_dev(och_gpu_pool *p, const och_camera *cams, in
     return st;
 }
 
+OCH_API int och_gpu_render_lit_steps_dev(och_gpu_pool *p, const och_camera *cams, int n_views, const och_light *light,
+                                         int n_steps, void *const *streams, uint32_t *const *frames, int n_buffers,
+                                         void *const *start_events, void *const *stop_events, int row_chunk)
+{
+    OCH_ENTRY();
+    if (!p || !cams || !light || !streams || !frames) return fail(OCH_E_INVALID, "NULL argument");
+    if (int ls = och_light_check(light)) return ls;
+    if (n_steps < 0 || n_buffers < 1) return fail(OCH_E_INVALID, "n_steps %d / n_buffers %d", n_steps, n_buffers);
+    if ((start_events == nullptr) != (stop_events == nullptr))
+        return fail(OCH_E_INVALID, "start_events and stop_events: both or neither");
+    for (int b = 0; b < n_buffers; ++b)
+        if (!frames[b]) return fail(OCH_E_INVALID, "frames[%d] is NULL", b);
+    if (int vs = och::check_views(cams, n_views)) return vs;
+    // och_gpu_render_steps_dev's loop, each frame a lit frame as one shard
+    const size_t pixels = (size_t)n_views * (size_t)cams[0].width * (size_t)cams[0].height;
+    FrameLoopScope loop{p};
+    int st = OCH_OK;
+    for (int k = 0; k < n_steps && st == OCH_OK; ++k) {
+        const int b = k % n_buffers;
+        loop.frame(streams[b], start_events, stop_events, k);
+        st = render_lit_views(p, cams, n_views, light, frames[b], nullptr, pixels, row_chunk, 0, 1);
+    }
+    return st;
+}
+
 }  // extern "C"
 
 int och::sharded_steps(och_gpu_pool *p, och_comm *comm, const och_camera *cams, int n_views, int n_steps,
                        void *const *streams, uint8_t *const *slices, uint8_t *const *gathered, uint32_t *const *frames,
                        int n_buffers, void *const *start_events, void *const *stop_events, int row_chunk, int bounce,
-                       int exchange, bool codes)
+                       int exchange, bool codes, const och_light *light)
 {
     if (!p || !comm || !cams || !streams || !slices) return fail(OCH_E_INVALID, "NULL argument");
+    if (light && bounce) return fail(OCH_E_INVALID, "lit and bounce together are out of scope");
+    if (light)
+        if (int ls = och_light_check(light)) return ls;
     if (n_steps < 0 || n_buffers < 1) return fail(OCH_E_INVALID, "n_steps %d / n_buffers %d", n_steps, n_buffers);
     if (n_views < 1 || n_views > OCH_MAX_VIEWS || row_chunk <= 0) return fail(OCH_E_INVALID, "bad views / row_chunk");
     if (exchange < OCH_EXCHANGE_ALL_GATHER || exchange > OCH_EXCHANGE_GATHER)
@@ -2067,8 +2131,13 @@ int och::sharded_steps(och_gpu_pool *p, och_comm *comm, const och_camera *cams, 
     if (int vs = check_views(cams, n_views)) return vs;
     if (codes && shades && !p->d_code_table.d)
         return fail(OCH_E_INVALID, "no code table: set a palette of at most %d voxel ids", OCH_CODE_MAX_VOXELS);
+    // lit codes: the rendering rank needs the palette too (render_lit_views would refuse mid-window)
+    if (codes && light && (p->n_voxels > OCH_CODE_MAX_VOXELS || !p->d_code_table.d))
+        return fail(OCH_E_INVALID, "lit codes need a palette (och_gpu_set_palette) of at most %d voxel ids",
+                    OCH_CODE_MAX_VOXELS);
     const int W = cams[0].width, H = cams[0].height;
-    const size_t bytes = (size_t)n_views * p->slice_rows(H, row_chunk, n_ranks) * W * (codes ? 1 : 4);
+    const size_t pixels = (size_t)n_views * p->slice_rows(H, row_chunk, n_ranks) * W;
+    const size_t bytes = pixels * (codes ? (light ? 2 : 1) : 4);
     DeviceGuard g(p->device);
     // Per frame: render -> exchange -> shade, all on the frame's stream, so
     // the three are ordered on the device and the host never waits.  A
@@ -2080,8 +2149,13 @@ int och::sharded_steps(och_gpu_pool *p, och_comm *comm, const och_camera *cams, 
         const int b = k % n_buffers;
         const hipStream_t s = static_cast<hipStream_t>(streams[b]);
         loop.frame(streams[b], start_events, stop_events, k);
-        st = render_views(p, cams, n_views, codes ? nullptr : reinterpret_cast<uint32_t *>(slices[b]), row_chunk, rank,
-                          n_ranks, bounce != 0, codes ? slices[b] : nullptr);
+        if (light)
+            st = render_lit_views(p, cams, n_views, light, codes ? nullptr : reinterpret_cast<uint32_t *>(slices[b]),
+                                  nullptr, pixels, row_chunk, rank, n_ranks,
+                                  codes ? reinterpret_cast<uint16_t *>(slices[b]) : nullptr);
+        else
+            st = render_views(p, cams, n_views, codes ? nullptr : reinterpret_cast<uint32_t *>(slices[b]), row_chunk,
+                              rank, n_ranks, bounce != 0, codes ? slices[b] : nullptr);
         if (st == OCH_OK) {
             st = exchange == OCH_EXCHANGE_GATHER
                      ? och::comm_gather(comm, slices[b], receives ? gathered[b] : nullptr, bytes, 0, s)
@@ -2089,9 +2163,11 @@ int och::sharded_steps(och_gpu_pool *p, och_comm *comm, const och_camera *cams, 
             issued = issued || st == OCH_OK;
         }
         if (st == OCH_OK && shades)
-            st = codes ? och_gpu_shade_unshard_views_dev(p, gathered[b], frames[b], W, H, row_chunk, n_ranks, n_views)
-                       : och_gpu_unshard_views_dev(p, reinterpret_cast<const uint32_t *>(gathered[b]), frames[b], W, H,
-                                                   row_chunk, n_ranks, n_views);
+            st = !codes ? och_gpu_unshard_views_dev(p, reinterpret_cast<const uint32_t *>(gathered[b]), frames[b], W, H,
+                                                    row_chunk, n_ranks, n_views)
+                 : light ? och_gpu_shade_lit_unshard_views_dev(p, reinterpret_cast<const uint16_t *>(gathered[b]),
+                                                               frames[b], W, H, row_chunk, n_ranks, n_views, light)
+                         : och_gpu_shade_unshard_views_dev(p, gathered[b], frames[b], W, H, row_chunk, n_ranks, n_views);
     }
     if (st != OCH_OK && issued) {
         // The peers' collectives of this window can no longer all complete.
@@ -2115,7 +2191,19 @@ OCH_API int och_gpu_render_sharded_steps_dev(och_gpu_pool *p, och_comm *comm, co
 {
     OCH_ENTRY();
     return och::sharded_steps(p, comm, cams, n_views, n_steps, streams, slices, gathered, frames, n_buffers, start_events,
-                              stop_events, row_chunk, bounce, exchange, true);
+                              stop_events, row_chunk, bounce, exchange, true, nullptr);
+}
+
+OCH_API int och_gpu_render_lit_sharded_steps_dev(och_gpu_pool *p, och_comm *comm, const och_camera *cams, int n_views,
+                                                 int n_steps, void *const *streams, uint8_t *const *slices,
+                                                 uint8_t *const *gathered, uint32_t *const *frames, int n_buffers,
+                                                 void *const *start_events, void *const *stop_events, int row_chunk,
+                                                 const och_light *light, int exchange)
+{
+    OCH_ENTRY();
+    if (!light) return fail(OCH_E_INVALID, "light is NULL");
+    return och::sharded_steps(p, comm, cams, n_views, n_steps, streams, slices, gathered, frames, n_buffers, start_events,
+                              stop_events, row_chunk, 0, exchange, true, light);
 }
 
 OCH_API int och_gpu_render_codes_views_dev(och_gpu_pool *p, const och_camera *cams, int n_views, uint8_t *code_slices,

@@ -7,7 +7,8 @@
 //     (och_shard_rows, or och_frame_group_plan's cost deal); each device
 //     renders its slice -- raygen, traversal and shading fused -- as 1-byte
 //     colour codes (or RGBA8 words for palettes of more than
-//     OCH_CODE_MAX_VOXELS ids);
+//     OCH_CODE_MAX_VOXELS ids); lit frames (och_frame_group_render_lit) as
+//     2-byte lit codes, or lit RGBA8 words for such palettes;
 //   * one RCCL all-gather over xGMI (ncclCommInitAll over the devices) gives
 //     every device all slices, and one kernel per device shades + unshards
 //     them into the [views][H][W] RGBA8 frames (olc::Pixel layout).
@@ -201,13 +202,17 @@ void abort_comms(och_frame_group *g)
     g->broken = true;
 }
 
+// light (optional): lit frames -- 2-byte lit codes when the palette fits, lit
+// RGBA8 slices and a plain unshard otherwise.
 int render_steps(och_frame_group *g, const och_camera *cams, int n_views, int n_steps, int n_sets, int row_chunk,
-                 int bounce)
+                 int bounce, const och_light *light = nullptr)
 {
     if (!g || !cams || n_views < 1 || n_views > OCH_MAX_VIEWS || row_chunk < 1 || n_steps < 0 || n_sets < 1 ||
         n_sets > kMaxSets)
         return fail(OCH_E_INVALID, "bad frame group render arguments");
     if (g->broken) return fail(OCH_E_HIP, "frame group unusable after a failed frame (communicators aborted)");
+    if (light)
+        if (int ls = och_light_check(light)) return ls;
     if (int vs = och::check_views(cams, n_views)) return vs;
     const int W = cams[0].width, H = cams[0].height;
     // Indexed colour when the palette allows it (a quarter of the RGBA8 bytes on xGMI).
@@ -215,7 +220,7 @@ int render_steps(och_frame_group *g, const och_camera *cams, int n_views, int n_
     int st = och::pool_palette_size(g->pools[0], &n_vox);
     if (st != OCH_OK) return st;
     const bool codes = n_vox <= OCH_CODE_MAX_VOXELS;
-    st = ensure_buffers(g, W, H, n_views, row_chunk, codes ? 1 : 4, n_sets);
+    st = ensure_buffers(g, W, H, n_views, row_chunk, codes ? (light ? 2 : 1) : 4, n_sets);
     if (st != OCH_OK) return st;
     if (n_steps == 0) return OCH_OK;
     // the shade of every device needs its code table (checked before any frame is queued)
@@ -239,7 +244,7 @@ int render_steps(och_frame_group *g, const och_camera *cams, int n_views, int n_
         }
         // one thread per communicator: no RCCL group call is needed
         return och::sharded_steps(g->pools[r], g->comms[r], cams, n_views, n_steps, streams, slices, gathered, frames,
-                                  n_sets, nullptr, nullptr, row_chunk, bounce, OCH_EXCHANGE_ALL_GATHER, codes);
+                                  n_sets, nullptr, nullptr, row_chunk, bounce, OCH_EXCHANGE_ALL_GATHER, codes, light);
     });
     if (st != OCH_OK) {
         abort_comms(g);                      // leaves the error text alone
@@ -406,6 +411,22 @@ OCH_API int och_frame_group_render_steps(och_frame_group *g, const och_camera *c
 {
     OCH_ENTRY();
     return render_steps(g, cams, n_views, n_steps, n_buffers, row_chunk, bounce);
+}
+
+OCH_API int och_frame_group_render_lit(och_frame_group *g, const och_camera *cams, int n_views, int row_chunk,
+                                       const och_light *light)
+{
+    OCH_ENTRY();
+    if (!light) return fail(OCH_E_INVALID, "light is NULL");
+    return render_steps(g, cams, n_views, 1, 1, row_chunk, 0, light);
+}
+
+OCH_API int och_frame_group_render_lit_steps(och_frame_group *g, const och_camera *cams, int n_views, int n_steps,
+                                             int n_buffers, int row_chunk, const och_light *light)
+{
+    OCH_ENTRY();
+    if (!light) return fail(OCH_E_INVALID, "light is NULL");
+    return render_steps(g, cams, n_views, n_steps, n_buffers, row_chunk, 0, light);
 }
 
 OCH_API int och_frame_group_frames_dev(och_frame_group *g, int rank, uint32_t **frames)

@@ -84,10 +84,14 @@ int check_views(const och_camera *cams, int n_views);
 // frame's stream.  codes: the slices travel as 1-byte colour codes and the
 // shade needs the pool's code table; otherwise as RGBA8 words (slices and
 // gathered then hold 4 bytes a pixel) and the frames are only unsharded.
+// light (optional, refused together with bounce): lit frames -- with codes the
+// slices travel as 2-byte lit codes (och_gpu_render_lit_codes_views_dev) and
+// the shade is och_gpu_shade_lit_unshard_views_dev, otherwise as lit RGBA8
+// words.  It is checked, like the buffers, before the first frame is queued.
 int sharded_steps(och_gpu_pool *pool, och_comm *comm, const och_camera *cams, int n_views, int n_steps,
                   void *const *streams, uint8_t *const *slices, uint8_t *const *gathered, uint32_t *const *frames,
                   int n_buffers, void *const *start_events, void *const *stop_events, int row_chunk, int bounce,
-                  int exchange, bool codes);
+                  int exchange, bool codes, const och_light *light = nullptr);
 
 // An och_comm around an RCCL communicator the caller made (och_comm.cpp).
 och_comm *comm_adopt(ncclComm_t comm, int n_ranks, int rank, int device);

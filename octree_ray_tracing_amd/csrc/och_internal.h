@@ -203,6 +203,16 @@ hipError_t launch_render_ssaa(const DevPool &p, const DevFrame &f, const Schedul
 // when it is an unsplit permutation of this grid.
 hipError_t launch_render_lit(const DevPool &p, const DevFrame &f, const Schedule &sc, const och_light &light,
                              uint8_t *masks, hipStream_t stream);
+// Lit codes (k_trace_lit with LitCodeSink): launch_render_lit's pixels as one
+// uint16 each, pixel_code | mask << 8, laid out as the mask slices.
+hipError_t launch_render_lit_codes(const DevPool &p, const DevFrame &f, const Schedule &sc, const och_light &light,
+                                   uint16_t *codes, hipStream_t stream);
+// Gathered lit codes -> RGBA8 frames: table[code] shaded by the mask with the
+// light's two weights (k_shade_lit_unshard, the 4-pixel form when width % 4 == 0,
+// gathered is 8-byte and frames 16-byte aligned).  owner as for launch_shade_unshard.
+hipError_t launch_shade_lit_unshard(const uint16_t *gathered, uint32_t *frames, const uint32_t *table, int width,
+                                    int height, int row_chunk, int n_shards, int slice_rows, int n_views,
+                                    const int32_t *owner, int sun_shade, int ao_shade, hipStream_t stream);
 // Supersampled lit frames (k_trace_lit_ssaa): launch_render_ssaa's sample grid
 // and output, every sample launch_render_lit's frame colour under light.  One
 // shard's whole frame, width and height multiples of s, block <= 1024;

@@ -1482,6 +1482,21 @@ struct LitMaskSink {
     }
 };
 
+// Lit codes (the lit frame's exchange format, 2 B per pixel):
+// pixel_code of the primary record in the low byte, the pixel's mask byte --
+// LitMaskSink's -- in the high byte.  k_shade_lit_unshard turns them into the
+// words LitFrameSink stores.
+struct LitCodeSink {
+    uint16_t *out;
+    uint32_t n_voxels;
+    __device__ __forceinline__ uint32_t payload(const Hit &h) const { return pixel_code(h, n_voxels); }
+    __device__ __forceinline__ void put_plain(uint32_t i, uint32_t c) const { out[i] = (uint16_t)(c | (0x80u << 8)); }
+    __device__ __forceinline__ void put_lit(uint32_t i, uint32_t c, uint32_t mask, const och_light &) const
+    {
+        out[i] = (uint16_t)(c | (mask << 8));
+    }
+};
+
 // Words per thread of k_trace_lit's pixel queue: the secondary origin (3), the
 // output index, the payload, and the state word (hit direction | mask << 8).
 constexpr uint32_t kLitQueueWords = 6;
@@ -1784,6 +1799,59 @@ __global__ __launch_bounds__(256) void k_shade_unshard4(const uint8_t *__restric
     const uint32_t c = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>(gathered + src));
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const u32x4 px = {lut[c & 0xFFu], lut[(c >> 8) & 0xFFu], lut[(c >> 16) & 0xFFu], lut[c >> 24]};
+    __builtin_nontemporal_store(px, reinterpret_cast<u32x4 *>(frames + ((size_t)view * height + row) * width + col));
+}
+
+// Gathered lit codes [n_shards][n_views][slice_rows][width] (code | mask << 8,
+// LitCodeSink) -> RGBA8 frames [n_views][height][width]: the code table's word
+// shaded by the pixel's mask, lit_shade with the light's two weights.  A mask
+// of 0x80 (not a face hit) has weight 256, the identity, so one formula serves
+// every pixel.
+__device__ __forceinline__ uint32_t lit_code_word(const uint32_t *lut, uint32_t code16, int sun_shade, int ao_shade)
+{
+    och_light L;
+    L.sun_shade = sun_shade;
+    L.ao_shade = ao_shade;
+    return lit_shade(lut[code16 & 0xFFu], (code16 >> 8) & 0xFFu, L);
+}
+
+__global__ __launch_bounds__(256) void k_shade_lit_unshard(const uint16_t *__restrict__ gathered,
+                                                           uint32_t *__restrict__ frames,
+                                                           const uint32_t *__restrict__ table, int width, int height,
+                                                           int row_chunk, int n_shards, int slice_rows, int n_views,
+                                                           const int32_t *__restrict__ owner, int sun_shade, int ao_shade)
+{
+    __shared__ uint32_t lut[256];
+    lut[threadIdx.x] = table[threadIdx.x];
+    __syncthreads();
+    const int col = blockIdx.x * 256 + threadIdx.x;
+    const int row = blockIdx.y, view = blockIdx.z;
+    if (col >= width || row >= height) return;
+    const size_t src = gathered_row(row, row_chunk, n_shards, slice_rows, n_views, view, owner) * width + col;
+    frames[((size_t)view * height + row) * width + col] = lit_code_word(lut, gathered[src], sun_shade, ao_shade);
+}
+
+// The same for width % 4 == 0: four pixels per thread, one 8-B load of their
+// lit codes and one 16-B store (6 B of HBM traffic per pixel).
+__global__ __launch_bounds__(256) void k_shade_lit_unshard4(const uint16_t *__restrict__ gathered,
+                                                            uint32_t *__restrict__ frames,
+                                                            const uint32_t *__restrict__ table, int width, int height,
+                                                            int row_chunk, int n_shards, int slice_rows, int n_views,
+                                                            const int32_t *__restrict__ owner, int sun_shade, int ao_shade)
+{
+    __shared__ uint32_t lut[256];
+    lut[threadIdx.x] = table[threadIdx.x];
+    __syncthreads();
+    const int col = (blockIdx.x * 256 + threadIdx.x) * 4;
+    const int row = blockIdx.y, view = blockIdx.z;
+    if (col >= width || row >= height) return;
+    const size_t src = gathered_row(row, row_chunk, n_shards, slice_rows, n_views, view, owner) * width + col;
+    // streaming accesses, as in k_shade_unshard4
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const u32x2 c = __builtin_nontemporal_load(reinterpret_cast<const u32x2 *>(gathered + src));
+    const u32x4 px = {lit_code_word(lut, c.x & 0xFFFFu, sun_shade, ao_shade), lit_code_word(lut, c.x >> 16, sun_shade, ao_shade),
+                      lit_code_word(lut, c.y & 0xFFFFu, sun_shade, ao_shade), lit_code_word(lut, c.y >> 16, sun_shade, ao_shade)};
     __builtin_nontemporal_store(px, reinterpret_cast<u32x4 *>(frames + ((size_t)view * height + row) * width + col));
 }
 
@@ -2120,6 +2188,15 @@ hipError_t launch_render_lit(const DevPool &p, const DevFrame &f, const Schedule
     return launch_lit(p, src, LitFrameSink{FrameSink{f.out, f.palette, f.n_voxels}}, light, sc, stream);
 }
 
+hipError_t launch_render_lit_codes(const DevPool &p, const DevFrame &f, const Schedule &sc, const och_light &light,
+                                   uint16_t *codes, hipStream_t stream)
+{
+    if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
+    if ((uint32_t)sc.block > 1024u) return hipErrorInvalidValue;          // wave_count holds 16 waves
+    const CameraSource src = camera_source(p, f, sc);
+    return launch_lit(p, src, LitCodeSink{codes, f.n_voxels}, light, sc, stream);
+}
+
 hipError_t launch_render_codes(const DevPool &p, const DevFrame &f, const Schedule &sc, bool bounce, hipStream_t stream)
 {
     if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
@@ -2146,6 +2223,25 @@ hipError_t launch_shade_unshard(const uint8_t *gathered, uint32_t *frames, const
     clear_pending_error(__func__);
     hipLaunchKernelGGL(k_shade_unshard, grid, dim3(256), 0, stream, gathered, frames, table, width, height, row_chunk,
                        n_shards, slice_rows, n_views, owner);
+    return hipGetLastError();
+}
+
+hipError_t launch_shade_lit_unshard(const uint16_t *gathered, uint32_t *frames, const uint32_t *table, int width,
+                                    int height, int row_chunk, int n_shards, int slice_rows, int n_views,
+                                    const int32_t *owner, int sun_shade, int ao_shade, hipStream_t stream)
+{
+    const bool vec4 = width % 4 == 0 && ((uintptr_t)gathered & 7u) == 0 && ((uintptr_t)frames & 15u) == 0;
+    if (vec4) {
+        const dim3 grid((width / 4 + 255) / 256, height, n_views);
+        clear_pending_error(__func__);
+        hipLaunchKernelGGL(k_shade_lit_unshard4, grid, dim3(256), 0, stream, gathered, frames, table, width, height,
+                           row_chunk, n_shards, slice_rows, n_views, owner, sun_shade, ao_shade);
+        return hipGetLastError();
+    }
+    const dim3 grid((width + 255) / 256, height, n_views);
+    clear_pending_error(__func__);
+    hipLaunchKernelGGL(k_shade_lit_unshard, grid, dim3(256), 0, stream, gathered, frames, table, width, height, row_chunk,
+                       n_shards, slice_rows, n_views, owner, sun_shade, ao_shade);
     return hipGetLastError();
 }
 

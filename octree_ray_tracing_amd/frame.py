@@ -92,6 +92,38 @@ def shade_lit(frame: np.ndarray, masks: np.ndarray, light) -> np.ndarray:
     return out
 
 
+# include/och_gpu.h OCH_CODE_*: the fixed colours' codes and trace_pixel's colours for them
+CODE_MAGENTA, CODE_INSIDE, CODE_SKY, CODE_BLOCKED = 125, 126, 127, 128
+CODE_COLOURS = {CODE_MAGENTA: 0xFFFF00FF, CODE_INSIDE: 0xFF07193F, CODE_SKY: 0xFFFEBF00}
+
+
+def code_table(palette) -> np.ndarray:
+    """The 256-word code table on the host: the palette's words at their indices
+    6 * (voxel - 1) + direction, the fixed colours at OCH_CODE_MAGENTA / _INSIDE /
+    _SKY, and at code | OCH_CODE_BLOCKED the word with R, G, B halved (config 5's
+    blocked secondary ray); magenta elsewhere."""
+    pal = np.ascontiguousarray(palette, np.uint32).reshape(-1)
+    if pal.size % 6 or pal.size > 120:
+        raise ValueError("a code table holds at most 20 voxel ids, 6 colours each")
+    t = np.full(256, CODE_COLOURS[CODE_MAGENTA], np.uint32)
+    t[:pal.size] = pal
+    for c, w in CODE_COLOURS.items():
+        t[c] = w
+    t[128:] = ((t[:128] >> np.uint32(1)) & np.uint32(0x007F7F7F)) | (t[:128] & np.uint32(0xFF000000))
+    return t
+
+
+def shade_lit_codes(codes16: np.ndarray, palette, light) -> np.ndarray:
+    """The lit codes' definition on the host (och_gpu_shade_lit_unshard_views_dev
+    without the unshard): 2-byte lit codes, code | mask << 8, -> the lit RGBA8
+    words shade_lit(code_table(palette)[code], mask, light)."""
+    c = np.ascontiguousarray(codes16)
+    if c.dtype.itemsize != 2:
+        raise ValueError("lit codes are 2-byte elements")
+    c = c.view(np.uint16)                                  # int16 (torch's 16-bit type) holds the same bits
+    return shade_lit(code_table(palette)[c & np.uint16(0xFF)], (c >> np.uint16(8)).astype(np.uint8), light)
+
+
 class RcclComm:
     """The library's own RCCL communicator (och_comm_*): one rank per process
     and GPU, as the driver's torch.distributed launch runs them.  Rank 0 makes
@@ -206,10 +238,14 @@ class ShardedFrame:
     def __init__(self, pool: GpuPool, width: int, height: int, row_chunk: int = 8, n_views: int = 1, group=None,
                  indexed: bool = False, shard: tuple[int, int] | None = None, shade: str = "all",
                  direct: bool = False, deal=None, shade_stream=None, comm: RcclComm | None = None,
-                 sharded: bool = False, exchange: str = "all_gather"):
+                 sharded: bool = False, exchange: str = "all_gather", light=None):
         import torch
         import torch.distributed as dist
 
+        # light: lit frames (GpuPool.render_lit_views_dev's words).  With indexed=True the slices are
+        # 2-byte lit codes (int16: code | mask << 8) and the shade is shade_lit_unshard_dev;
+        # otherwise lit RGBA8 slices.  Not with bounce.
+        self.light = light
         self.pool, self.width, self.height, self.row_chunk = pool, width, height, row_chunk
         self.n_views, self.group = n_views, group
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -253,7 +289,7 @@ class ShardedFrame:
         self.sharded = bool(sharded) or self.world > 1
         self.direct = bool(direct) and self.world == 1 and not self.proxy and not self.sharded
         dev = torch.device("cuda", torch.cuda.current_device())
-        dt = torch.uint8 if indexed else torch.int32
+        dt = (torch.int16 if light is not None else torch.uint8) if indexed else torch.int32
         self.slice = torch.empty((n_views, self.rows, width), dtype=dt, device=dev)
         self.gathered = torch.empty((self.world, n_views, self.rows, width), dtype=dt, device=dev)
         self.frames = torch.empty((n_views, height, width), dtype=torch.int32, device=dev)
@@ -271,9 +307,18 @@ class ShardedFrame:
     def render_local(self, cams, bounce: bool = False):
         """This rank's rows of every view; bounce=True renders config 5 (one
         mirrored secondary ray per hit pixel)."""
+        if bounce and self.light is not None:
+            raise ValueError("lit and bounce together are out of scope")
         if not isinstance(cams, (list, tuple)):
             cams = [cams]
         assert len(cams) == self.n_views
+        if self.light is not None:
+            if self.direct:
+                self.pool.render_lit_views_dev(list(cams), self.light, self.frames, None, self.row_chunk, 0, 1)
+                return self.frames
+            render = self.pool.render_lit_codes_views_dev if self.indexed else self.pool.render_lit_views_dev
+            render(list(cams), self.light, self.slice, None, self.row_chunk, self.rank, self.world)
+            return self.slice
         if self.direct:
             render = self.pool.render_bounce_views_dev if bounce else self.pool.render_views_dev
             render(list(cams), self.frames, self.row_chunk, 0, 1)
@@ -307,12 +352,15 @@ class ShardedFrame:
                 self.comm.all_gather(self.slice, self.gathered, cur)
             src = self.gathered
         elif self.sharded and (self.world > 1 or dist.is_initialized()):
+            send, recv = self.slice, self.gathered
+            if send.dtype == torch.int16:                   # lit codes travel as bytes: no 16-bit type in the collectives
+                send, recv = send.view(torch.uint8), recv.view(torch.uint8)
             if dist.get_backend(self.group) == "gloo":      # host-staged (CPU tests, rehearsal runs)
-                host = self.gathered.new_empty(self.gathered.shape, device="cpu")
-                dist.all_gather(list(host.unbind(0)), self.slice.cpu(), group=self.group)
-                self.gathered.copy_(host)
+                host = recv.new_empty(recv.shape, device="cpu")
+                dist.all_gather(list(host.unbind(0)), send.cpu(), group=self.group)
+                recv.copy_(host)
             else:
-                dist.all_gather_into_tensor(self.gathered, self.slice, group=self.group)
+                dist.all_gather_into_tensor(recv, send, group=self.group)
             src = self.gathered
         if self.shade == "display" and self.rank != 0:
             return None
@@ -354,7 +402,10 @@ class ShardedFrame:
         return self.frames
 
     def _shade(self, src):
-        if self.indexed:
+        if self.indexed and self.light is not None:
+            self.pool.shade_lit_unshard_dev(src, self.frames, self.width, self.height, self.row_chunk, self.world,
+                                            self.light, self.n_views)
+        elif self.indexed:
             self.pool.shade_unshard_dev(src, self.frames, self.width, self.height, self.row_chunk, self.world,
                                         self.n_views)
         else:
@@ -414,19 +465,35 @@ class FrameGroup:
         arr = (Camera * len(cams))(*cams)
         call("och_frame_group_plan", self._h, C.cast(arr, C.c_void_p), len(cams), int(row_chunk))
 
-    def render(self, cams, row_chunk: int = 8, bounce: bool = False):
+    def render(self, cams, row_chunk: int = 8, bounce: bool = False, light=None):
+        """One frame on every device; light: a lit frame (och_frame_group_render_lit), not with bounce."""
+        if bounce and light is not None:
+            raise ValueError("lit and bounce together are out of scope")
         cams = list(cams) if isinstance(cams, (list, tuple)) else [cams]
         arr = (Camera * len(cams))(*cams)
-        call("och_frame_group_render", self._h, C.cast(arr, C.c_void_p), len(cams), int(row_chunk), int(bool(bounce)))
+        if light is not None:
+            call("och_frame_group_render_lit", self._h, C.cast(arr, C.c_void_p), len(cams), int(row_chunk),
+                 C.byref(light))
+        else:
+            call("och_frame_group_render", self._h, C.cast(arr, C.c_void_p), len(cams), int(row_chunk),
+                 int(bool(bounce)))
         self._shape = (len(cams), cams[0].height, cams[0].width)
 
-    def render_steps(self, cams, n_steps: int, n_buffers: int = 3, row_chunk: int = 8, bounce: bool = False):
+    def render_steps(self, cams, n_steps: int, n_buffers: int = 3, row_chunk: int = 8, bounce: bool = False,
+                     light=None):
         """n_steps frames issued by the devices' own threads, up to n_buffers
-        in flight (och_frame_group_render_steps); download() gives the last."""
+        in flight (och_frame_group_render_steps, or _render_lit_steps with a
+        light); download() gives the last."""
+        if bounce and light is not None:
+            raise ValueError("lit and bounce together are out of scope")
         cams = list(cams) if isinstance(cams, (list, tuple)) else [cams]
         arr = (Camera * len(cams))(*cams)
-        call("och_frame_group_render_steps", self._h, C.cast(arr, C.c_void_p), len(cams), int(n_steps),
-             int(n_buffers), int(row_chunk), int(bool(bounce)))
+        if light is not None:
+            call("och_frame_group_render_lit_steps", self._h, C.cast(arr, C.c_void_p), len(cams), int(n_steps),
+                 int(n_buffers), int(row_chunk), C.byref(light))
+        else:
+            call("och_frame_group_render_steps", self._h, C.cast(arr, C.c_void_p), len(cams), int(n_steps),
+                 int(n_buffers), int(row_chunk), int(bool(bounce)))
         self._shape = (len(cams), cams[0].height, cams[0].width)
 
     def synchronize(self):
@@ -453,6 +520,12 @@ class ShardedSteps:
         f0 = frames[0]
         if len(frames) != len(streams) or not all(f.comm is comm and f.indexed and not f.direct for f in frames):
             raise ValueError("one indexed, sharded ShardedFrame per stream, all on this comm")
+        # frames made with a light: the lit window (och_gpu_render_lit_sharded_steps_dev), lit codes
+        self.light = getattr(f0, "light", None)
+        if any(getattr(f, "light", None) is not self.light for f in frames):
+            raise ValueError("the frames of one window share one light (or none)")
+        if self.light is not None and bounce:
+            raise ValueError("lit and bounce together are out of scope")
         self.lib = load()
         self.pool = f0.pool
         self.frames, self.streams, self.comm = list(frames), list(streams), comm
@@ -480,14 +553,15 @@ class ShardedSteps:
 
     def prepare(self, n_steps: int, start_events=None, stop_events=None):
         """The window's call with its arguments built now; returns issue()."""
-        fn = self.lib.och_gpu_render_sharded_steps_dev
+        lit = self.light is not None
+        fn = self.lib.och_gpu_render_lit_sharded_steps_dev if lit else self.lib.och_gpu_render_sharded_steps_dev
         e0 = e1 = None
         if start_events is not None:
             e0 = (C.c_void_p * n_steps)(*start_events)
             e1 = (C.c_void_p * n_steps)(*stop_events)
         args = (self.pool._h, self.comm.handle, C.cast(self.cams, C.c_void_p), self.n_views, int(n_steps),
                 self._streams, self._slices, self._gathered, self._frames, len(self.frames), e0, e1,
-                self.row_chunk, self.bounce, self.exchange)
+                self.row_chunk, C.byref(self.light) if lit else self.bounce, self.exchange)
 
         def issue():
             if fn(*args):

@@ -384,6 +384,54 @@ class GpuPool:
         self._lit_views("och_gpu_render_lit_masks_views_dev", cams, light, mask_slices, 1, capacity_pixels, row_chunk,
                         shard, n_shards)
 
+    # Lit codes (include/och_gpu.h): the lit frame's exchange format, one int16
+    # per pixel = OCH_CODE_* byte | mask byte << 8; shade_lit_unshard_dev yields
+    # the RGBA8 frames render_lit_views_dev writes (frame.shade_lit_codes on the host).
+    @staticmethod
+    def _need_lit_codes(buf, what):
+        if hasattr(buf, "element_size") and buf.element_size() != 2:
+            raise ValueError(f"{what}: lit codes are 2-byte elements (int16), not {buf.element_size()}-byte ones")
+
+    def render_lit_codes_views_dev(self, cams, light: Light, code_slices, capacity_pixels: int | None = None,
+                                   row_chunk: int | None = None, shard: int = 0, n_shards: int = 1):
+        """render_codes_views_dev's slices, lit (och_gpu_render_lit_codes_views_dev): code_slices is a device
+        tensor of int16, or a raw pointer with capacity_pixels.  Asynchronous on the pool's stream."""
+        self._need_lit_codes(code_slices, "code_slices")
+        self._lit_views("och_gpu_render_lit_codes_views_dev", cams, light, code_slices, 2, capacity_pixels, row_chunk,
+                        shard, n_shards)
+
+    def shade_lit_unshard_dev(self, gathered_codes, frames, width: int, height: int, row_chunk: int, n_shards: int,
+                              light: Light, n_views: int = 1):
+        """Gathered lit codes [n_shards][n_views][rows][W] -> RGBA8 frames [n_views][H][W] under light's
+        two weights (och_gpu_shade_lit_unshard_views_dev)."""
+        self._need_lit_codes(gathered_codes, "gathered_codes")
+        rows = self.slice_rows(height, row_chunk, n_shards)
+        _need(gathered_codes, 2 * n_shards * n_views * rows * width, "gathered_codes")
+        _need(frames, 4 * n_views * height * width, "frames")
+        call("och_gpu_shade_lit_unshard_views_dev", self._h, _dev_ptr(gathered_codes), _dev_ptr(frames), int(width),
+             int(height), int(row_chunk), int(n_shards), int(n_views), C.byref(light))
+
+    def render_lit_steps_dev(self, cams, light: Light, frames, streams, n_steps: int, events=None,
+                             row_chunk: int | None = None):
+        """render_steps_dev with every frame a lit frame (och_gpu_render_lit_steps_dev)."""
+        if len(frames) != len(streams) or not frames:
+            raise ValueError("one stream per frame buffer")
+        arr = (Camera * len(cams))(*cams)
+        if row_chunk is None:
+            row_chunk = cams[0].height
+        sp = (C.c_void_p * len(streams))(*[getattr(s_, "cuda_stream", s_) for s_ in streams])
+        for f in frames:
+            self._need_frames(f, list(cams), row_chunk, 0, 1, 4, "frames")
+        fp = (C.c_void_p * len(frames))(*[_dev_ptr(f) for f in frames])
+        e0 = e1 = None
+        if events is not None:
+            if len(events) != n_steps:
+                raise ValueError("one event pair per step")
+            e0 = (C.c_void_p * n_steps)(*[_event_handle(a) for a, _ in events])
+            e1 = (C.c_void_p * n_steps)(*[_event_handle(b) for _, b in events])
+        call("och_gpu_render_lit_steps_dev", self._h, C.cast(arr, C.c_void_p), len(cams), C.byref(light), int(n_steps),
+             sp, fp, len(frames), e0, e1, int(row_chunk))
+
     def render_lit_ssaa(self, cam: Camera, light: Light, s: int) -> np.ndarray:
         """The lit frame of `cam` (the sample grid's camera, as for render_ssaa) supersampled s x s:
         (H / s, W / s) uint32, every sample shaded as render_lit shades it, then the rounded mean

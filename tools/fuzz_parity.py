@@ -26,6 +26,11 @@ corners and edges); then one launch path with random options:
   lit_ssaa  supersampled lit frames (och_gpu_render_lit_ssaa_views_dev), s = 2, 4, 8: the lit path's
             lights and options, the expected frame the box mean of the oracle's lit sample grid;
             only with --paths
+  lit_codes lit frames across shards on one device: 1-8 shards under round-robin and weighted row
+            deals, every shard's 2-byte lit codes (och_gpu_render_lit_codes_views_dev) laid out as an
+            all-gather lays them, then och_gpu_shade_lit_unshard_views_dev; only with --paths
+  lit_sharded_steps  the lit window at world size 1 (och_gpu_render_lit_sharded_steps_dev), the three
+            exchange modes, several frames over B streams; only with --paths
   image     och_gpu_trace_batch_image (host rays, x + y * W, 8x8 tiles)
   editor    h_octree::set edits flushed to the device pool in 1-3 windows
   steps     the N = 1 frame loop issued by the library (och_gpu_render_steps_dev)
@@ -348,6 +353,93 @@ def lit_ssaa_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, scene, o
     return miss, nv * Ws * Hs, hits
 
 
+def lit_expected(O, ref_pool, pal, depth, views, W, H, lit):
+    """The oracle's lit frames of these views ([view][H * W]) and their face hits (lit_case's comparison)."""
+    from test_gpu_lit import Expected, shade
+    light, sun, reach, sun_shade, ao_shade, flags = lit
+    want, hits = [], 0
+    for pos, fov, y, p in views:
+        e = Expected(O, ref_pool, pal, depth, pos, y, p, W, H, sun=sun, check_origins=False, fov=fov)
+        want.append(shade(e.plain.reshape(H, W), e.masks(flags, sun, reach), sun_shade, ao_shade).reshape(-1))
+        hits += len(e.hit)
+    return np.stack(want), hits
+
+
+def lit_codes_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, scene, o, d):
+    """codes_case for lit frames: every shard's lit codes on one device, concatenated as an
+    all-gather would lay them, shaded and unsharded by och_gpu_shade_lit_unshard_views_dev."""
+    W, H, nv = int(rng.integers(1, 193)), int(rng.integers(1, 121)), int(rng.integers(1, 4))
+    n, rc = int(rng.integers(1, 9)), int(rng.choice([1, 2, 5, 8, 16]))
+    views, cams = random_views(rng, ort, depth, W, H, nv)
+    pal = rng.integers(0, 2 ** 32, 6 * int(rng.integers(1, 21)), dtype=np.uint64).astype(np.uint32)
+    pool.set_palette(pal)
+    lit = random_light(rng, ort, depth)
+    chunks = -(-H // rc)
+    dealt = bool(rng.random() < 0.5)
+    pool.set_row_deal(H, rc, n, ort.deal_chunks(rng.uniform(0.1, 2.0, chunks), n, rng.uniform(0.3, 1.0, n)) if dealt else None)
+    compact = int(rng.integers(0, 3))
+    pool.set_option("bounce_compact", compact)
+    plan = bool(rng.random() < 0.4)
+    pool.set_option("tile_order", 2 if plan else int(rng.integers(0, 2)))
+    opts.update({"W": W, "H": H, "views": nv, "n_shards": n, "row_chunk": rc, "dealt": dealt, "plan": plan,
+                 "bounce_compact": compact, "flags": lit[5], "sun": lit[1]})
+    rows = pool.slice_rows(H, rc, n)
+    gathered = torch.full((n, nv, rows, W), 0x5A5A, dtype=torch.int16, device=dev)
+    pool.set_stream(torch.cuda.current_stream())
+    for s_ in range(n):
+        if plan:                                   # each shard's own plan, as each rank makes it
+            pool.plan_views(cams, rc, s_, n)
+        pool.render_lit_codes_views_dev(cams, lit[0], gathered[s_], None, rc, s_, n)
+    full = torch.full((nv, H, W), 7, dtype=torch.int32, device=dev)
+    pool.shade_lit_unshard_dev(gathered, full, W, H, rc, n, lit[0], nv)
+    torch.cuda.synchronize()
+    got = full.cpu().numpy().view(np.uint32).reshape(nv, H * W)
+    want, hits = lit_expected(O, ref_pool, pal, depth, views, W, H, lit)
+    return int((got != want).sum()), nv * W * H, hits
+
+
+def lit_sharded_steps_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, scene, o, d):
+    """sharded_steps_case for lit frames (och_gpu_render_lit_sharded_steps_dev at world size 1):
+    lit codes, the exchange in one of its three modes, the lit shade; n frames over B buffer sets."""
+    from octree_ray_tracing_amd.frame import ShardedFrame, ShardedSteps
+    if not COMM:
+        COMM.append(ort.RcclComm.local(0))
+    comm = COMM[0]
+    W, H, nv = int(rng.integers(1, 193)), int(rng.integers(1, 121)), int(rng.integers(1, 4))
+    rc, B, n = int(rng.choice([1, 2, 5, 8, 16])), int(rng.integers(1, 4)), int(rng.integers(1, 6))
+    exchange = str(rng.choice(["all_gather", "display", "gather"]))
+    views, cams = random_views(rng, ort, depth, W, H, nv)
+    pal = rng.integers(0, 2 ** 32, 6 * int(rng.integers(1, 21)), dtype=np.uint64).astype(np.uint32)
+    pool.set_palette(pal)
+    lit = random_light(rng, ort, depth)
+    compact = int(rng.integers(0, 3))
+    pool.set_option("bounce_compact", compact)
+    plan = bool(rng.random() < 0.5)
+    pool.set_option("tile_order", 2 if plan else 0)
+    if plan:
+        pool.plan_views(cams, rc, 0, 1)
+    opts.update({"W": W, "H": H, "views": nv, "row_chunk": rc, "buffers": B, "steps": n, "exchange": exchange,
+                 "plan": plan, "bounce_compact": compact, "flags": lit[5], "sun": lit[1]})
+    streams = [torch.cuda.current_stream()] + [torch.cuda.Stream(device=dev) for _ in range(B - 1)]
+    shade = "all" if exchange == "all_gather" else "display"
+    mode = "gather" if exchange == "gather" else "all_gather"
+    sfs = []
+    for s_ in streams:
+        with torch.cuda.stream(s_):
+            sfs.append(ShardedFrame(pool, W, H, rc, n_views=nv, indexed=True, shade=shade, comm=comm,
+                                    sharded=True, exchange=mode, light=lit[0]))
+    for f in sfs:
+        f.frames.fill_(7)
+    ShardedSteps(sfs, streams, comm, cams).run(n)
+    torch.cuda.synchronize()
+    want, hits = lit_expected(O, ref_pool, pal, depth, views, W, H, lit)
+    miss = 0
+    for b in range(min(B, n)):
+        miss += int((sfs[b].frames.cpu().numpy().view(np.uint32).reshape(nv, H * W) != want).sum())
+    pool.set_stream(torch.cuda.current_stream())
+    return miss, n * nv * W * H, hits
+
+
 FORCE_SPLIT = [False]
 
 
@@ -513,7 +605,7 @@ def editor_case(rng, ort, O, torch, dev, pool, ref_pool, depth, opts, scene, o, 
 
 
 CASES = {"render": render_case, "codes": codes_case, "bounce_frames": bounce_frames_case, "lit": lit_case, "lit_ssaa": lit_ssaa_case,
-         "image": image_case,
+         "lit_codes": lit_codes_case, "lit_sharded_steps": lit_sharded_steps_case, "image": image_case,
          "editor": editor_case, "steps": steps_case, "sharded_steps": sharded_steps_case}
 
 
