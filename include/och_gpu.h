@@ -671,6 +671,35 @@ typedef struct och_host_pool {
 
 OCH_API int och_build_terrain(const och_terrain_params *params, och_host_pool *out);
 OCH_API void och_host_pool_free(och_host_pool *pool);
+
+/* A DAG from the caller's voxels, in the form och_build_terrain(dedup = 1)
+ * returns: 1-based, root 1 (root 0 and one zero node for a world without
+ * voxels), breadth-first in first-occurrence order, no empty node.  That form
+ * depends on the content alone: the GPU and the host path, every record order
+ * and both input kinds give the same pool, slot for slot.
+ * A list's records act as successive h_octree::set calls: a later record for a
+ * coordinate replaces an earlier one, id 0 removes the voxel, a coordinate
+ * outside [0, dim) is ignored.  Ids are any uint32.
+ * solid_voxels = the distinct non-zero voxels, voxel_hist[k] those of id k
+ * (k = 1..7; [0] stays 0), tree_nodes = the expanded tree's nodes.
+ * OCH_E_INVALID: depth outside 1..21, a grid deeper than 10 (u8) / 9 (u32), a
+ * list of 2^31 records or more, device data without use_gpu.  OCH_E_CAPACITY:
+ * the caller's capacity is too small.  OCH_BUILD_TRACE=1 prints phase times. */
+enum { OCH_VOXELS_LIST = 0, OCH_VOXELS_GRID_U8 = 1, OCH_VOXELS_GRID_U32 = 2 };
+typedef struct och_voxel_params {
+    int32_t depth;       /* 1..21: dim = 1 << depth (3 * depth bits of Morton key fit 64) */
+    int32_t kind;
+    const void *data;    /* LIST: n x 4 uint32 (x, y, z, id), AoS.  GRID_*: dim^3 ids, x fastest, then y, then z */
+    uint64_t n;          /* LIST: records, < 2^31.  GRID_*: ignored */
+    int32_t on_device;   /* data is device memory of the current device (use_gpu = 1 only), its
+                            writes complete: the build reads it on a stream of its own */
+    int32_t use_gpu;     /* as och_terrain_params.use_gpu: 1 = current GPU, OCH_E_NODEV without one; 0 = host threads */
+    int32_t threads;     /* host path; 0 = all */
+    uint32_t capacity;   /* node ids to reserve, id 0 included; 0 = the exact bound, tree_nodes + 1.
+                            Less is enough when subtrees are shared: the unique nodes + 1 on the GPU */
+} och_voxel_params;
+OCH_API int och_build_voxels(const och_voxel_params *params, och_host_pool *out);
+
 /* The packed device layout (OCH_OPT_LAYOUT 1) of a pool, on the host: node 0
  * is zero padding, ids are breadth-first per level, interior slots hold
  * child_id | child_mask << 24, leaf-level slots voxel ids; *out_root =

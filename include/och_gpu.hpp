@@ -11,6 +11,7 @@
 #include <stdexcept>
 #include <string>
 #include <array>
+#include <utility>
 #include <vector>
 
 #include "och_gpu.h"
@@ -208,6 +209,36 @@ private:
     och_editor *ed_ = nullptr;
     int depth_;
 };
+
+// A pool built into host memory (och_build_voxels); owns its nodes.
+class host_pool {
+public:
+    host_pool() = default;
+    host_pool(host_pool &&o) noexcept : pool_(o.pool_) { o.pool_ = och_host_pool{}; }
+    host_pool &operator=(host_pool &&o) noexcept
+    {
+        std::swap(pool_, o.pool_);
+        return *this;
+    }
+    host_pool(const host_pool &) = delete;
+    host_pool &operator=(const host_pool &) = delete;
+    ~host_pool() { och_host_pool_free(&pool_); }
+
+    const och_host_pool &get() const { return pool_; }
+    och_host_pool *out() { return &pool_; }
+
+private:
+    och_host_pool pool_{};
+};
+
+// A DAG from the caller's voxels: a list of (x, y, z, id) records that act as
+// successive h_octree::set calls, or a dense grid (och_voxel_params).
+inline host_pool build_voxels(const och_voxel_params &params)
+{
+    host_pool p;
+    check(och_build_voxels(&params, p.out()), "och_build_voxels");
+    return p;
+}
 
 // Every GPU of the node from one host thread: a pool replica
 // per device, row chunks dealt round-robin, one RCCL all-gather, shading on

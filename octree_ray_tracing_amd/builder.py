@@ -15,7 +15,7 @@ from pathlib import Path
 
 import numpy as np
 
-from ._lib import HostPool, TerrainParams, call
+from ._lib import HostPool, TerrainParams, VoxelParams, call
 
 
 @dataclass
@@ -101,8 +101,12 @@ def build_terrain(depth: int, tunnels: bool = True, dedup: bool = True, rand_kin
     OchError OCH_E_NODEV without one); the pool is the same either way."""
     params = TerrainParams(int(depth), int(tunnels), int(dedup), 1 if rand_kind == "msvc" else 0,
                            int(threads), int(bool(use_gpu)))
+    return _build("och_build_terrain", params)
+
+
+def _build(name: str, params) -> NodePool:
     hp = HostPool()
-    call("och_build_terrain", C.byref(params), C.byref(hp))
+    call(name, C.byref(params), C.byref(hp))
     try:
         n = hp.n_nodes
         arr = np.ctypeslib.as_array(hp.nodes, shape=(n * 8,)).reshape(n, 8).copy()
@@ -110,6 +114,72 @@ def build_terrain(depth: int, tunnels: bool = True, dedup: bool = True, rand_kin
         call("och_host_pool_free", C.byref(hp))
     return NodePool(arr, hp.root, hp.depth, hp.index_base, hp.solid_voxels, list(hp.voxel_hist),
                     hp.tree_nodes, hp.build_seconds)
+
+
+VOXELS_LIST, VOXELS_GRID_U8, VOXELS_GRID_U32 = 0, 1, 2
+
+
+def build_voxels(voxels, depth: int | None = None, use_gpu: bool = False, threads: int = 0, capacity: int = 0) -> NodePool:
+    """A DAG from the caller's voxels (och_build_voxels), the same canonical pool whatever the path,
+    the record order or the input kind.
+
+    voxels is an (n, 4) integer array of (x, y, z, id) records that act as successive set() calls (a
+    later record replaces an earlier one, id 0 removes, coordinates outside the tree are ignored; depth
+    is required), or a cubic 3-D uint8 / uint32 array indexed [z, y, x] with a power-of-two side (the
+    depth follows from the side).  A numpy array is host memory; a CUDA torch tensor (int32 / uint32
+    records) is read where it lies, on the current device, and needs use_gpu=True.  capacity = node ids
+    to reserve, 0 = the exact bound."""
+    if hasattr(voxels, "is_cuda") and not voxels.is_cuda:
+        voxels = voxels.numpy()
+    on_device = hasattr(voxels, "is_cuda")
+    if on_device:
+        if not use_gpu:
+            raise ValueError("build_voxels: a device tensor needs use_gpu=True")
+        import torch
+
+        if voxels.dim() != 2 or voxels.shape[1] != 4 or voxels.dtype not in (torch.int32, torch.uint32):
+            raise ValueError(f"build_voxels: a device list is an (n, 4) int32 / uint32 tensor, not "
+                             f"{tuple(voxels.shape)} {voxels.dtype}")
+        if voxels.device.index != torch.cuda.current_device():
+            raise ValueError(f"build_voxels: the tensor is on {voxels.device}, the current device is "
+                             f"{torch.cuda.current_device()}")
+        voxels = voxels.contiguous()
+        torch.cuda.current_stream().synchronize()      # the build reads on a stream of its own
+        kind, n, ptr = VOXELS_LIST, voxels.shape[0], voxels.data_ptr()
+    else:
+        voxels = np.asarray(voxels)
+        if voxels.ndim == 2 and voxels.shape[1] == 4:
+            if voxels.dtype.kind not in "iu":
+                raise ValueError(f"build_voxels: records are integers, not {voxels.dtype}")
+            if voxels.dtype.itemsize != 4:
+                wide = voxels.astype(np.int64)
+                if wide.size and not (0 <= wide[:, 3].min() and wide[:, 3].max() <= 0xFFFFFFFF):
+                    raise ValueError("build_voxels: a voxel id outside uint32")
+                outside = ((wide[:, :3] < 0) | (wide[:, :3] > 0xFFFFFFFF)).any(axis=1)
+                wide[outside, :3] = 0xFFFFFFFF         # outside any tree: ignored
+                voxels = wide.astype(np.uint32)
+            voxels = np.ascontiguousarray(voxels).view(np.uint32)
+            kind, n = VOXELS_LIST, voxels.shape[0]
+        elif voxels.ndim == 3:
+            side = voxels.shape[0]
+            if voxels.shape != (side, side, side) or side < 2 or side & (side - 1):
+                raise ValueError(f"build_voxels: a grid is cubic with a power-of-two side >= 2, not {voxels.shape}")
+            if voxels.dtype not in (np.uint8, np.uint32):
+                raise ValueError(f"build_voxels: a grid holds uint8 or uint32 ids, not {voxels.dtype}")
+            if depth is not None and 1 << int(depth) != side:
+                raise ValueError(f"build_voxels: depth {depth} does not match a grid of side {side}")
+            depth = side.bit_length() - 1
+            voxels = np.ascontiguousarray(voxels)
+            kind, n = (VOXELS_GRID_U8 if voxels.dtype == np.uint8 else VOXELS_GRID_U32), 0
+        else:
+            raise ValueError(f"build_voxels: an (n, 4) record list or a cubic 3-D grid, not shape {voxels.shape}")
+        ptr = voxels.ctypes.data
+    if depth is None:
+        raise ValueError("build_voxels: a record list needs depth")
+    if not 0 <= int(capacity) <= 0xFFFFFFFF:
+        raise ValueError(f"build_voxels: capacity {capacity} outside uint32")
+    params = VoxelParams(int(depth), kind, ptr, int(n), int(on_device), int(bool(use_gpu)), int(threads), int(capacity))
+    return _build("och_build_voxels", params)
 
 
 def occupied_box(nodes: np.ndarray, root: int, depth: int, index_base: int = 1):

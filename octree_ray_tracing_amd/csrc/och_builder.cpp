@@ -23,6 +23,10 @@
 // on the GPU too (build_dag_gpu, below) and only renumbered on the host; an
 // expanded tree's nodes are allocated by host threads from the codes, batch
 // after batch, while the GPU computes the next batch.  Same pool either way.
+//
+// och_build_voxels ("voxel builder", below) builds the same canonical DAG from
+// a caller's voxels -- a record list or a dense grid -- through Morton keys and
+// a sort, with the same table, kernels and renumbering.
 #include <hip/hip_runtime.h>
 #include <sched.h>
 #include <sys/mman.h>
@@ -550,13 +554,15 @@ struct GpuStore {
 };
 
 // One level: nb grids of side n (node index = grid * n^3 + (z * n + y) * n + x),
-// children in the previous level's grids of side 2n.
+// children in the previous level's grids of side 2n; or (rows = 1, the voxel
+// builder) a list of count rows, node index i's eight child words at src[8 i].
 struct GpuLevel {
     const uint32_t *src;   // child ids, or leaf codes (codes = 1: the child id is leaf_id[code])
     int codes;
     int log2n;
-    uint32_t count;        // nb * n^3
+    uint32_t count;        // nb * n^3, or the rows
     int h;
+    int rows = 0;
 };
 
 constexpr int kCounters = 64;
@@ -590,6 +596,12 @@ __device__ inline uint32_t alloc_node(const GpuStore &S, const uint32_t c[8], in
 
 __device__ inline bool gather(const GpuStore &S, const GpuLevel &L, uint32_t idx, uint32_t c[8])
 {
+    if (L.rows) {   // child words as they are: a leaf-level row holds voxel ids, all 32 bits
+        const uint4 *row = reinterpret_cast<const uint4 *>(L.src + (size_t)idx * 8);
+        const uint4 a = row[0], b = row[1];
+        c[0] = a.x, c[1] = a.y, c[2] = a.z, c[3] = a.w, c[4] = b.x, c[5] = b.y, c[6] = b.z, c[7] = b.w;
+        return (a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w) != 0;
+    }
     const uint32_t n = 1u << L.log2n, m = 2u * n;
     const uint32_t g = idx >> (3 * L.log2n), r = idx & ((1u << (3 * L.log2n)) - 1u);
     const uint32_t x = r & (n - 1u), y = (r >> L.log2n) & (n - 1u), z = r >> (2 * L.log2n);
@@ -629,28 +641,22 @@ __global__ __launch_bounds__(256) void k_intern_codes(GpuStore S, const uint32_t
     __hip_atomic_store(&S.leaf_id[code], alloc_node(S, c, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ __launch_bounds__(256) void k_intern(GpuStore S, GpuLevel L, uint32_t *__restrict__ rep,
-                                                uint32_t *__restrict__ slot)
+// Probe the table for node idx of level L (children c, not all empty): the
+// node's rep value.  The claimant of an empty slot allocates the id and
+// returns it (slot[idx] = its slot); everyone else returns what the slot of an
+// equal node holds, kCand | the claimant's index or a finished id.  Only table
+// values carry the kCand flag: child words are compared, never tested for it.
+__device__ inline uint32_t probe_node(const GpuStore &S, const GpuLevel &L, uint32_t idx, const uint32_t c[8],
+                                      uint32_t *__restrict__ slot)
 {
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t c[8];
-    const bool any = idx < L.count && gather(S, L, idx, c);
-    count_nodes(S, any);
-    if (idx >= L.count) return;
-    slot[idx] = kNoSlot;
-    if (!any) {
-        rep[idx] = 0;
-        return;
-    }
     uint32_t i = node_slot(c, L.h, S.tmask);
     for (uint32_t probe = 0; probe <= S.tmask; ++probe, i = (i + 1u) & S.tmask) {
         uint32_t v = S.table[i];   // a stale 0 is corrected by the CAS; claims and ids are never stale
         if (v == 0) {
             v = atomicCAS(&S.table[i], 0u, kCand | idx);
             if (v == 0) {
-                rep[idx] = alloc_node(S, c, L.h);
                 slot[idx] = i;
-                return;
+                return alloc_node(S, c, L.h);
             }
         }
         bool same = true;
@@ -665,13 +671,45 @@ __global__ __launch_bounds__(256) void k_intern(GpuStore S, GpuLevel L, uint32_t
             same = S.level[v] == (uint8_t)L.h && a.x == c[0] && a.y == c[1] && a.z == c[2] && a.w == c[3] &&
                    b.x == c[4] && b.y == c[5] && b.z == c[6] && b.w == c[7];
         }
-        if (same) {
-            rep[idx] = v;
-            return;
-        }
+        if (same) return v;
     }
     atomicOr(S.overflow, 2u);
-    rep[idx] = 0;
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void k_intern(GpuStore S, GpuLevel L, uint32_t *__restrict__ rep,
+                                                uint32_t *__restrict__ slot)
+{
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t c[8];
+    const bool any = idx < L.count && gather(S, L, idx, c);
+    count_nodes(S, any);
+    if (idx >= L.count) return;
+    slot[idx] = kNoSlot;
+    rep[idx] = any ? probe_node(S, L, idx, c, slot) : 0u;
+}
+
+// The voxel builder's rows (GpuLevel.rows; none is empty).  A solid region is
+// millions of equal rows in a row, all bound for one table slot: the lanes of
+// a wavefront whose row equals its first lane's leave the probe to that lane
+// and take its rep value through the registers, so one slot sees a wavefront's
+// worth fewer compare-and-swaps while the claim is still invisible to others.
+__global__ __launch_bounds__(256) void k_intern_rows(GpuStore S, GpuLevel L, uint32_t *__restrict__ rep,
+                                                     uint32_t *__restrict__ slot)
+{
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = idx < L.count;
+    uint32_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (live) gather(S, L, idx, c);
+    // lane 0 of a wavefront is live whenever any of its lanes is (idx ascends)
+    bool follows = live && (threadIdx.x & 63u) != 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) follows &= __shfl(c[k], 0) == c[k];
+    uint32_t r = 0;
+    if (live) slot[idx] = kNoSlot;
+    if (live && !follows) r = probe_node(S, L, idx, c, slot);
+    const uint32_t lead = __shfl(r, 0);   // an id or kCand | index, both final for an equal row
+    if (live) rep[idx] = follows ? lead : r;
 }
 
 // dst[dst_index ? dst_index[idx] : idx] = the node's id.
@@ -740,6 +778,71 @@ __global__ __launch_bounds__(256) void k_bfs_output(const uint32_t *__restrict__
     out[q] = (level[v] == 0 || !c) ? c : newid[c];
 }
 
+#define DAG_HIP(expr)                          \
+    do {                                       \
+        if ((expr) != hipSuccess) return OCH_E_HIP; \
+    } while (0)
+
+using DeviceAlloc = std::function<bool(void **, size_t)>;   // hipMalloc into the caller's list of buffers
+
+dim3 blocks(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+// The store's nodes reachable from root (!= 0), renumbered breadth-first and
+// 1-based on the device (k_bfs_*).  *out: malloc'd n_out x 8 words, as renumber().
+int renumber_gpu(const GpuStore &S, uint32_t used, uint32_t root, int depth, hipStream_t st, const DeviceAlloc &dalloc,
+                 uint32_t **out, uint32_t *n_out, bool trace)
+{
+    const auto t_bfs = std::chrono::steady_clock::now();
+    // first / newid / order over the ids, mark / pos over one level's candidates
+    uint32_t *d_first, *d_newid, *d_order, *d_mark, *d_pos, *d_out;
+    const size_t max_cand = (size_t)used * 8;
+    if (!dalloc((void **)&d_first, (size_t)used * 4) || !dalloc((void **)&d_newid, (size_t)used * 4) ||
+        !dalloc((void **)&d_order, (size_t)used * 4) || !dalloc((void **)&d_mark, max_cand * 4) ||
+        !dalloc((void **)&d_pos, max_cand * 4) || !dalloc((void **)&d_out, max_cand * 4))
+        return OCH_E_NOMEM;
+    size_t scan_bytes = 0;
+    DAG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, d_mark, d_pos, (int)max_cand, st));
+    void *d_scan = nullptr;
+    if (!dalloc(&d_scan, std::max<size_t>(scan_bytes, 4))) return OCH_E_NOMEM;
+    const uint32_t base = 1;
+    DAG_HIP(hipMemsetAsync(d_first, 0xFF, (size_t)used * 4, st));
+    DAG_HIP(hipMemcpyAsync(d_order, &root, 4, hipMemcpyHostToDevice, st));
+    DAG_HIP(hipMemcpyAsync(d_newid + root, &base, 4, hipMemcpyHostToDevice, st));
+    uint32_t off = 0, f = 1;
+    for (int l = 1; l < depth && f; ++l) {
+        const uint32_t nc = 8 * f, next = off + f;
+        hipLaunchKernelGGL(k_bfs_first, blocks(nc), dim3(256), 0, st, S.nodes, d_order + off, f, d_first);
+        hipLaunchKernelGGL(k_bfs_mark, blocks(nc), dim3(256), 0, st, S.nodes, d_order + off, f, d_first, d_mark);
+        DAG_HIP(hipGetLastError());
+        DAG_HIP(hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, d_mark, d_pos, (int)nc, st));
+        hipLaunchKernelGGL(k_bfs_place, blocks(nc), dim3(256), 0, st, S.nodes, d_order + off, f, d_mark, d_pos, d_order,
+                           next, d_newid, base);
+        DAG_HIP(hipGetLastError());
+        uint32_t tail[2];
+        DAG_HIP(hipMemcpyAsync(&tail[0], d_pos + nc - 1, 4, hipMemcpyDeviceToHost, st));
+        DAG_HIP(hipMemcpyAsync(&tail[1], d_mark + nc - 1, 4, hipMemcpyDeviceToHost, st));
+        DAG_HIP(hipStreamSynchronize(st));
+        off = next;
+        f = tail[0] + tail[1];
+    }
+    const uint32_t n = off + f;
+    hipLaunchKernelGGL(k_bfs_output, blocks((size_t)n * 8), dim3(256), 0, st, S.nodes, S.level, d_order, d_newid, n, d_out);
+    DAG_HIP(hipGetLastError());
+    uint32_t *nodes = static_cast<uint32_t *>(std::malloc((size_t)n * 32));
+    if (!nodes) return OCH_E_NOMEM;
+    if (hipMemcpyAsync(nodes, d_out, (size_t)n * 32, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+        std::free(nodes);
+        return OCH_E_HIP;
+    }
+    *out = nodes;
+    *n_out = n;
+    if (trace)
+        std::fprintf(stderr, "[och_build] gpu renumbering %.3f s\n",
+                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t_bfs).count());
+    return OCH_OK;
+}
+
 // The whole DAG on the current GPU: bricks voxelised (k_brick_codes) and
 // interned batch by batch, then the levels above the bricks, then renumbered
 // breadth-first (1-based).  *out: malloc'd n_out x 8 words, as renumber().
@@ -790,10 +893,6 @@ int build_dag_gpu(const Terrain &tr, uint32_t cap, const std::vector<uint32_t> &
             enc[i] = (w % G) | ((w / G) % G) << 10 | (w / (G * G)) << 20;
         }
         const uint32_t one = 1;
-#define DAG_HIP(expr)                          \
-    do {                                       \
-        if ((expr) != hipSuccess) return OCH_E_HIP; \
-    } while (0)
         DAG_HIP(hipMemcpyAsync(d_heights, tr.heights.data(), cols * 4, hipMemcpyHostToDevice, st));
         DAG_HIP(hipMemcpyAsync(d_tops, tr.tops.data(), cols, hipMemcpyHostToDevice, st));
         DAG_HIP(hipMemcpyAsync(d_enc, enc.data(), n_work * 4, hipMemcpyHostToDevice, st));
@@ -804,7 +903,6 @@ int build_dag_gpu(const Terrain &tr, uint32_t cap, const std::vector<uint32_t> &
         DAG_HIP(hipMemsetAsync(S.leaf_id, 0, (size_t)4 << 24, st));
         DAG_HIP(hipMemsetAsync(S.nodes, 0, 32, st));
         DAG_HIP(hipMemsetAsync(d_grid[0], 0, grid_cells * 4, st));
-        auto blocks = [](size_t n) { return dim3((unsigned)((n + 255) / 256)); };
         auto level_pass = [&](const GpuLevel &L, uint32_t *dst, const uint32_t *dst_index) -> bool {
             if (L.count == 0) return true;
             hipLaunchKernelGGL(k_intern, blocks(L.count), dim3(256), 0, st, S, L, d_rep, d_slot);
@@ -847,62 +945,14 @@ int build_dag_gpu(const Terrain &tr, uint32_t cap, const std::vector<uint32_t> &
             for (int v = 0; v < 6; ++v) total.hist[v] += info[i * 8 + 1 + v];
             total.tree_nodes += info[i * 8 + 7];
         }
-        const auto t_bfs = std::chrono::steady_clock::now();
         if (!root) {   // empty world: one zero node
             *n_out = 1;
             *out = static_cast<uint32_t *>(std::calloc(8, 4));
             return *out ? OCH_OK : OCH_E_NOMEM;
         }
-        // renumbering: first / newid / order over the ids, mark / pos over one level's candidates
-        uint32_t *d_first, *d_newid, *d_order, *d_mark, *d_pos, *d_out;
-        const size_t max_cand = (size_t)used * 8;
-        if (!dalloc((void **)&d_first, (size_t)used * 4) || !dalloc((void **)&d_newid, (size_t)used * 4) ||
-            !dalloc((void **)&d_order, (size_t)used * 4) || !dalloc((void **)&d_mark, max_cand * 4) ||
-            !dalloc((void **)&d_pos, max_cand * 4) || !dalloc((void **)&d_out, max_cand * 4))
-            return OCH_E_NOMEM;
-        size_t scan_bytes = 0;
-        DAG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, d_mark, d_pos, (int)max_cand, st));
-        void *d_scan = nullptr;
-        if (!dalloc(&d_scan, std::max<size_t>(scan_bytes, 4))) return OCH_E_NOMEM;
-        const uint32_t base = 1;
-        DAG_HIP(hipMemsetAsync(d_first, 0xFF, (size_t)used * 4, st));
-        DAG_HIP(hipMemcpyAsync(d_order, &root, 4, hipMemcpyHostToDevice, st));
-        DAG_HIP(hipMemcpyAsync(d_newid + root, &base, 4, hipMemcpyHostToDevice, st));
-        uint32_t off = 0, f = 1;
-        for (int l = 1; l < tr.depth && f; ++l) {
-            const uint32_t nc = 8 * f, next = off + f;
-            hipLaunchKernelGGL(k_bfs_first, blocks(nc), dim3(256), 0, st, S.nodes, d_order + off, f, d_first);
-            hipLaunchKernelGGL(k_bfs_mark, blocks(nc), dim3(256), 0, st, S.nodes, d_order + off, f, d_first, d_mark);
-            DAG_HIP(hipGetLastError());
-            DAG_HIP(hipcub::DeviceScan::ExclusiveSum(d_scan, scan_bytes, d_mark, d_pos, (int)nc, st));
-            hipLaunchKernelGGL(k_bfs_place, blocks(nc), dim3(256), 0, st, S.nodes, d_order + off, f, d_mark, d_pos, d_order,
-                               next, d_newid, base);
-            DAG_HIP(hipGetLastError());
-            uint32_t tail[2];
-            DAG_HIP(hipMemcpyAsync(&tail[0], d_pos + nc - 1, 4, hipMemcpyDeviceToHost, st));
-            DAG_HIP(hipMemcpyAsync(&tail[1], d_mark + nc - 1, 4, hipMemcpyDeviceToHost, st));
-            DAG_HIP(hipStreamSynchronize(st));
-            off = next;
-            f = tail[0] + tail[1];
-        }
-        const uint32_t n = off + f;
-        hipLaunchKernelGGL(k_bfs_output, blocks((size_t)n * 8), dim3(256), 0, st, S.nodes, S.level, d_order, d_newid, n, d_out);
-        DAG_HIP(hipGetLastError());
-        uint32_t *nodes = static_cast<uint32_t *>(std::malloc((size_t)n * 32));
-        if (!nodes) return OCH_E_NOMEM;
-        if (hipMemcpyAsync(nodes, d_out, (size_t)n * 32, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) {
-            std::free(nodes);
-            return OCH_E_HIP;
-        }
-        *out = nodes;
-        *n_out = n;
-        if (trace)
-            std::fprintf(stderr, "[och_build] gpu renumbering %.3f s\n",
-                         std::chrono::duration<double>(std::chrono::steady_clock::now() - t_bfs).count());
-#undef DAG_HIP
-        if (trace) std::fprintf(stderr, "[och_build] gpu dag: %zu bricks, %u ids\n", n_work, used);
-        return OCH_OK;
+        const int rs = renumber_gpu(S, used, root, tr.depth, st, dalloc, out, n_out, trace);
+        if (rs == OCH_OK && trace) std::fprintf(stderr, "[och_build] gpu dag: %zu bricks, %u ids\n", n_work, used);
+        return rs;
     };
     status = run();
     if (st) {
@@ -952,6 +1002,504 @@ int renumber(const uint32_t *store, const uint8_t *level, uint32_t used, uint32_
     }
     *out = nodes;
     return OCH_OK;
+}
+
+// ------------------------------------------------------------ voxel builder
+//
+// A DAG from the caller's voxels (och_build_voxels): a list of (x, y, z, id)
+// records that act as successive h_octree::set calls, or a dense grid of ids.
+// Every voxel gets a Morton key, three bits per level with the leaf level's
+// child index x | y << 1 | z << 2 in the low bits, so key >> 3 (h + 1) names
+// its ancestor at height h and a sorted list of unique keys holds every node's
+// children side by side.  Host and GPU run the same steps:
+//   keys      -- one key per record, value = the record's index; a record
+//                outside the tree gets bit 3 depth, sorts last and is dropped.
+//                A grid's cell i *is* key i: sorted and unique as it stands.
+//   sort      -- stable, so equal keys keep record order.
+//   last wins -- an entry survives iff it is the last of its key and its id is
+//                not 0; the survivors are counted per id here.
+//   counts    -- neighbours i - 1, i of the unique list first differ in child
+//                index t = (highest differing bit) / 3: entry i opens a new
+//                node at the heights below t.  One pass bins t; the suffix
+//                sums are the node counts of all levels, which size every
+//                buffer and launch before the level loop starts.
+//   levels    -- h = 0 .. depth - 1: entries with equal key >> 3 form one row
+//                of eight child words (voxel ids at h = 0, all 32 bits; node
+//                ids above), rows are interned into (level, 8 words) -> id and
+//                the ids become the next level's child words.
+//   renumber  -- breadth-first, as the terrain builder.
+// On the GPU each step is its own dispatch: rows, keys and node records are
+// read only by later dispatches than the one that wrote them, and within a
+// dispatch workgroups meet only in the atomics (k_intern's rule, above).
+
+constexpr int kMaxVoxelDepth = 21;   // 3 * 21 key bits + the out-of-range bit = 64
+constexpr int kBins = 32;            // level bins per counter row (>= kMaxVoxelDepth + 1)
+
+struct VoxelStats {
+    uint64_t solid = 0, hist[8] = {0}, tree_nodes = 0;
+};
+
+__host__ __device__ inline uint64_t spread3(uint64_t x)   // bit i of 21 -> bit 3 i
+{
+    x &= 0x1FFFFFull;
+    x = (x | x << 32) & 0x1F00000000FFFFull;
+    x = (x | x << 16) & 0x1F0000FF0000FFull;
+    x = (x | x << 8) & 0x100F00F00F00F00Full;
+    x = (x | x << 4) & 0x10C30C30C30C30C3ull;
+    x = (x | x << 2) & 0x1249249249249249ull;
+    return x;
+}
+
+__host__ __device__ inline uint32_t compact3(uint64_t x)   // bit 3 i -> bit i
+{
+    x &= 0x1249249249249249ull;
+    x = (x ^ (x >> 2)) & 0x10C30C30C30C30C3ull;
+    x = (x ^ (x >> 4)) & 0x100F00F00F00F00Full;
+    x = (x ^ (x >> 8)) & 0x1F0000FF0000FFull;
+    x = (x ^ (x >> 16)) & 0x1F00000000FFFFull;
+    x = (x ^ (x >> 32)) & 0x1FFFFFull;
+    return (uint32_t)x;
+}
+
+__host__ __device__ inline uint64_t voxel_key(uint32_t x, uint32_t y, uint32_t z, int depth)
+{
+    if ((x | y | z) >> depth) return 1ull << (3 * depth);   // outside the tree
+    return spread3(x) | spread3(y) << 1 | spread3(z) << 2;
+}
+
+// The heights below which `key` opens new nodes after its predecessor `prev`
+// in the unique list (first = no predecessor: a new node at every height).
+__host__ __device__ inline int level_bin(bool first, uint64_t prev, uint64_t key, int depth)
+{
+    return first ? depth : (63 - __builtin_clzll(prev ^ key)) / 3;
+}
+
+// counts[h], h < depth, from the bins; returns their sum (the expanded tree's nodes).
+uint64_t level_counts(const uint64_t *bins, int depth, uint64_t *counts)
+{
+    uint64_t above = 0, sum = 0;
+    for (int h = depth - 1; h >= 0; --h) {
+        above += bins[h + 1];
+        counts[h] = above;
+        sum += above;
+    }
+    return sum;
+}
+
+// Ids to reserve: the caller's, or the exact bound (one per tree node, + id 0).
+// Ids and row indices share a word with the kCand flag: below 2^31 both.
+uint32_t voxel_capacity(uint32_t wanted, uint64_t tree_nodes)
+{
+    const uint64_t bound = std::min<uint64_t>(tree_nodes + 1, kCand);
+    return (uint32_t)(wanted ? std::min<uint64_t>(wanted, bound) : bound);
+}
+
+// Block-wide count of the kept voxels per id 1..7, then one atomic per id and
+// block on one of kCounters rows (128 B apart), as count_nodes.
+__device__ inline void count_ids(bool keep, uint32_t id, unsigned long long *counters)
+{
+    __shared__ uint32_t hist[8];
+    if (threadIdx.x < 8) hist[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint32_t k = 1; k < 8; ++k) {
+        const uint64_t b = __ballot(keep && id == k);
+        if ((threadIdx.x & 63u) == 0 && b) atomicAdd(&hist[k], (uint32_t)__popcll(b));
+    }
+    __syncthreads();
+    if (threadIdx.x >= 1 && threadIdx.x < 8 && hist[threadIdx.x])
+        atomicAdd(counters + 16 * (blockIdx.x % kCounters) + threadIdx.x, (unsigned long long)hist[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(256) void k_vox_keys(const uint32_t *__restrict__ recs, uint32_t n, int depth,
+                                                  uint64_t *__restrict__ keys, uint32_t *__restrict__ vals)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t *r = recs + (size_t)i * 4;
+    keys[i] = voxel_key(r[0], r[1], r[2], depth);
+    vals[i] = i;
+}
+
+// Last wins, over the sorted list: flags[i] = entry i is kept, ids[i] = its id.
+__global__ __launch_bounds__(256) void k_vox_last(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
+                                                  const uint32_t *__restrict__ recs, uint32_t n, int depth,
+                                                  uint32_t *__restrict__ flags, uint32_t *__restrict__ ids,
+                                                  unsigned long long *__restrict__ counters)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t id = 0;
+    if (i < n) {
+        const uint64_t key = keys[i];
+        if (!(key >> (3 * depth)) && (i + 1 == n || keys[i + 1] != key)) id = recs[(size_t)vals[i] * 4 + 3];
+        flags[i] = id != 0;
+        ids[i] = id;
+    }
+    count_ids(id != 0, id, counters);
+}
+
+// A grid's cells in key order (n = dim^3 <= 2^30): thread i is key i.
+template <class T>
+__global__ __launch_bounds__(256) void k_vox_cells(const T *__restrict__ grid, uint32_t n, int depth,
+                                                   uint32_t *__restrict__ flags, uint32_t *__restrict__ ids,
+                                                   unsigned long long *__restrict__ counters)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t id = 0;
+    if (i < n) {
+        const size_t x = compact3(i), y = compact3(i >> 1), z = compact3(i >> 2);
+        id = grid[(z << depth | y) << depth | x];
+        flags[i] = id != 0;
+        ids[i] = id;
+    }
+    count_ids(id != 0, id, counters);
+}
+
+// The kept entries, packed: pos = the inclusive sum of flags; keys = null for a grid.
+__global__ __launch_bounds__(256) void k_vox_compact(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ flags,
+                                                     const uint32_t *__restrict__ pos, const uint32_t *__restrict__ ids,
+                                                     uint32_t n, uint64_t *__restrict__ ukeys, uint32_t *__restrict__ words)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !flags[i]) return;
+    const uint32_t p = pos[i] - 1u;
+    ukeys[p] = keys ? keys[i] : (uint64_t)i;
+    words[p] = ids[i];
+}
+
+// Level bins of the unique list: an LDS histogram per block, then one atomic
+// per bin and block on one of kCounters rows of kBins.
+__global__ __launch_bounds__(256) void k_vox_levels(const uint64_t *__restrict__ ukeys, uint32_t m, int depth,
+                                                    uint32_t *__restrict__ bins)
+{
+    __shared__ uint32_t hist[kBins];
+    if (threadIdx.x < kBins) hist[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < m) {
+        const int t = level_bin(i == 0, i ? ukeys[i - 1] : 0, ukeys[i], depth);
+        if (t) atomicAdd(&hist[t], 1u);   // t = 0: another voxel of the same leaf-level node
+    }
+    __syncthreads();
+    if (threadIdx.x < kBins && hist[threadIdx.x])
+        atomicAdd(bins + kBins * (blockIdx.x % kCounters) + threadIdx.x, hist[threadIdx.x]);
+}
+
+// flags[i] = entry i is the first child of its parent.
+__global__ __launch_bounds__(256) void k_vox_heads(const uint64_t *__restrict__ keys, uint32_t n, uint32_t *__restrict__ flags)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    flags[i] = i == 0 || (keys[i] >> 3) != (keys[i - 1] >> 3);
+}
+
+// Entry i's child word into its parent's (pre-zeroed) row, node = pos[i] - 1
+// (pos = the inclusive sum of the head flags); every head stores the parent key.
+__global__ __launch_bounds__(256) void k_vox_rows(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ words,
+                                                  uint32_t n, const uint32_t *__restrict__ flags,
+                                                  const uint32_t *__restrict__ pos, uint32_t n_rows,
+                                                  uint32_t *__restrict__ rows, uint64_t *__restrict__ parents,
+                                                  uint32_t *__restrict__ overflow)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t node = pos[i] - 1u;
+    if (node >= n_rows) {   // the level counts size the rows: never, unless they are wrong
+        atomicOr(overflow, 4u);
+        return;
+    }
+    const uint64_t key = keys[i];
+    rows[(size_t)node * 8 + (key & 7u)] = words[i];
+    if (flags[i]) parents[node] = key >> 3;
+}
+
+int build_voxels_gpu(const och_voxel_params &P, uint32_t **out, uint32_t *n_out, uint32_t &root, VoxelStats &vs, bool trace)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return OCH_E_NODEV;
+    (void)hipGetLastError();        // a stale error of an earlier HIP call (another library's) is not this build's
+    const int depth = P.depth;
+    const bool list = P.kind == OCH_VOXELS_LIST;
+    const uint32_t n = list ? (uint32_t)P.n : 1u << (3 * depth);
+    const size_t in_bytes = list ? (size_t)n * 16 : (size_t)n * (P.kind == OCH_VOXELS_GRID_U8 ? 1 : 4);
+    auto empty = [&] {   // no voxels: one zero node
+        root = 0;
+        *n_out = 1;
+        *out = static_cast<uint32_t *>(std::calloc(8, 4));
+        return *out ? OCH_OK : OCH_E_NOMEM;
+    };
+    if (n == 0) return empty();
+    std::vector<void *> bufs;
+    hipStream_t st = nullptr;
+    auto dalloc = [&](void **p, size_t bytes) {
+        if (hipMalloc(p, std::max<size_t>(bytes, 4)) != hipSuccess) return false;
+        bufs.push_back(*p);
+        return true;
+    };
+    auto run = [&]() -> int {
+        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return OCH_E_HIP;
+        auto t_last = std::chrono::steady_clock::now();
+        auto phase = [&](const char *name) -> bool {   // OCH_BUILD_TRACE only: a synchronise per phase
+            if (!trace) return true;
+            if (hipStreamSynchronize(st) != hipSuccess) return false;
+            const auto now = std::chrono::steady_clock::now();
+            std::fprintf(stderr, "[och_build] voxels gpu %-10s %8.4f s\n", name,
+                         std::chrono::duration<double>(now - t_last).count());
+            t_last = now;
+            return true;
+        };
+        const void *d_in = P.data;
+        if (!P.on_device) {
+            void *up;
+            if (!dalloc(&up, in_bytes)) return OCH_E_NOMEM;
+            DAG_HIP(hipMemcpyAsync(up, P.data, in_bytes, hipMemcpyHostToDevice, st));
+            d_in = up;
+        }
+        uint64_t *d_keys[2] = {nullptr, nullptr};
+        uint32_t *d_words[2] = {nullptr, nullptr}, *d_flags, *d_pos, *d_ids, *d_bins;
+        unsigned long long *d_counters;
+        const size_t bins_bytes = (size_t)kCounters * kBins * 4, counters_bytes = (size_t)kCounters * 128;
+        if (!dalloc((void **)&d_flags, (size_t)n * 4) || !dalloc((void **)&d_pos, (size_t)n * 4) ||
+            !dalloc((void **)&d_ids, (size_t)n * 4) || !dalloc((void **)&d_bins, bins_bytes) ||
+            !dalloc((void **)&d_counters, counters_bytes))
+            return OCH_E_NOMEM;
+        if (list && (!dalloc((void **)&d_keys[0], (size_t)n * 8) || !dalloc((void **)&d_keys[1], (size_t)n * 8) ||
+                     !dalloc((void **)&d_words[0], (size_t)n * 4) || !dalloc((void **)&d_words[1], (size_t)n * 4)))
+            return OCH_E_NOMEM;
+        const int key_bits = std::min(64, 3 * depth + 1);
+        size_t sort_bytes = 0, scan_bytes = 0;
+        if (list)
+            DAG_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_keys[0], d_keys[1], d_words[0], d_words[1],
+                                                       (int)n, 0, key_bits, st));
+        DAG_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, d_flags, d_pos, (int)n, st));
+        const size_t temp_bytes = std::max(sort_bytes, scan_bytes);
+        void *d_temp;
+        if (!dalloc(&d_temp, temp_bytes)) return OCH_E_NOMEM;
+        DAG_HIP(hipMemsetAsync(d_bins, 0, bins_bytes, st));
+        DAG_HIP(hipMemsetAsync(d_counters, 0, counters_bytes, st));
+        if (!phase("upload")) return OCH_E_HIP;
+        const uint64_t *d_sorted = nullptr;
+        if (list) {
+            const uint32_t *recs = static_cast<const uint32_t *>(d_in);
+            hipLaunchKernelGGL(k_vox_keys, blocks(n), dim3(256), 0, st, recs, n, depth, d_keys[0], d_words[0]);
+            DAG_HIP(hipGetLastError());
+            size_t tb = temp_bytes;
+            DAG_HIP(hipcub::DeviceRadixSort::SortPairs(d_temp, tb, d_keys[0], d_keys[1], d_words[0], d_words[1], (int)n, 0,
+                                                       key_bits, st));
+            if (!phase("sort")) return OCH_E_HIP;
+            hipLaunchKernelGGL(k_vox_last, blocks(n), dim3(256), 0, st, d_keys[1], d_words[1], recs, n, depth, d_flags,
+                               d_ids, d_counters);
+            d_sorted = d_keys[1];
+        } else if (P.kind == OCH_VOXELS_GRID_U8) {
+            hipLaunchKernelGGL(k_vox_cells<uint8_t>, blocks(n), dim3(256), 0, st, static_cast<const uint8_t *>(d_in), n,
+                               depth, d_flags, d_ids, d_counters);
+        } else {
+            hipLaunchKernelGGL(k_vox_cells<uint32_t>, blocks(n), dim3(256), 0, st, static_cast<const uint32_t *>(d_in), n,
+                               depth, d_flags, d_ids, d_counters);
+        }
+        DAG_HIP(hipGetLastError());
+        size_t tb = temp_bytes;
+        DAG_HIP(hipcub::DeviceScan::InclusiveSum(d_temp, tb, d_flags, d_pos, (int)n, st));
+        uint32_t m = 0;
+        DAG_HIP(hipMemcpyAsync(&m, d_pos + (n - 1), 4, hipMemcpyDeviceToHost, st));
+        DAG_HIP(hipStreamSynchronize(st));
+        if (m == 0) return empty();
+        // a list packs into the sort's input buffers (free by now) and the levels
+        // alternate with its output buffers; a grid's are sized by its voxels
+        if (!list && (!dalloc((void **)&d_keys[0], (size_t)m * 8) || !dalloc((void **)&d_keys[1], (size_t)m * 8) ||
+                      !dalloc((void **)&d_words[0], (size_t)m * 4) || !dalloc((void **)&d_words[1], (size_t)m * 4)))
+            return OCH_E_NOMEM;
+        hipLaunchKernelGGL(k_vox_compact, blocks(n), dim3(256), 0, st, d_sorted, d_flags, d_pos, d_ids, n, d_keys[0],
+                           d_words[0]);
+        hipLaunchKernelGGL(k_vox_levels, blocks(m), dim3(256), 0, st, d_keys[0], m, depth, d_bins);
+        DAG_HIP(hipGetLastError());
+        std::vector<uint32_t> h_bins((size_t)kCounters * kBins);
+        std::vector<unsigned long long> h_counters((size_t)kCounters * 16);
+        DAG_HIP(hipMemcpyAsync(h_bins.data(), d_bins, bins_bytes, hipMemcpyDeviceToHost, st));
+        DAG_HIP(hipMemcpyAsync(h_counters.data(), d_counters, counters_bytes, hipMemcpyDeviceToHost, st));
+        DAG_HIP(hipStreamSynchronize(st));
+        if (!phase("last wins")) return OCH_E_HIP;
+        uint64_t bins[kBins] = {0}, counts[kMaxVoxelDepth] = {0};
+        for (int r = 0; r < kCounters; ++r) {
+            for (int t = 0; t < kBins; ++t) bins[t] += h_bins[(size_t)r * kBins + t];
+            for (int k = 1; k < 8; ++k) vs.hist[k] += h_counters[(size_t)r * 16 + k];
+        }
+        vs.solid = m;
+        vs.tree_nodes = level_counts(bins, depth, counts);
+        if (counts[0] > m || counts[depth - 1] != 1) return och::report(OCH_E_HIP, "GPU voxel builder: inconsistent level counts");
+        const uint32_t rows_max = (uint32_t)counts[0];   // counts only shrink towards the root
+        GpuStore S{};
+        S.cap = voxel_capacity(P.capacity, vs.tree_nodes);
+        uint64_t tsize = 1;
+        while (tsize < 2 * (uint64_t)S.cap) tsize <<= 1;
+        S.tmask = (uint32_t)(tsize - 1);
+        uint32_t *d_rows, *d_rep, *d_slot;
+        if (!dalloc((void **)&d_rows, (size_t)rows_max * 32) || !dalloc((void **)&d_rep, (size_t)rows_max * 4) ||
+            !dalloc((void **)&d_slot, (size_t)rows_max * 4) || !dalloc((void **)&S.nodes, (size_t)S.cap * 32) ||
+            !dalloc((void **)&S.level, S.cap) || !dalloc((void **)&S.next, 256) ||
+            !dalloc((void **)&S.table, (size_t)tsize * 4))
+            return OCH_E_NOMEM;
+        S.overflow = S.next + 1;
+        const uint32_t one = 1;
+        DAG_HIP(hipMemsetAsync(S.next, 0, 256, st));
+        DAG_HIP(hipMemcpyAsync(S.next, &one, 4, hipMemcpyHostToDevice, st));
+        DAG_HIP(hipMemsetAsync(S.table, 0, (size_t)tsize * 4, st));
+        DAG_HIP(hipMemsetAsync(S.nodes, 0, 32, st));
+        int cur = 0;
+        uint32_t n_in = m;
+        for (int h = 0; h < depth; ++h) {
+            const uint32_t n_rows = (uint32_t)counts[h];
+            hipLaunchKernelGGL(k_vox_heads, blocks(n_in), dim3(256), 0, st, d_keys[cur], n_in, d_flags);
+            DAG_HIP(hipGetLastError());
+            tb = temp_bytes;
+            DAG_HIP(hipcub::DeviceScan::InclusiveSum(d_temp, tb, d_flags, d_pos, (int)n_in, st));
+            DAG_HIP(hipMemsetAsync(d_rows, 0, (size_t)n_rows * 32, st));
+            hipLaunchKernelGGL(k_vox_rows, blocks(n_in), dim3(256), 0, st, d_keys[cur], d_words[cur], n_in, d_flags, d_pos,
+                               n_rows, d_rows, d_keys[cur ^ 1], S.overflow);
+            GpuLevel L{d_rows, 0, 0, n_rows, h, 1};
+            hipLaunchKernelGGL(k_intern_rows, blocks(n_rows), dim3(256), 0, st, S, L, d_rep, d_slot);
+            hipLaunchKernelGGL(k_settle, blocks(n_rows), dim3(256), 0, st, S, n_rows, d_rep, d_slot, d_words[cur ^ 1], nullptr);
+            DAG_HIP(hipGetLastError());
+            cur ^= 1;
+            n_in = n_rows;
+        }
+        uint32_t head[2] = {0, 0};
+        DAG_HIP(hipMemcpyAsync(head, S.next, 8, hipMemcpyDeviceToHost, st));
+        DAG_HIP(hipMemcpyAsync(&root, d_words[cur], 4, hipMemcpyDeviceToHost, st));
+        DAG_HIP(hipStreamSynchronize(st));
+        if (!phase("levels")) return OCH_E_HIP;
+        if (head[1] & 4u) return och::report(OCH_E_HIP, "GPU voxel builder: a row outside its level");
+        if (head[1] || !root) return OCH_E_CAPACITY;
+        const uint32_t used = std::min(head[0], S.cap);
+        const int rs = renumber_gpu(S, used, root, depth, st, dalloc, out, n_out, trace);
+        if (rs == OCH_OK && trace)
+            std::fprintf(stderr, "[och_build] voxels gpu: %u entries, %u voxels, %u ids of %u\n", n, m, used - 1, S.cap - 1);
+        return rs;
+    };
+    const int status = run();
+    if (st) {
+        (void)hipStreamSynchronize(st);
+        (void)hipStreamDestroy(st);
+    }
+    for (void *p : bufs) (void)hipFree(p);
+    return status;
+}
+
+// Stable sort of (key, record) pairs by key: sorted chunks on the threads, then merged pairwise.
+void sort_pairs_host(std::vector<std::pair<uint64_t, uint32_t>> &v, int threads)
+{
+    auto less = [](const std::pair<uint64_t, uint32_t> &a, const std::pair<uint64_t, uint32_t> &b) { return a.first < b.first; };
+    size_t parts = 1;
+    while ((int)(parts * 2) <= threads && v.size() / (parts * 2) >= 65536) parts *= 2;
+    auto edge = [&](size_t k) { return v.size() * k / parts; };
+    parallel_for((int)parts, parts, [&](uint64_t k, int) { std::stable_sort(v.begin() + edge(k), v.begin() + edge(k + 1), less); });
+    for (size_t w = 1; w < parts; w *= 2)
+        parallel_for((int)(parts / (2 * w)), parts / (2 * w), [&](uint64_t k, int) {
+            std::inplace_merge(v.begin() + edge(2 * w * k), v.begin() + edge(2 * w * k + w), v.begin() + edge(2 * w * (k + 1)), less);
+        });
+}
+
+int build_voxels_host(const och_voxel_params &P, int threads, uint32_t **out, uint32_t *n_out, uint32_t &root,
+                      VoxelStats &vs, const std::function<void(const char *)> &phase)
+{
+    const int depth = P.depth;
+    std::vector<uint64_t> keys;    // unique, ascending
+    std::vector<uint32_t> words;   // the ids, then each level's node ids
+    if (P.kind == OCH_VOXELS_LIST) {
+        const uint32_t *recs = static_cast<const uint32_t *>(P.data);
+        const size_t n = (size_t)P.n;
+        std::vector<std::pair<uint64_t, uint32_t>> kv(n);
+        const size_t chunk = 1 << 16;
+        parallel_for(threads, (n + chunk - 1) / chunk, [&](uint64_t c, int) {
+            for (size_t i = c * chunk; i < std::min(n, (c + 1) * chunk); ++i)
+                kv[i] = {voxel_key(recs[i * 4], recs[i * 4 + 1], recs[i * 4 + 2], depth), (uint32_t)i};
+        });
+        sort_pairs_host(kv, threads);
+        phase("sort");
+        for (size_t i = 0; i < n; ++i) {
+            const uint64_t key = kv[i].first;
+            if (key >> (3 * depth)) break;   // the records outside the tree, sorted last
+            if (i + 1 < n && kv[i + 1].first == key) continue;
+            const uint32_t id = recs[(size_t)kv[i].second * 4 + 3];
+            if (!id) continue;
+            keys.push_back(key);
+            words.push_back(id);
+        }
+    } else {
+        // key ranges in order, one at a time per thread, joined in order
+        const size_t n = (size_t)1 << (3 * depth), parts = (size_t)std::min<uint64_t>(n, 256);
+        const uint8_t *g8 = static_cast<const uint8_t *>(P.data);
+        const uint32_t *g32 = static_cast<const uint32_t *>(P.data);
+        std::vector<std::vector<uint64_t>> part_keys(parts);
+        std::vector<std::vector<uint32_t>> part_words(parts);
+        parallel_for(threads, parts, [&](uint64_t p, int) {
+            for (size_t i = n / parts * p; i < n / parts * (p + 1); ++i) {
+                const size_t x = compact3(i), y = compact3(i >> 1), z = compact3(i >> 2);
+                const size_t cell = (z << depth | y) << depth | x;
+                const uint32_t id = P.kind == OCH_VOXELS_GRID_U8 ? g8[cell] : g32[cell];
+                if (!id) continue;
+                part_keys[p].push_back(i);
+                part_words[p].push_back(id);
+            }
+        });
+        for (size_t p = 0; p < parts; ++p) {
+            keys.insert(keys.end(), part_keys[p].begin(), part_keys[p].end());
+            words.insert(words.end(), part_words[p].begin(), part_words[p].end());
+        }
+        phase("cells");
+    }
+    const size_t m = keys.size();
+    vs.solid = m;
+    uint64_t bins[kBins] = {0}, counts[kMaxVoxelDepth] = {0};
+    for (size_t i = 0; i < m; ++i) {
+        if (words[i] < 8) ++vs.hist[words[i]];
+        ++bins[level_bin(i == 0, i ? keys[i - 1] : 0, keys[i], depth)];
+    }
+    vs.tree_nodes = level_counts(bins, depth, counts);
+    phase("last wins");
+    if (m == 0) {
+        root = 0;
+        return renumber(nullptr, nullptr, 0, 0, depth, 1, out, n_out);
+    }
+    NodeStore ns;
+    if (!ns.init(voxel_capacity(P.capacity, vs.tree_nodes), true)) {
+        ns.release();
+        return OCH_E_NOMEM;
+    }
+    std::vector<uint64_t> pkeys;
+    std::vector<uint32_t> pwords, heads;
+    for (int h = 0; h < depth; ++h) {
+        const size_t n_in = keys.size(), n_rows = (size_t)counts[h];
+        heads.clear();
+        for (size_t i = 0; i < n_in; ++i)
+            if (i == 0 || (keys[i] >> 3) != (keys[i - 1] >> 3)) heads.push_back((uint32_t)i);
+        if (heads.size() != n_rows) {   // the level counts and the grouping are two views of one list
+            ns.release();
+            return OCH_E_INVALID;
+        }
+        pkeys.resize(n_rows);
+        pwords.resize(n_rows);
+        const size_t chunk = 4096;
+        parallel_for(threads, (n_rows + chunk - 1) / chunk, [&](uint64_t c, int) {
+            for (size_t r = c * chunk; r < std::min(n_rows, (c + 1) * chunk); ++r) {
+                uint32_t row[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                const size_t end = r + 1 < n_rows ? heads[r + 1] : n_in;
+                for (size_t i = heads[r]; i < end; ++i) row[keys[i] & 7u] = words[i];
+                pkeys[r] = keys[heads[r]] >> 3;
+                pwords[r] = ns.intern(row, h);
+            }
+        });
+        keys.swap(pkeys);
+        words.swap(pwords);
+    }
+    phase("levels");
+    root = words[0];
+    if (ns.full.load() || !root) {
+        ns.release();
+        return OCH_E_CAPACITY;
+    }
+    const int rs = renumber(ns.nodes, ns.level, std::min(ns.next.load(), ns.cap), root, depth, 1, out, n_out);
+    ns.release();
+    return rs;
 }
 
 }  // namespace
@@ -1117,6 +1665,55 @@ OCH_API int och_build_terrain(const och_terrain_params *params, och_host_pool *o
     for (int k = 0; k < 8; ++k) out->voxel_hist[k] = total.hist[k];
     out->solid_voxels = 0;
     for (int k = 1; k < 8; ++k) out->solid_voxels += total.hist[k];
+    out->build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    return OCH_OK;
+}
+
+OCH_API int och_build_voxels(const och_voxel_params *params, och_host_pool *out)
+{
+    if (!params || !out) return och::report(OCH_E_INVALID, "och_build_voxels: null argument");
+    const och_voxel_params &P = *params;
+    if (P.depth < 1 || P.depth > kMaxVoxelDepth)
+        return och::report(OCH_E_INVALID, "och_build_voxels: depth must be 1..21 (a Morton key of 3 * depth bits and the "
+                                          "out-of-range bit fill 64 bits)");
+    if (P.kind != OCH_VOXELS_LIST && P.kind != OCH_VOXELS_GRID_U8 && P.kind != OCH_VOXELS_GRID_U32)
+        return och::report(OCH_E_INVALID, "och_build_voxels: unknown kind");
+    if (P.kind == OCH_VOXELS_LIST && P.n >= (1ull << 31))
+        return och::report(OCH_E_INVALID, "och_build_voxels: a list holds fewer than 2^31 records");
+    if (P.kind != OCH_VOXELS_LIST && P.depth > (P.kind == OCH_VOXELS_GRID_U8 ? 10 : 9))
+        return och::report(OCH_E_INVALID, "och_build_voxels: a dense grid is limited to depth 10 (u8) / 9 (u32); pass a list");
+    if (!P.data && (P.kind != OCH_VOXELS_LIST || P.n))
+        return och::report(OCH_E_INVALID, "och_build_voxels: data is null");
+    if (P.on_device && !P.use_gpu)
+        return och::report(OCH_E_INVALID, "och_build_voxels: device data needs use_gpu = 1");
+    const auto t_start = std::chrono::steady_clock::now();
+    const bool trace = std::getenv("OCH_BUILD_TRACE") != nullptr;
+    auto phase = [&, t_last = t_start](const char *name) mutable {
+        if (!trace) return;
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "[och_build] voxels %-10s %8.4f s\n", name, std::chrono::duration<double>(now - t_last).count());
+        t_last = now;
+    };
+    std::memset(out, 0, sizeof *out);
+    VoxelStats vs;
+    uint32_t root = 0, n_out = 0;
+    uint32_t *nodes = nullptr;
+    const int st = P.use_gpu ? build_voxels_gpu(P, &nodes, &n_out, root, vs, trace)
+                             : build_voxels_host(P, P.threads > 0 ? P.threads : default_threads(), &nodes, &n_out, root, vs, phase);
+    if (st != OCH_OK)
+        return och::report(st, st == OCH_E_NODEV      ? "use_gpu: no HIP device"
+                               : st == OCH_E_CAPACITY ? "voxel builder: node capacity exhausted"
+                               : st == OCH_E_NOMEM    ? "voxel builder: allocation failed"
+                                                      : "voxel builder: HIP error");
+    phase(P.use_gpu ? "gpu, whole" : "renumber");
+    out->nodes = nodes;
+    out->n_nodes = n_out;
+    out->root = root ? 1 : 0;
+    out->depth = P.depth;
+    out->index_base = 1;
+    out->tree_nodes = vs.tree_nodes;
+    for (int k = 1; k < 8; ++k) out->voxel_hist[k] = vs.hist[k];
+    out->solid_voxels = vs.solid;
     out->build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     return OCH_OK;
 }
