@@ -301,7 +301,15 @@ OCH_API int och_gpu_render_dev(och_gpu_pool *pool, const och_camera *cam, uint32
 OCH_API int och_shard_rows(int height, int row_chunk, int n_shards);
 /* Several cameras of equal size in one launch (stereo / multi-view frames):
  * view v's slice goes to rgba_slices + v * och_shard_rows(H, row_chunk, n_shards) * W.
- * One launch keeps the GPU busy with other views while a view's slowest rays finish. */
+ * One launch keeps the GPU busy with other views while a view's slowest rays finish.
+ *
+ * Every camera render (this one, the bounce, codes, supersampled and lit forms,
+ * och_gpu_plan_views) runs a table of 8-byte tile descriptors, one per wave,
+ * which the pool makes on the first launch of a geometry (size, views, row
+ * chunk, shard, block, launch order, row deal) and keeps for the next frames;
+ * nothing in it depends on the cameras.  A descriptor holds columns, rows and
+ * slice rows in 16 bits: frames of more than 65 535 columns, rows or slice
+ * rows, or of 2^25 or more tiles, are refused with OCH_E_INVALID. */
 OCH_API int och_gpu_render_views_dev(och_gpu_pool *pool, const och_camera *cams, int n_views, uint32_t *rgba_slices,
                                      int row_chunk, int shard, int n_shards);
 /* Plan the launch order of frames of this geometry (size, views, sharding,

@@ -123,6 +123,8 @@ struct LaunchPlan {
     DevBuf<uint32_t> order;         // OCH_OPT_TILE_ORDER = 2
     DevBuf<uint32_t> order_xcd;     // OCH_OPT_TILE_ORDER = 3: grouped per XCD
     uint32_t blocks = 0;            // entries of the current plan (its launch's grid)
+    std::vector<uint32_t> h_order, h_order_xcd;   // the host's copies: tile tables bake them in (use_tiles)
+    uint64_t serial = 0;            // och_gpu_pool::plan_serial when the plan was made (tile-table keys)
     int64_t key[9] = {};
     // no plan until a new one is in place: later launches run in natural order
     void invalidate() { key[0] = -1; }
@@ -135,9 +137,21 @@ struct LaunchPlan {
 // made with
 struct SplitPlan {
     DevBuf<uint32_t> order, tasks;
+    std::vector<uint32_t> h_order, h_tasks;       // the host's copies (use_tiles)
     uint32_t n = 0, extra = 0, tiles = 0;
     int params[3] = {0, 0, 0};      // threshold, segments, level
     void invalidate() { n = extra = tiles = params[0] = params[1] = params[2] = 0; }
+};
+
+// One camera launch as the kernels run it (och::plan::tile_table), on the
+// device, and the launch it was made for.  The pool keeps the last few: a frame
+// loop's geometry, sharding and plan stay the same from frame to frame, so
+// after the first frame a launch only looks its table up.
+struct TileTable {
+    DevBuf<uint64_t> d;
+    uint32_t n = 0, grid = 0, block = 0;
+    int64_t key[12] = {};
+    uint64_t used = 0;              // och_gpu_pool::tile_clock at the last launch; 0 = empty
 };
 
 }  // namespace
@@ -203,12 +217,16 @@ struct och_gpu_pool {
     // [2] tiled trace batches (och_gpu_plan_batch_tiled)
     LaunchPlan plans[3];
     SplitPlan split;
+    uint64_t plan_serial = 0;                 // counts the plans made (och_gpu_plan_views)
+    TileTable tile_tables[8];                 // camera launches' tile tables (use_tiles), least recently used out first
+    uint64_t tile_clock = 0;
     // row deal (och_gpu_set_row_deal): for frames of deal_h rows in chunks of
     // deal_chunk over deal_n shards, chunk g belongs to a chosen shard instead
     // of g % n; slices hold deal_max chunks (the largest shard's, the rest padded)
     int deal_h = 0, deal_chunk = 0, deal_n = 0, deal_max = 0;
     uint64_t deal_serial = 0;                 // changes with every deal (plan keys)
     DevBuf<int32_t> d_chunk_map;              // [deal_n][deal_max] global chunk, -1 = padding
+    std::vector<int32_t> h_chunk_map;         // and the host's copy (tile tables)
     DevBuf<int32_t> d_owner;                  // [n_chunks] shard << 16 | local chunk
     std::vector<int32_t> deal_table;          // the chunk -> shard table as set
     bool deal_for(int H, int rc, int n) const { return deal_n && H == deal_h && rc == deal_chunk && n == deal_n; }
@@ -1087,12 +1105,18 @@ och::DevFrame make_frame(const och_gpu_pool *p, const och_camera *cams, int n_vi
 
 // A planning render: launch(sc) in natural order, sc.cost naming n_words words preset to
 // 0xFFFFFFFF that every launched workgroup overwrites with its duration; c receives them.
+// frame: the camera frame the launch renders (bounce: by the config-5 kernel), for its tile table.
+int use_tiles(och_gpu_pool *p, const och::DevFrame &f, bool bounce, och::Schedule &sc);
+
 template <class Launch>
-int cost_render(och_gpu_pool *p, uint32_t *cost, uint32_t n_words, std::vector<uint32_t> &c, Launch launch)
+int cost_render(och_gpu_pool *p, uint32_t *cost, uint32_t n_words, std::vector<uint32_t> &c, Launch launch,
+                const och::DevFrame *frame = nullptr, bool bounce = false)
 {
     och::Schedule sc = p->schedule();
     sc.tile_order = 0;
     sc.cost = cost;
+    if (frame)
+        if (int ts = use_tiles(p, *frame, bounce, sc)) return ts;
     OCH_HIP(hipMemsetAsync(cost, 0xFF, (size_t)n_words * 4, p->stream()));
     OCH_HIP(launch(sc));
     c.resize(n_words);
@@ -1569,6 +1593,67 @@ void use_plan(const och_gpu_pool *p, const och::DevFrame &f, bool bounce, bool s
     }
 }
 
+// The tile table of frame f's launch under sc (after use_plan): the pool's
+// table of this geometry, block size and launch order, made and uploaded when
+// the pool holds none.  Nothing in it depends on the cameras.  bounce: the
+// config-5 kernel's launch (its own block size).
+int use_tiles(och_gpu_pool *p, const och::DevFrame &f, bool bounce, och::Schedule &sc)
+{
+    const int block = bounce ? std::max(och::kBounceBlock, sc.block) : sc.block;
+    const LaunchPlan &plan = p->plans[bounce ? 1 : 0];
+    // the launch order: the split plan's, the plan's (whole, or grouped per XCD), or none
+    const std::vector<uint32_t> *order = nullptr, *tasks = nullptr;
+    int mode = sc.tile_order == 1 ? 1 : 0;
+    if (sc.split_tasks) {
+        order = &p->split.h_order;
+        tasks = &p->split.h_tasks;
+        mode = 4;
+    } else if (sc.order) {
+        mode = p->opt_tile_order == 3 ? 3 : 2;
+        order = mode == 3 ? &plan.h_order_xcd : &plan.h_order;
+    }
+    const int64_t key[12] = {f.cams[0].width, f.cams[0].height, f.n_views, f.row_chunk, f.shard, f.n_shards,
+                             f.slice_rows, block, mode, f.chunk_map ? (int64_t)p->deal_serial : 0,
+                             order ? (int64_t)plan.serial : 0, bounce ? 1 : 0};
+    TileTable *t = nullptr, *oldest = &p->tile_tables[0];
+    for (TileTable &c : p->tile_tables) {
+        if (c.used && std::memcmp(c.key, key, sizeof key) == 0) t = &c;
+        if (c.used < oldest->used) oldest = &c;
+    }
+    if (!t) {
+        och::plan::TileGeometry g = {f.cams[0].width, f.cams[0].height, f.n_views, f.row_chunk, f.shard, f.n_shards,
+                                     f.slice_rows, block, mode == 1 ? 1 : 0, nullptr};
+        if (f.chunk_map) g.chunk_map = p->h_chunk_map.data() + (size_t)f.shard * p->deal_max;
+        std::vector<uint64_t> table;
+        uint32_t grid = 0;
+        // a plan of another grid (stale, or for another block size) is not this launch's: natural order
+        const uint32_t blocks = (uint32_t)(((uint64_t)f.n_views * ((f.cams[0].width + 7) / 8) * ((f.slice_rows + 7) / 8) * 64 +
+                                            block - 1) / block);
+        if (order && mode != 4 && order->size() != blocks) order = nullptr;
+        const char *why = "";
+        if (int st = och::plan::tile_table(g, order ? order->data() : nullptr, order ? (uint32_t)order->size() : 0u,
+                                           tasks ? tasks->data() : nullptr, tasks ? (uint32_t)tasks->size() : 0u, table,
+                                           grid, &why))
+            return fail(st, "tile table of a %d x %d frame, %d views: %s", g.width, g.height, g.n_views, why);
+        t = oldest;
+        if (t->used) {                          // launches in flight on other streams may read the table it replaces
+            t->used = 0;
+            if (int ds = och::pool_drain(p)) return ds;
+        }
+        OCH_HIP(t->d.upload(table));
+        t->n = (uint32_t)table.size();
+        t->grid = grid;
+        t->block = (uint32_t)block;
+        std::memcpy(t->key, key, sizeof key);
+    }
+    t->used = ++p->tile_clock;
+    sc.tiles = t->d.d;
+    sc.tiles_n = t->n;
+    sc.tiles_grid = t->grid;
+    sc.tiles_block = t->block;
+    return OCH_OK;
+}
+
 int render_views(och_gpu_pool *p, const och_camera *cams, int n_views, uint32_t *rgba_slices, int row_chunk, int shard,
                  int n_shards, bool bounce, uint8_t *code_slices = nullptr)
 {
@@ -1589,6 +1674,7 @@ int render_views(och_gpu_pool *p, const och_camera *cams, int n_views, uint32_t 
     och::Schedule sc = timed_schedule(p, ts);
     if (ts) return ts;
     use_plan(p, f, bounce, true, sc);
+    if (int us = use_tiles(p, f, bounce, sc)) return us;
     if (code_slices)
         OCH_HIP(och::launch_render_codes(p->dev(), f, sc, bounce, p->stream()));
     else if (bounce)
@@ -1615,7 +1701,12 @@ int plan_split(och_gpu_pool *p, const och::DevFrame &f, const std::vector<uint32
     OCH_HIP(d_push.reserve(push.size()));
     och::Schedule sc = p->schedule();
     sc.tile_order = 0;
-    hipError_t e = och::launch_render_push(p->dev(), f, sc, d_push.d, p->stream());
+    if (int us = use_tiles(p, f, false, sc)) return us;
+    // The counting render writes only the frame's pixels: rows past the height in
+    // the last chunk and padding chunks keep the cleared 0, a ray without a PUSH,
+    // so the plan does not depend on what the allocation held.
+    hipError_t e = hipMemsetAsync(d_push.d, 0, push.size() * 2, p->stream());
+    if (e == hipSuccess) e = och::launch_render_push(p->dev(), f, sc, d_push.d, p->stream());
     if (e == hipSuccess) e = hipMemcpyAsync(push.data(), d_push.d, push.size() * 2, hipMemcpyDeviceToHost, p->stream());
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream());
     (void)d_push.release();
@@ -1625,6 +1716,8 @@ int plan_split(och_gpu_pool *p, const och::DevFrame &f, const std::vector<uint32
     if (s.tiles == 0) return OCH_OK;
     OCH_HIP(sp.order.upload(s.order));
     OCH_HIP(sp.tasks.upload(s.tasks));
+    sp.h_order = s.order;
+    sp.h_tasks = s.tasks;
     sp.n = (uint32_t)s.order.size();
     sp.extra = s.extra;
     sp.tiles = s.tiles;
@@ -1663,7 +1756,7 @@ OCH_API int och_gpu_plan_views(och_gpu_pool *p, const och_camera *cams, int n_vi
         st = cost_render(p, cost, max_blocks, c, [&](const och::Schedule &sc) {
             return which ? och::launch_render_bounce(p->dev(), f, sc, p->stream())
                          : och::launch_render(p->dev(), f, sc, p->stream());
-        });
+        }, &f, which != 0);
         if (st != OCH_OK) return st;
         c.resize(std::find(c.begin(), c.end(), 0xFFFFFFFFu) - c.begin());   // launched blocks wrote a cost
         if (c.empty()) {
@@ -1679,6 +1772,9 @@ OCH_API int och_gpu_plan_views(och_gpu_pool *p, const och_camera *cams, int n_vi
         if (int ds = och::pool_drain(p)) return ds;   // launches in flight on other streams may read the old order
         OCH_HIP(plan.order.upload(order));
         OCH_HIP(plan.order_xcd.upload(grouped));
+        plan.h_order = order;
+        plan.h_order_xcd = grouped;
+        plan.serial = ++p->plan_serial;
         if (which == 0)
             if (int ss = plan_split(p, f, by_cost, order, c)) return ss;
         frame_key(p, f, which != 0, plan.key);
@@ -1731,6 +1827,7 @@ OCH_API int och_gpu_set_row_deal(och_gpu_pool *p, int height, int row_chunk, int
     if (se != hipSuccess) return fail(OCH_E_HIP, "row deal: hipDeviceSynchronize: %s", hipGetErrorString(se));
     p->d_chunk_map.swap(d_map);
     p->d_owner.swap(d_own);
+    p->h_chunk_map.swap(map);
     ++p->deal_serial;
     if (!chunk_shard) {                        // back to round-robin
         p->deal_n = p->deal_h = p->deal_chunk = p->deal_max = 0;
@@ -1775,7 +1872,7 @@ OCH_API int och_gpu_chunk_costs(och_gpu_pool *p, const och_camera *cams, int n_v
     // uninitialised scratch.
     std::vector<uint32_t> c;
     st = cost_render(p, reinterpret_cast<uint32_t *>(p->scratch.d + frame_bytes), n_blocks, c,
-                     [&](const och::Schedule &sc) { return och::launch_render(p->dev(), f, sc, p->stream()); });
+                     [&](const och::Schedule &sc) { return och::launch_render(p->dev(), f, sc, p->stream()); }, &f);
     if (st != OCH_OK) return st;
     for (uint32_t b = 0; b < n_blocks; ++b)
         if (c[b] == 0xFFFFFFFFu) return fail(OCH_E_INVALID, "chunk-cost render left workgroup %u untimed", b);
@@ -1859,6 +1956,7 @@ OCH_API int och_gpu_render_ssaa_views_dev(och_gpu_pool *p, const och_camera *cam
     och::Schedule sc = timed_schedule(p, ts);
     if (ts) return ts;
     use_plan(p, f, false, false, sc);
+    if (int us = use_tiles(p, f, false, sc)) return us;
     OCH_HIP(och::launch_render_ssaa(p->dev(), f, sc, s == 2 ? 1 : s == 4 ? 2 : 3, p->stream()));
     return timed_done(p, sc, true);
 }
@@ -1915,6 +2013,7 @@ int render_lit_views(och_gpu_pool *p, const och_camera *cams, int n_views, const
     och::Schedule sc = timed_schedule(p, ts);
     if (ts) return ts;
     use_plan(p, f, false, false, sc);            // the primary render's plan of this grid, never its split form
+    if (int us = use_tiles(p, f, false, sc)) return us;
     if (codes)
         OCH_HIP(och::launch_render_lit_codes(p->dev(), f, sc, *light, codes, p->stream()));
     else
@@ -2020,6 +2119,7 @@ OCH_API int och_gpu_render_lit_ssaa_views_dev(och_gpu_pool *p, const och_camera 
     och::Schedule sc = timed_schedule(p, ts);
     if (ts) return ts;
     use_plan(p, f, false, false, sc);
+    if (int us = use_tiles(p, f, false, sc)) return us;
     OCH_HIP(och::launch_render_lit_ssaa(p->dev(), f, sc, *light, s == 2 ? 1 : s == 4 ? 2 : 3, p->stream()));
     return timed_done(p, sc, true);
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/och_gpu.h"
+#include "och_tiles.h"
 
 namespace och {
 
@@ -166,7 +167,15 @@ struct Schedule {
     uint32_t split_extra;
     hipEvent_t ev_start;    // optional: recorded by the traversal kernel's own dispatch (hipExtLaunchKernel)
     hipEvent_t ev_stop;
+    // Camera launches: the launch as a table of tile descriptors (plan::tile_table),
+    // tiles_n entries for tiles_grid workgroups of tiles_block threads.  The launch
+    // order (order, tile_order, a split plan's order) is baked into it; camera
+    // launches read neither order nor order_n.  Required: a camera launch
+    // without a table of its block size fails.
+    const uint64_t *tiles;
+    uint32_t tiles_n, tiles_grid, tiles_block;
 };
+
 
 hipError_t launch_trace_batch(const DevPool &p, const float *origin, int origin_stride, const float *dirs,
                               uint32_t n, int32_t *hit_dir, uint32_t *hit_voxel, uint32_t *hit_time,

@@ -670,7 +670,7 @@ __device__ __forceinline__ void bounce_ray(const float *o, const float *d, const
 // Rays from arrays: shared (stride 0) or per-ray (stride 3) origin, AoS float3 dirs.
 struct ArraySource {
     static constexpr bool kProvenMiss = false;    // no camera_proven_miss before setup
-    static constexpr bool kSplittable = false;    // split plans come from och_gpu_plan_views (camera rays)
+    static constexpr bool kTileTable = false;
     const float *origin;
     const float *dirs;
     int origin_stride;
@@ -801,8 +801,8 @@ __device__ __forceinline__ void camera_ray(const och_camera &C, int col, int row
     camera_ray_from(ru, rv, rw, d);
 }
 
-// Pixel tile of one wave: kTileW x kTileH = 64 pixels.
-constexpr uint32_t kTileW = 8, kTileH = 64 / kTileW;
+// Pixel tile of one wave: kTileW columns x 64 / kTileW rows = 64 pixels.
+constexpr uint32_t kTileW = 8;
 
 // Division by a launch constant: n / d = (mulhi(n, m) + n) >> s for every
 // 32-bit n, with m, s from the host (round-up multiplier; checked against
@@ -833,7 +833,7 @@ struct FastDiv {
 // of a wave runs on the scalar unit.
 struct TiledArraySource {
     static constexpr bool kProvenMiss = false;
-    static constexpr bool kSplittable = false;
+    static constexpr bool kTileTable = false;
     const float *origin;
     const float *dirs;
     int origin_stride;
@@ -864,19 +864,27 @@ struct TiledArraySource {
 };
 
 // Camera rays of one shard's slice for up to kMaxViews cameras of equal size,
-// enumerated view after view, 8x8 pixel tile after tile, so a wave's 64 rays
-// are one tile of one view (ray i -> tile i / 64, pixel i % 64).  Tiles run
-// row-major (order 0) or in 64x64-pixel supertiles of 8x8 tiles (order 1),
-// which the grid kernel hands to one XCD as a unit (see xcd_block).  The
-// output token is view * slice_pixels + slice pixel.
+// one 8x8 pixel tile of one view per wave.  Which tile a wave of the launch
+// walks is not computed here: the host lays the launch out as a table of tile
+// descriptors, one per wave in launch order (och::plan::tile_table in
+// och_api.cpp: row-major tiles, supertiles grouped per XCD, a planned order,
+// all baked in), which depends on the frame's geometry and the launch order
+// but never on the cameras.  The output token is view * slice_pixels + slice
+// pixel.
+//
+// A descriptor (och_internal.h kTile*): word 0 = first column | view << 16 |
+// flags, word 1 = lane 0's frame row | its slice row << 16.
 struct CameraSource {
     static constexpr bool kProvenMiss = true;     // get_wave_culled runs camera_proven_miss when P.cam_cull
-    static constexpr bool kSplittable = true;     // heavy tiles' long rays split over lanes (kSplit launches)
+    static constexpr bool kTileTable = true;      // the launch's waves are the table's entries, in order
     och_camera cam[kMaxViews];
     CameraView view[kMaxViews];
-    int32_t n_views, row_chunk, shard, n_shards, slice_rows, width, height, order;
-    uint32_t tiles_x, supertiles_x, per_view, slice_pixels;
-    FastDiv by_per_view, by_tiles_x, by_supertiles_x, by_row_chunk;
+    int32_t row_chunk, shard, n_shards, slice_rows, width, height;
+    uint32_t slice_pixels, n_tiles;
+    const uint2 *tiles;                           // n_tiles descriptors
+    // Only tiles that straddle row chunks (kTileRows: a row chunk that is no
+    // multiple of the tile height, on more than one shard) map their rows here.
+    FastDiv by_row_chunk;
     // Row deal (och_gpu_set_row_deal): the global chunk of each of this
     // shard's local chunks, -1 past its last; null = round-robin.
     const int32_t *chunk_map;
@@ -887,32 +895,23 @@ struct CameraSource {
         const int g = chunk_map ? chunk_map[chunk] : chunk * n_shards + shard;
         return g < 0 ? height : g * row_chunk + within;
     }
-    __host__ __device__ __forceinline__ uint32_t count() const { return per_view * (uint32_t)n_views; }
-    // Tile of ray i.
-    __device__ __forceinline__ void tile_of(uint32_t i, uint32_t &view, uint32_t &tx, uint32_t &ty) const
-    {
-        view = by_per_view.div(i);
-        const uint32_t tile = (i - view * per_view) >> 6;
-        if (order == 1) {
-            const uint32_t st = tile >> 6, sub = tile & 63u, sy = by_supertiles_x.div(st);
-            tx = (st - sy * supertiles_x) * 8u + (sub & 7u);
-            ty = sy * 8u + (sub >> 3);
-        } else {
-            ty = by_tiles_x.div(tile);
-            tx = tile - ty * tiles_x;
-        }
-    }
+    __host__ __device__ __forceinline__ uint32_t count() const { return n_tiles * 64u; }
     // One wave's tile, or miss = true without a ray when camera_proven_miss
     // shows the ray ends as the MISS (cull: the launch may cull,
-    // OCH_OPT_CULL).  wave_base (a multiple of 64, wave-uniform) moves the tile
-    // arithmetic, divisions included, to the scalar unit.
+    // OCH_OPT_CULL).  wave_base = 64 * the wave's table entry (wave-uniform).
     __device__ __forceinline__ bool get_wave_culled(uint32_t wave_base, uint32_t lane, const DevPool &P, bool cull,
                                                     float *o, float *d, uint32_t &out, bool &miss) const
+    {
+        return get_tile_culled(tile(wave_base), lane, P, cull, o, d, out, miss);
+    }
+    // The same for a descriptor the caller holds.
+    __device__ __forceinline__ bool get_tile_culled(uint2 e, uint32_t lane, const DevPool &P, bool cull, float *o, float *d,
+                                                    uint32_t &out, bool &miss) const
     {
         uint32_t view;
         int col, srow, row;
         miss = false;
-        if (!locate_wave(wave_base, lane, view, col, srow, row)) return false;
+        if (!locate(e, lane, view, col, srow, row)) return false;
         const och_camera &C = cam[view];
         out = view * slice_pixels + (uint32_t)srow * (uint32_t)width + (uint32_t)col;
         float ru, rv, rw;
@@ -925,22 +924,39 @@ struct CameraSource {
         camera_ray_from(ru, rv, rw, d);
         return true;
     }
-    __device__ __forceinline__ bool locate_wave(uint32_t wave_base, uint32_t lane, uint32_t &view, int &col, int &srow,
-                                                int &row) const
+    // The descriptor of the wave's entry: one scalar load of two words.
+    __device__ __forceinline__ uint2 tile(uint32_t wave_base) const
     {
-        uint32_t tx, ty;
-        tile_of(__builtin_amdgcn_readfirstlane(wave_base), view, tx, ty);
-        view = __builtin_amdgcn_readfirstlane(view);
-        tx = __builtin_amdgcn_readfirstlane(tx);
-        ty = __builtin_amdgcn_readfirstlane(ty);
-        col = (int)(tx * kTileW + lane % kTileW);
-        const int srow0 = (int)(ty * kTileH);
-        srow = srow0 + (int)(lane / kTileW);
+        // through the constant address space: nothing writes the table while a
+        // launch runs, which the compiler cannot see behind a struct member
+#if defined(__HIP_DEVICE_COMPILE__)
+        typedef const __attribute__((address_space(4))) uint32_t *table_ptr;
+#else
+        typedef const uint32_t *table_ptr;
+#endif
+        const table_ptr w = (table_ptr)(uintptr_t)tiles + 2u * __builtin_amdgcn_readfirstlane(wave_base >> 6);
+        const uint2 e = make_uint2(w[0], w[1]);
+        return make_uint2(__builtin_amdgcn_readfirstlane(e.x), __builtin_amdgcn_readfirstlane(e.y));
+    }
+    // The supersampled kernels' output word of this lane's sample, s = 1 << log2_s
+    // samples a side: view * (W / s) * (H / s) + (Y / s) * (W / s) + X / s.
+    __device__ __forceinline__ uint32_t sample_word(uint32_t wave_base, uint32_t lane, int log2_s) const
+    {
+        const uint2 e = tile(wave_base);
+        const uint32_t w = (uint32_t)width >> log2_s, h = (uint32_t)height >> log2_s;
+        const uint32_t x = (e.x & 0xFFFFu) + lane % kTileW, y = (e.y >> 16) + lane / kTileW;
+        return (((e.x >> 16) & 15u) * h + (y >> log2_s)) * w + (x >> log2_s);
+    }
+    __device__ __forceinline__ bool locate(uint2 e, uint32_t lane, uint32_t &view, int &col, int &srow, int &row) const
+    {
+        if (e.x & kTileEmpty) return false;                 // a padding wave: no pixel of the frame
+        view = (e.x >> 16) & 15u;
+        col = (int)((e.x & 0xFFFFu) + lane % kTileW);
+        srow = (int)((e.y >> 16) + lane / kTileW);
+        row = (int)((e.y & 0xFFFFu) + lane / kTileW);
+        if (e.x & kTileInside) return true;                 // all 64 pixels lie in the frame
         if (col >= width || srow >= slice_rows) return false;
-        if (row_chunk % (int)kTileH == 0) {                // the tile lies inside one row chunk
-            const int chunk = __builtin_amdgcn_readfirstlane((int)by_row_chunk.div((uint32_t)srow0));
-            row = global_row(chunk, srow - chunk * row_chunk);
-        } else {
+        if (e.x & kTileRows) {
             const int chunk = (int)by_row_chunk.div((uint32_t)srow);
             row = global_row(chunk, srow - chunk * row_chunk);
         }
@@ -1098,7 +1114,8 @@ __device__ __forceinline__ void stamp(uint64_t *stamps, uint32_t cap, uint64_t t
 
 // A heavy tile's rays, the long ones walked by S lanes each (kSplit launches,
 // OCH_OPT_SPLIT).  The workgroup is one wave of lane tasks from
-// the plan's task table (och_api.cpp plan_split): word 0 the tile, then per
+// the plan's task table (och_api.cpp plan_split): word 0 the tile (for the host:
+// the wave's table entry names the descriptor, och_tiles.h kTileSplit), then per
 // lane pixel | seg << 6 | log2(S) << 10, or ~0 for an idle lane.  A lane walks
 // its ray's whole walk above the split level but enters only the present
 // split-level cells (segments) whose ordinal is seg modulo S (S = 1: all, the
@@ -1109,12 +1126,13 @@ __device__ __forceinline__ void stamp(uint64_t *stamps, uint32_t cap, uint64_t t
 // min of ordinal << 6 | lane); the winning lane stores its record, or, with no
 // HIT, the ray's segment-0 lane stores the MISS.
 template <class Src, class Sink, int kPacked>
-__device__ __forceinline__ void split_tile(const DevPool &P, const Src &S, const Sink &K, uint32_t ent,
+__device__ __forceinline__ void split_tile(const DevPool &P, const Src &S, const Sink &K, uint2 ent,
                                            const uint32_t *__restrict__ tasks, uint32_t level, uint32_t *lds_stack)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t *w = tasks + (size_t)(ent & 0x7FFFFFFFu) * 65u;
-    const uint32_t tile = __builtin_amdgcn_readfirstlane(w[0]);
+    // ent: the wave's table entry, word 0 its task row, word 1 the entry that holds its tile
+    const uint32_t *w = tasks + (size_t)(ent.x & 0x7FFFFFFFu) * 65u;
+    const uint32_t tile = ent.y;
     const uint32_t task = w[1u + lane];
     const uint32_t pix = task & 63u, seg = (task >> 6) & 15u, log2s = (task >> 10) & 7u;
     const uint32_t stack = stack_column(lds_stack, P.depth);
@@ -1149,51 +1167,58 @@ __device__ __forceinline__ void split_tile(const DevPool &P, const Src &S, const
     }
 }
 
-// Workgroups are dealt round-robin over the 8 XCDs (blocks b, b + 8, ... share
-// one XCD and its L2).  Remap so each XCD receives runs of `group`
-// consecutive logical blocks -- one supertile of neighbouring rays, which walk
-// the same DAG nodes -- instead of every eighth block.  A bijection on the
-// grid; placement only changes speed, never results.
-__device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t nb, uint32_t group)
-{
-    if (group == 0) return b;
-    const uint32_t span = 8u * group, full = nb - nb % span;
-    if (b >= full) return b;
-    const uint32_t x = b & 7u, s = b >> 3;
-    return ((s / group) * 8u + x) * group + s % group;
-}
-
 // order: optional block permutation (a cost-planned launch order: the
 // most expensive workgroups of the planning frame first, so the frame does not
-// end on a few late grazing tiles); cost: optional per-block duration in
+// end on a few late grazing tiles) of sources without a tile table; a camera
+// launch's order is its table's (CameraSource).  cost: optional per-block duration in
 // shader clocks (the planning launch).  Placement only: results are the same.
 // The traversal kernels are capped at 80 SGPRs: above 80 a SIMD admits 7 waves, not 8
 // (MI355X_MICROARCH.md, residency; the compiler's occupancy note says 8 there), and 8
 // give +5 % sustained.  tools/isa_check.py check 4 holds every
 // traversal kernel to 8 waves per SIMD.
-// kSplit: order entries with bit 31 set are split waves (split_tile): their
+// kSplit: table entries with bit 31 set are split waves (split_tile): their
 // task table row, split_level the split's level.
-template <class Src, class Sink, int kPacked, bool kCount, bool kSplit>
-__global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_grid(DevPool P, Src S, Sink K, uint32_t xcd_group, const uint32_t *__restrict__ order,
+// kDiag: the launch has a cost or a stamp buffer (planning and diagnostic
+// launches); a frame loop's launches run the instantiation without either,
+// whose waves neither load nor test the two pointers.
+template <class Src, class Sink, int kPacked, bool kCount, bool kSplit, bool kDiag>
+__global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_grid(DevPool P, Src S, Sink K, const uint32_t *__restrict__ order,
                              uint32_t *__restrict__ cost, uint64_t *stamps, uint32_t stamp_cap,
                              const uint32_t *__restrict__ split_tasks, uint32_t split_level)
 {
     extern __shared__ uint32_t lds_stack[];
+    if constexpr (!kDiag) {
+        cost = nullptr;
+        stamps = nullptr;
+    }
     const uint64_t t0 = stamps ? realtime() : 0;
     const uint64_t c0 = cost ? __builtin_amdgcn_s_memtime() : 0;
-    const uint32_t blk = order ? order[blockIdx.x] : xcd_block(blockIdx.x, gridDim.x, xcd_group);
-    if (kSplit && (blk >> 31)) {                    // a split wave (wave-uniform)
-        split_tile<Src, Sink, kPacked>(P, S, K, blk, split_tasks, split_level, lds_stack);
-        if (stamps) stamp(stamps, stamp_cap, t0, 64);
-        return;
-    }
+    // a tile table holds the launch's order: its blocks run as they come
+    // (a planning launch, the only one with cost, is in natural order)
+    uint32_t blk = blockIdx.x;
+    if constexpr (!Src::kTileTable) blk = order ? order[blockIdx.x] : blockIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave_base = blk * blockDim.x + (threadIdx.x & ~63u);
+    // a split launch's workgroups are one wave each (launch_as)
+    const uint32_t wave_base = kSplit ? blk * 64u : blk * blockDim.x + (threadIdx.x & ~63u);
     float o[3], d[3];
     uint32_t out;
-    bool miss;
-    if (wave_base + lane < S.count() &&
-        S.get_wave_culled(wave_base, lane, P, kCount ? P.cull == 2 : P.cull != 0, o, d, out, miss)) {
+    bool miss, have;
+    if constexpr (Src::kTileTable) {
+        // the launch covers whole workgroups of the table (launch_as): no bound to test
+        const uint2 ent = S.tile(wave_base);
+        if constexpr (kSplit) {
+            if (ent.x >> 31) {                      // a split wave (wave-uniform)
+                split_tile<Src, Sink, kPacked>(P, S, K, ent, split_tasks, split_level, lds_stack);
+                if (stamps) stamp(stamps, stamp_cap, t0, 64);
+                return;
+            }
+        }
+        have = S.get_tile_culled(ent, lane, P, kCount ? P.cull == 2 : P.cull != 0, o, d, out, miss);
+    } else {
+        have = wave_base + lane < S.count() &&
+               S.get_wave_culled(wave_base, lane, P, kCount ? P.cull == 2 : P.cull != 0, o, d, out, miss);
+    }
+    if (have) {
         if (miss) {                                 // proven before setup: the MISS record, 0 PUSHes
             K.put(out, Hit{OCH_EXIT, 0u, P.miss_bits, 0u});
         } else {
@@ -1260,14 +1285,13 @@ __device__ __forceinline__ uint32_t block_sum(uint32_t v)
 // multiples of 8, so an s x s block lies wholly inside the frame or wholly
 // outside it: lanes without a pixel add 0 to blocks nobody stores.
 template <int kPacked, int kLog2S>
-__global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_ssaa(DevPool P, CameraSource S, FrameSink K, uint32_t xcd_group,
-                                                                  const uint32_t *__restrict__ order, uint64_t *stamps,
+__global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_ssaa(DevPool P, CameraSource S, FrameSink K, uint64_t *stamps,
                                                                   uint32_t stamp_cap)
 {
     extern __shared__ uint32_t lds_stack[];
     constexpr uint32_t kS = 1u << kLog2S;
     const uint64_t t0 = stamps ? realtime() : 0;
-    const uint32_t blk = order ? order[blockIdx.x] : xcd_block(blockIdx.x, gridDim.x, xcd_group);
+    const uint32_t blk = blockIdx.x;                // the tile table holds the launch order
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave_base = blk * blockDim.x + (threadIdx.x & ~63u);
     float o[3], d[3];
@@ -1275,10 +1299,7 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_ssaa(DevPool P, Cam
     bool miss;
     if (wave_base + lane < S.count() && S.get_wave_culled(wave_base, lane, P, P.cull != 0, o, d, out, miss)) {
         // this sample's output word: view * W * H + Y * W + X
-        uint32_t view, tx, ty;
-        S.tile_of(__builtin_amdgcn_readfirstlane(wave_base), view, tx, ty);
-        const uint32_t w = (uint32_t)S.width >> kLog2S, h = (uint32_t)S.height >> kLog2S;
-        word = (view * h + ((ty * kTileH + lane / kTileW) >> kLog2S)) * w + ((tx * kTileW + lane % kTileW) >> kLog2S);
+        word = S.sample_word(wave_base, lane, kLog2S);
         if (miss) {                                 // proven before setup: the sky
             colour = pixel_colour(Hit{OCH_EXIT, 0u, P.miss_bits, 0u}, K.palette, K.n_voxels);
         } else {
@@ -1325,7 +1346,8 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_bounce(DevPool P, S
     extern __shared__ uint32_t lds_stack[];
     __shared__ uint32_t wave_count[16];
     const uint64_t c0 = cost ? __builtin_amdgcn_s_memtime() : 0;
-    const uint32_t blk = order ? order[blockIdx.x] : blockIdx.x;
+    uint32_t blk = blockIdx.x;                      // a tile table holds the launch order
+    if constexpr (!Src::kTileTable) blk = order ? order[blockIdx.x] : blockIdx.x;
     const uint64_t t0 = stamps ? realtime() : 0;
     const uint32_t stack = stack_column(lds_stack, P.depth);
     uint32_t *queue = lds_stack;
@@ -1518,13 +1540,12 @@ constexpr uint32_t kLitNoPixel = 0xFFu;        // state of a slot without a hit 
 // the lanes without a hit left idle.  Both forms write the same bytes.
 template <class Sink, int kPacked>
 __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_lit(DevPool P, CameraSource S, Sink K, och_light L, int compact,
-                                                                 uint32_t xcd_group, const uint32_t *__restrict__ order,
                                                                  uint64_t *stamps, uint32_t stamp_cap)
 {
     extern __shared__ uint32_t lds_stack[];
     __shared__ uint32_t wave_count[16];
     const uint64_t t0 = stamps ? realtime() : 0;
-    const uint32_t blk = order ? order[blockIdx.x] : xcd_block(blockIdx.x, gridDim.x, xcd_group);
+    const uint32_t blk = blockIdx.x;                // the tile table holds the launch order
     const uint32_t nb = blockDim.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t stack = stack_column(lds_stack, P.depth);
     // the queue starts where the stacks' word plane ends (launch_lit sizes both)
@@ -1624,14 +1645,13 @@ constexpr uint32_t kLitSsaaQueueWords = 4;
 // compact as in k_trace_lit; both forms write the same bytes.
 template <int kPacked, int kLog2S>
 __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_lit_ssaa(DevPool P, CameraSource S, FrameSink K, och_light L, int compact,
-                                                                      uint32_t xcd_group, const uint32_t *__restrict__ order,
                                                                       uint64_t *stamps, uint32_t stamp_cap)
 {
     extern __shared__ uint32_t lds_stack[];
     __shared__ uint32_t wave_count[16];
     constexpr uint32_t kS = 1u << kLog2S;
     const uint64_t t0 = stamps ? realtime() : 0;
-    const uint32_t blk = order ? order[blockIdx.x] : xcd_block(blockIdx.x, gridDim.x, xcd_group);
+    const uint32_t blk = blockIdx.x;                // the tile table holds the launch order
     const uint32_t nb = blockDim.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t stack = stack_column(lds_stack, P.depth);
     // the queue starts where the stacks' word plane ends (launch_lit_ssaa_as sizes both)
@@ -1646,10 +1666,7 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_lit_ssaa(DevPool P,
     bool miss;
     if (wave_base + lane < S.count() && S.get_wave_culled(wave_base, lane, P, P.cull != 0, o, d, out, miss)) {
         // this sample's output word: view * W * H + Y * W + X
-        uint32_t view, tx, ty;
-        S.tile_of(__builtin_amdgcn_readfirstlane(wave_base), view, tx, ty);
-        const uint32_t w = (uint32_t)S.width >> kLog2S, h = (uint32_t)S.height >> kLog2S;
-        word = (view * h + ((ty * kTileH + lane / kTileW) >> kLog2S)) * w + ((tx * kTileW + lane % kTileW) >> kLog2S);
+        word = S.sample_word(wave_base, lane, kLog2S);
         if (miss) {                                 // proven before setup: the sky
             colour = pixel_colour(Hit{OCH_EXIT, 0u, P.miss_bits, 0u}, K.palette, K.n_voxels);
         } else {
@@ -1880,50 +1897,79 @@ size_t stack_bytes(int depth, int block)
     return 4 * (c > kStaticLds ? c : kStaticLds) + 4 * e;
 }
 
-template <class Src, class Sink, int kPacked, bool kCount>
-hipError_t launch_as(const DevPool &p, const Src &s, const Sink &k, uint32_t n, const Schedule &sc, hipStream_t stream,
-                     uint32_t supertile_rays)
+// A camera launch runs the schedule's tile table: one made for this block size,
+// whole workgroups of it (och_api.cpp use_tiles).
+bool tiles_fit(const Schedule &sc, int block)
 {
-    if (n == 0) return hipSuccess;
+    return sc.tiles && block > 0 && sc.tiles_block == (uint32_t)block &&
+           (uint64_t)sc.tiles_grid * ((uint32_t)block / 64u) <= sc.tiles_n;
+}
+
+template <class Src, class Sink, int kPacked, bool kCount>
+hipError_t launch_as(const DevPool &p, const Src &s, const Sink &k, uint32_t n, const Schedule &sc, hipStream_t stream)
+{
+    if (!Src::kTileTable && n == 0) return hipSuccess;     // a camera launch without its table is an error
     const int block = sc.block;
     const size_t lds = stack_bytes(p.depth, block);
-    const uint32_t xcd_group = supertile_rays >= (uint32_t)block ? supertile_rays / (uint32_t)block : 0u;
     const uint32_t grid = (n + (uint32_t)block - 1) / (uint32_t)block;
-    if constexpr (Src::kSplittable && kPacked && !kCount) {
-        // a split plan (och_api.cpp plan_split): this grid's workgroups, the
-        // heavy ones replaced by their parts; one wave per workgroup
-        if (sc.split_tasks && sc.order && block == 64 && sc.order_n == grid + sc.split_extra) {
-            OCH_LAUNCH_TIMED(sc, (k_trace_grid<Src, Sink, kPacked, kCount, true>), dim3(sc.order_n), dim3(block), lds,
-                             stream, p, s, k, 0u, sc.order, sc.cost, sc.stamps, sc.stamp_cap, sc.split_tasks,
-                             sc.split_level);
-            return hipGetLastError();
+    if constexpr (Src::kTileTable) {
+        // the table is the launch: its order, and with a split plan (och_api.cpp
+        // plan_split) the heavy workgroups replaced by their parts, one wave per
+        // workgroup.  Made for another block size it would index past its end.
+        if (!tiles_fit(sc, block)) return hipErrorInvalidValue;
+        const bool diag = sc.cost || sc.stamps;
+        if (sc.split_tasks) {
+            if constexpr (kPacked && !kCount) {
+                if (block != 64) return hipErrorInvalidValue;
+                if (diag)
+                    OCH_LAUNCH_TIMED(sc, (k_trace_grid<Src, Sink, kPacked, kCount, true, true>), dim3(sc.tiles_grid),
+                                     dim3(block), lds, stream, p, s, k, nullptr, sc.cost, sc.stamps, sc.stamp_cap,
+                                     sc.split_tasks, sc.split_level);
+                else
+                    OCH_LAUNCH_TIMED(sc, (k_trace_grid<Src, Sink, kPacked, kCount, true, false>), dim3(sc.tiles_grid),
+                                     dim3(block), lds, stream, p, s, k, nullptr, nullptr, nullptr, 0u, sc.split_tasks,
+                                     sc.split_level);
+                return hipGetLastError();
+            }
+            return hipErrorInvalidValue;            // a split table in a launch that cannot split
         }
+        if (diag)
+            OCH_LAUNCH_TIMED(sc, (k_trace_grid<Src, Sink, kPacked, kCount, false, true>), dim3(sc.tiles_grid), dim3(block),
+                             lds, stream, p, s, k, nullptr, sc.cost, sc.stamps, sc.stamp_cap, nullptr, 0u);
+        else
+            OCH_LAUNCH_TIMED(sc, (k_trace_grid<Src, Sink, kPacked, kCount, false, false>), dim3(sc.tiles_grid), dim3(block),
+                             lds, stream, p, s, k, nullptr, nullptr, nullptr, 0u, nullptr, 0u);
+        return hipGetLastError();
     }
     // a plan is a permutation of exactly this grid's workgroups; any other
     // (stale or for another block size) would index past it
-    OCH_LAUNCH_TIMED(sc, (k_trace_grid<Src, Sink, kPacked, kCount, false>), dim3(grid), dim3(block), lds, stream, p, s,
-                     k, xcd_group, sc.order_n == grid ? sc.order : nullptr, sc.cost, sc.stamps, sc.stamp_cap, nullptr,
+    OCH_LAUNCH_TIMED(sc, (k_trace_grid<Src, Sink, kPacked, kCount, false, true>), dim3(grid), dim3(block), lds, stream, p, s,
+                     k, sc.order_n == grid ? sc.order : nullptr, sc.cost, sc.stamps, sc.stamp_cap, nullptr,
                      0u);
     return hipGetLastError();
 }
 
 template <class Src, class Sink, bool kCount>
-hipError_t launch(const DevPool &p, const Src &s, const Sink &k, uint32_t n, const Schedule &sc, hipStream_t stream,
-                  uint32_t supertile_rays = 0)
+hipError_t launch(const DevPool &p, const Src &s, const Sink &k, uint32_t n, const Schedule &sc, hipStream_t stream)
 {
-    return p.packed ? launch_as<Src, Sink, 1, kCount>(p, s, k, n, sc, stream, supertile_rays)
-                    : launch_as<Src, Sink, 0, kCount>(p, s, k, n, sc, stream, supertile_rays);
+    return p.packed ? launch_as<Src, Sink, 1, kCount>(p, s, k, n, sc, stream)
+                    : launch_as<Src, Sink, 0, kCount>(p, s, k, n, sc, stream);
 }
 
 template <class Src, class Sink, bool kCount>
 hipError_t launch_bounce(const DevPool &p, const Src &s, const Sink &k, uint32_t n, const Schedule &sc, hipStream_t stream)
 {
-    if (n == 0) return hipSuccess;
+    if (!Src::kTileTable && n == 0) return hipSuccess;
     const int block = sc.block > kBounceBlock ? sc.block : kBounceBlock;
     const size_t queue = 8u * (size_t)block * sizeof(uint32_t);
     const size_t lds = stack_bytes(p.depth, block) > queue ? stack_bytes(p.depth, block) : queue;
-    const dim3 grid((n + block - 1) / block);
+    dim3 grid((n + block - 1) / block);
     const uint32_t *order = sc.order_n == grid.x ? sc.order : nullptr;   // a plan of exactly this grid
+    if constexpr (Src::kTileTable) {
+        if (!tiles_fit(sc, block) || sc.split_tasks) return hipErrorInvalidValue;
+        grid.x = sc.tiles_grid;
+        order = nullptr;
+    }
     if (p.packed)
         OCH_LAUNCH_TIMED(sc, (k_trace_bounce<Src, Sink, 1, kCount>), grid, dim3(block), lds, stream, p, s, k,
                          sc.bounce_compact, order, sc.cost, sc.stamps, sc.stamp_cap);
@@ -1949,23 +1995,16 @@ CameraSource camera_source(const DevPool &p, const DevFrame &f, const Schedule &
             V.pos_ok &= (o > 1.0F && o < 2.0F) ? 1 : 0;
         }
     }
-    src.n_views = f.n_views;
     src.row_chunk = f.row_chunk;
     src.shard = f.shard;
     src.n_shards = f.n_shards;
     src.slice_rows = f.slice_rows;
     src.width = f.cams[0].width;
     src.height = f.cams[0].height;
-    src.tiles_x = (uint32_t)(src.width + kTileW - 1) / kTileW;
-    src.order = sc.tile_order == 1 ? 1 : 0;       // 2 = row-major tiles in a planned launch order
-    const uint32_t tiles_y = (uint32_t)(f.slice_rows + kTileH - 1) / kTileH;
-    src.supertiles_x = (src.tiles_x + 7) / 8;
-    src.per_view = sc.tile_order == 1 ? src.supertiles_x * ((tiles_y + 7) / 8) * 64u * 64u : src.tiles_x * tiles_y * 64u;
     src.slice_pixels = (uint32_t)f.slice_rows * (uint32_t)src.width;
-    src.by_per_view.init(src.per_view);
-    src.by_tiles_x.init(src.tiles_x);
-    src.by_supertiles_x.init(src.supertiles_x);
     src.by_row_chunk.init((uint32_t)src.row_chunk);
+    src.tiles = reinterpret_cast<const uint2 *>(sc.tiles);
+    src.n_tiles = sc.tiles ? sc.tiles_n : 0u;
     src.chunk_map = f.chunk_map;
     return src;
 }
@@ -1977,11 +2016,11 @@ hipError_t occupancy_blocks_per_cu(int kind, int block, int depth, int *blocks)
     const size_t lds = stack_bytes(depth, block);
     switch (kind) {
     case 0:
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, k_trace_grid<CameraSource, FrameSink, 1, false, false>,
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks, k_trace_grid<CameraSource, FrameSink, 1, false, false, false>,
                                                             block, lds);
     case 2:
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks,
-                                                            k_trace_grid<ArraySource, HitSink<false>, 1, false, false>,
+                                                            k_trace_grid<ArraySource, HitSink<false>, 1, false, false, true>,
                                                             block, lds);
     default:
         return hipErrorInvalidValue;
@@ -2034,7 +2073,7 @@ hipError_t launch_render(const DevPool &p, const DevFrame &f, const Schedule &sc
     if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
     const CameraSource src = camera_source(p, f, sc);
     return launch<CameraSource, FrameSink, false>(p, src, FrameSink{f.out, f.palette, f.n_voxels}, src.count(), sc,
-                                                  stream, sc.tile_order == 1 ? 64u * 64u : 0u);
+                                                  stream);
 }
 
 namespace {
@@ -2043,14 +2082,11 @@ template <int kPacked, int kLog2S>
 hipError_t launch_ssaa_as(const DevPool &p, const CameraSource &s, const FrameSink &k, const Schedule &sc,
                           hipStream_t stream)
 {
-    const uint32_t block = (uint32_t)sc.block, n = s.count();
-    const uint32_t grid = (n + block - 1) / block;
-    const uint32_t xcd_group = sc.tile_order == 1 && 64u * 64u >= block ? 64u * 64u / block : 0u;
-    // a plan is a permutation of exactly this grid's workgroups (launch_as); a
-    // split plan never reaches this kernel (split_tile maps lanes to rays differently)
-    const uint32_t *order = sc.order_n == grid && !sc.split_tasks ? sc.order : nullptr;
-    OCH_LAUNCH_TIMED(sc, (k_trace_ssaa<kPacked, kLog2S>), dim3(grid), dim3(block), stack_bytes(p.depth, (int)block),
-                     stream, p, s, k, xcd_group, order, sc.stamps, sc.stamp_cap);
+    const uint32_t block = (uint32_t)sc.block;
+    // a split plan never reaches this kernel (split_tile maps lanes to rays differently)
+    if (!tiles_fit(sc, (int)block) || sc.split_tasks) return hipErrorInvalidValue;
+    OCH_LAUNCH_TIMED(sc, (k_trace_ssaa<kPacked, kLog2S>), dim3(sc.tiles_grid), dim3(block),
+                     stack_bytes(p.depth, (int)block), stream, p, s, k, sc.stamps, sc.stamp_cap);
     return hipGetLastError();
 }
 
@@ -2077,7 +2113,6 @@ hipError_t launch_render_ssaa(const DevPool &p, const DevFrame &f, const Schedul
     const int s = 1 << log2_s;
     if (f.cams[0].width % s || f.cams[0].height % s) return hipErrorInvalidValue;
     const CameraSource src = camera_source(p, f, sc);
-    if (src.count() == 0) return hipSuccess;
     const FrameSink k{f.out, f.palette, f.n_voxels};
     return p.packed ? launch_ssaa_layout<1>(p, src, k, sc, log2_s, stream)
                     : launch_ssaa_layout<0>(p, src, k, sc, log2_s, stream);
@@ -2091,15 +2126,12 @@ template <int kPacked, int kLog2S>
 hipError_t launch_lit_ssaa_as(const DevPool &p, const CameraSource &s, const FrameSink &k, const och_light &light,
                               const Schedule &sc, hipStream_t stream)
 {
-    const uint32_t block = (uint32_t)sc.block, n = s.count();
-    const uint32_t grid = (n + block - 1) / block;
+    const uint32_t block = (uint32_t)sc.block;
     const size_t lds = stack_bytes(p.depth, (int)block) + (size_t)kLitSsaaQueueWords * block * sizeof(uint32_t);
-    const uint32_t xcd_group = sc.tile_order == 1 && 64u * 64u >= block ? 64u * 64u / block : 0u;
-    // a plan is a permutation of exactly this grid's workgroups (launch_as); a
-    // split plan never reaches this kernel (split_tile maps lanes to rays differently)
-    const uint32_t *order = sc.order_n == grid && !sc.split_tasks ? sc.order : nullptr;
-    OCH_LAUNCH_TIMED(sc, (k_trace_lit_ssaa<kPacked, kLog2S>), dim3(grid), dim3(block), lds, stream, p, s, k, light,
-                     sc.bounce_compact, xcd_group, order, sc.stamps, sc.stamp_cap);
+    // a split plan never reaches this kernel (split_tile maps lanes to rays differently)
+    if (!tiles_fit(sc, (int)block) || sc.split_tasks) return hipErrorInvalidValue;
+    OCH_LAUNCH_TIMED(sc, (k_trace_lit_ssaa<kPacked, kLog2S>), dim3(sc.tiles_grid), dim3(block), lds, stream, p, s, k,
+                     light, sc.bounce_compact, sc.stamps, sc.stamp_cap);
     return hipGetLastError();
 }
 
@@ -2128,7 +2160,6 @@ hipError_t launch_render_lit_ssaa(const DevPool &p, const DevFrame &f, const Sch
     const int s = 1 << log2_s;
     if (f.cams[0].width % s || f.cams[0].height % s) return hipErrorInvalidValue;
     const CameraSource src = camera_source(p, f, sc);
-    if (src.count() == 0) return hipSuccess;
     const FrameSink k{f.out, f.palette, f.n_voxels};
     return p.packed ? launch_lit_ssaa_layout<1>(p, src, k, light, sc, log2_s, stream)
                     : launch_lit_ssaa_layout<0>(p, src, k, light, sc, log2_s, stream);
@@ -2159,20 +2190,17 @@ template <class Sink>
 hipError_t launch_lit(const DevPool &p, const CameraSource &s, const Sink &k, const och_light &light, const Schedule &sc,
                       hipStream_t stream)
 {
-    const uint32_t block = (uint32_t)sc.block, n = s.count();
-    if (n == 0) return hipSuccess;
-    const uint32_t grid = (n + block - 1) / block;
+    const uint32_t block = (uint32_t)sc.block;
     const size_t lds = stack_bytes(p.depth, (int)block) + (size_t)kLitQueueWords * block * sizeof(uint32_t);
-    const uint32_t xcd_group = sc.tile_order == 1 && 64u * 64u >= block ? 64u * 64u / block : 0u;
-    // a plan is a permutation of exactly this grid's workgroups (launch_as); a
-    // split plan never reaches this kernel (split_tile maps lanes to rays differently)
-    const uint32_t *order = sc.order_n == grid && !sc.split_tasks ? sc.order : nullptr;
+    // a split plan never reaches this kernel (split_tile maps lanes to rays differently)
+    if (!tiles_fit(sc, (int)block) || sc.split_tasks) return hipErrorInvalidValue;
+    const dim3 grid(sc.tiles_grid);
     if (p.packed)
-        OCH_LAUNCH_TIMED(sc, (k_trace_lit<Sink, 1>), dim3(grid), dim3(block), lds, stream, p, s, k, light,
-                         sc.bounce_compact, xcd_group, order, sc.stamps, sc.stamp_cap);
+        OCH_LAUNCH_TIMED(sc, (k_trace_lit<Sink, 1>), grid, dim3(block), lds, stream, p, s, k, light,
+                         sc.bounce_compact, sc.stamps, sc.stamp_cap);
     else
-        OCH_LAUNCH_TIMED(sc, (k_trace_lit<Sink, 0>), dim3(grid), dim3(block), lds, stream, p, s, k, light,
-                         sc.bounce_compact, xcd_group, order, sc.stamps, sc.stamp_cap);
+        OCH_LAUNCH_TIMED(sc, (k_trace_lit<Sink, 0>), grid, dim3(block), lds, stream, p, s, k, light,
+                         sc.bounce_compact, sc.stamps, sc.stamp_cap);
     return hipGetLastError();
 }
 
@@ -2203,8 +2231,7 @@ hipError_t launch_render_codes(const DevPool &p, const DevFrame &f, const Schedu
     const CameraSource src = camera_source(p, f, sc);
     const CodeSink k{f.codes, f.n_voxels};
     if (bounce) return launch_bounce<CameraSource, BounceCodeSink, false>(p, src, BounceCodeSink{k}, src.count(), sc, stream);
-    return launch<CameraSource, CodeSink, false>(p, src, k, src.count(), sc, stream,
-                                                 sc.tile_order == 1 ? 64u * 64u : 0u);
+    return launch<CameraSource, CodeSink, false>(p, src, k, src.count(), sc, stream);
 }
 
 hipError_t launch_shade_unshard(const uint8_t *gathered, uint32_t *frames, const uint32_t *table, int width, int height,
