@@ -1125,6 +1125,45 @@ int cost_render(och_gpu_pool *p, uint32_t *cost, uint32_t n_words, std::vector<u
     return OCH_OK;
 }
 
+extern "C" {   // the render path's pieces, defined with the entries below inside extern "C": declared so here
+och::Schedule timed_schedule(och_gpu_pool *p, int &st);
+int timed_done(och_gpu_pool *p, const och::Schedule &sc, bool launched);
+void use_plan(const och_gpu_pool *p, const och::DevFrame &f, bool bounce, bool split, och::Schedule &sc);
+}
+
+// One camera launch of frame f: the schedule with the launch's timing, the plan of
+// this geometry (split: its split form too), the tile table, the launch, the timing's
+// end.  CAMERA_LAUNCH's launch expression takes the schedule as `sc`; a failure names it.
+template <class Launch>
+int camera_launch(och_gpu_pool *p, const och::DevFrame &f, bool bounce, bool split, const char *what, Launch launch)
+{
+    int ts;
+    och::Schedule sc = timed_schedule(p, ts);
+    if (ts) return ts;
+    use_plan(p, f, bounce, split, sc);
+    if (int us = use_tiles(p, f, bounce, sc)) return us;
+    const hipError_t e = launch(sc);
+    if (e != hipSuccess) return fail(OCH_E_HIP, "%s: %s", what, hipGetErrorString(e));
+    return timed_done(p, sc, true);
+}
+#define CAMERA_LAUNCH(p, f, bounce, split, call) \
+    camera_launch(p, f, bounce, split, #call, [&](const och::Schedule &sc) { return call; })
+
+// A host form: render(scratch) into the pool's scratch (pixels words and `spare`
+// bytes), then the pixels to the caller's rgba, complete on return.
+template <class Render>
+int to_host(och_gpu_pool *p, size_t pixels, size_t spare, uint32_t *rgba, Render render)
+{
+    DeviceGuard g(p->device);
+    int st = ensure_scratch(p, pixels * 4 + spare);
+    if (st != OCH_OK) return st;
+    st = render(reinterpret_cast<uint32_t *>(p->scratch.d));
+    if (st != OCH_OK) return st;
+    OCH_HIP(hipMemcpyAsync(rgba, p->scratch.d, pixels * 4, hipMemcpyDeviceToHost, p->stream()));
+    OCH_HIP(hipStreamSynchronize(p->stream()));
+    return OCH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1654,34 +1693,103 @@ int use_tiles(och_gpu_pool *p, const och::DevFrame &f, bool bounce, och::Schedul
     return OCH_OK;
 }
 
+// `what` (code frames of some kind) needs the code table of a palette small enough for 1-byte codes.
+static int needs_code_palette(const och_gpu_pool *p, const char *what)
+{
+    if (p->n_voxels > OCH_CODE_MAX_VOXELS || !p->d_code_table.d)
+        return fail(OCH_E_INVALID, "%s need a palette (och_gpu_set_palette) of at most %d voxel ids", what,
+                    OCH_CODE_MAX_VOXELS);
+    return OCH_OK;
+}
+
+// The shape of a sharded frame: the views, the sharding triple, one size, a token per pixel.
+static int frame_args(const och_camera *cams, int n_views, int row_chunk, int shard, int n_shards)
+{
+    if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
+    if (row_chunk <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards)
+        return fail(OCH_E_INVALID, "bad sharding (%d, %d, %d)", row_chunk, shard, n_shards);
+    if (int vs = och::check_views(cams, n_views)) return vs;
+    if ((uint64_t)cams[0].width * cams[0].height * n_views >= (1ull << 32)) return fail(OCH_E_INVALID, "frame too large");
+    return OCH_OK;
+}
+
+// A frame loop's arguments: the window, its events, a frame per buffer.
+static int loop_args(int n_steps, int n_buffers, void *const *start_events, void *const *stop_events, uint32_t *const *frames)
+{
+    if (n_steps < 0 || n_buffers < 1) return fail(OCH_E_INVALID, "n_steps %d / n_buffers %d", n_steps, n_buffers);
+    if ((start_events == nullptr) != (stop_events == nullptr))
+        return fail(OCH_E_INVALID, "start_events and stop_events: both or neither");
+    for (int b = 0; b < n_buffers; ++b)
+        if (!frames[b]) return fail(OCH_E_INVALID, "frames[%d] is NULL", b);
+    return OCH_OK;
+}
+
+// What the three unshard entries refuse (table: the entry shades through the code table).
+static int unshard_args(const och_gpu_pool *p, const void *gathered, const uint32_t *frames, int width, int height,
+                        int row_chunk, int n_shards, int n_views, bool table)
+{
+    if (!p || !gathered || !frames || width <= 0 || height <= 0 || row_chunk <= 0 || n_shards <= 0 || n_views < 1)
+        return fail(OCH_E_INVALID, "bad unshard arguments");
+    if (table && !p->d_code_table.d)
+        return fail(OCH_E_INVALID, "no code table: set a palette of at most %d voxel ids", OCH_CODE_MAX_VOXELS);
+    return OCH_OK;
+}
+
+// The host forms' refusal before the staging buffer is sized; the device form checks again.
+static int host_capacity(size_t capacity_pixels, int width, int height, size_t &pixels)
+{
+    pixels = (size_t)width * (size_t)height;
+    if (capacity_pixels < pixels)
+        return fail(OCH_E_INVALID, "rgba holds %zu pixels, %d x %d need %zu", capacity_pixels, width, height, pixels);
+    return OCH_OK;
+}
+
 int render_views(och_gpu_pool *p, const och_camera *cams, int n_views, uint32_t *rgba_slices, int row_chunk, int shard,
                  int n_shards, bool bounce, uint8_t *code_slices = nullptr)
 {
     if (!p || !cams || (!rgba_slices && !code_slices)) return fail(OCH_E_INVALID, "NULL argument");
-    if (code_slices && (p->n_voxels > OCH_CODE_MAX_VOXELS || !p->d_code_table.d))
-        return fail(OCH_E_INVALID, "indexed-colour frames need a palette (och_gpu_set_palette) of at most %d voxel ids",
-                    OCH_CODE_MAX_VOXELS);
-    if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
-    if (row_chunk <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards)
-        return fail(OCH_E_INVALID, "bad sharding (%d, %d, %d)", row_chunk, shard, n_shards);
-    if (int vs = check_views(cams, n_views)) return vs;
-    if ((uint64_t)cams[0].width * cams[0].height * n_views >= (1ull << 32))
-        return fail(OCH_E_INVALID, "frame too large");
+    if (int cs = code_slices ? needs_code_palette(p, "indexed-colour frames") : OCH_OK) return cs;
+    if (int fs = frame_args(cams, n_views, row_chunk, shard, n_shards)) return fs;
     if (int rs = check_ready(p)) return rs;
     DeviceGuard g(p->device);
     const och::DevFrame f = make_frame(p, cams, n_views, rgba_slices, code_slices, row_chunk, shard, n_shards);
-    int ts;
-    och::Schedule sc = timed_schedule(p, ts);
-    if (ts) return ts;
-    use_plan(p, f, bounce, true, sc);
-    if (int us = use_tiles(p, f, bounce, sc)) return us;
-    if (code_slices)
-        OCH_HIP(och::launch_render_codes(p->dev(), f, sc, bounce, p->stream()));
-    else if (bounce)
-        OCH_HIP(och::launch_render_bounce(p->dev(), f, sc, p->stream()));
-    else
-        OCH_HIP(och::launch_render(p->dev(), f, sc, p->stream()));
-    return timed_done(p, sc, true);
+    if (code_slices) return CAMERA_LAUNCH(p, f, bounce, true, och::launch_render_codes(p->dev(), f, sc, bounce, p->stream()));
+    if (bounce) return CAMERA_LAUNCH(p, f, bounce, true, och::launch_render_bounce(p->dev(), f, sc, p->stream()));
+    return CAMERA_LAUNCH(p, f, bounce, true, och::launch_render(p->dev(), f, sc, p->stream()));
+}
+
+// What the four supersampled entries refuse of s, the views and the sample grid
+// (the host forms pass their one camera).
+static int ssaa_args(const och_camera *cams, int n_views, int s)
+{
+    if (s != 2 && s != 4 && s != 8) return fail(OCH_E_INVALID, "samples per axis %d: must be 2, 4 or 8", s);
+    if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
+    if (int vs = och::check_views(cams, n_views)) return vs;
+    if (cams[0].width % s || cams[0].height % s)
+        return fail(OCH_E_INVALID, "sample grid %d x %d is not a multiple of %d", cams[0].width, cams[0].height, s);
+    return OCH_OK;
+}
+
+// och_gpu_render_ssaa_views_dev (light null) and och_gpu_render_lit_ssaa_views_dev behind
+// their NULL and light checks.  Every refusal comes before anything is written or launched.
+static int render_ssaa_views(och_gpu_pool *p, const och_camera *cams, int n_views, const och_light *light, int s,
+                             uint32_t *rgba, size_t capacity_pixels)
+{
+    if (int as = ssaa_args(cams, n_views, s)) return as;
+    const int Ws = cams[0].width, Hs = cams[0].height;
+    if ((uint64_t)Ws * Hs * n_views >= (1ull << 32)) return fail(OCH_E_INVALID, "frame too large");
+    const size_t pixels = (size_t)n_views * (Ws / s) * (Hs / s);
+    if (capacity_pixels < pixels)
+        return fail(OCH_E_INVALID, "rgba holds %zu pixels, %d views of %d x %d need %zu", capacity_pixels, n_views, Ws / s,
+                    Hs / s, pixels);
+    if (int rs = check_ready(p)) return rs;
+    DeviceGuard g(p->device);
+    // the sample grid as the 1-sample render's whole frame: its plan, never the split form
+    const och::DevFrame f = make_frame(p, cams, n_views, rgba, nullptr, Hs, 0, 1);
+    if (light)
+        return CAMERA_LAUNCH(p, f, false, false,
+                             och::launch_render_lit_ssaa(p->dev(), f, sc, *light, s == 2 ? 1 : s == 4 ? 2 : 3, p->stream()));
+    return CAMERA_LAUNCH(p, f, false, false, och::launch_render_ssaa(p->dev(), f, sc, s == 2 ? 1 : s == 4 ? 2 : 3, p->stream()));
 }
 
 // The primary plan's split form (och::plan::split_order has the whole story):
@@ -1936,29 +2044,8 @@ OCH_API int och_gpu_render_ssaa_views_dev(och_gpu_pool *p, const och_camera *cam
                                           size_t capacity_pixels)
 {
     OCH_ENTRY();
-    // every refusal comes before anything is written or launched
     if (!p || !cams || !rgba) return fail(OCH_E_INVALID, "NULL argument");
-    if (s != 2 && s != 4 && s != 8) return fail(OCH_E_INVALID, "samples per axis %d: must be 2, 4 or 8", s);
-    if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
-    if (int vs = check_views(cams, n_views)) return vs;
-    const int Ws = cams[0].width, Hs = cams[0].height;
-    if (Ws % s || Hs % s) return fail(OCH_E_INVALID, "sample grid %d x %d is not a multiple of %d", Ws, Hs, s);
-    if ((uint64_t)Ws * Hs * n_views >= (1ull << 32)) return fail(OCH_E_INVALID, "frame too large");
-    const size_t pixels = (size_t)n_views * (Ws / s) * (Hs / s);
-    if (capacity_pixels < pixels)
-        return fail(OCH_E_INVALID, "rgba holds %zu pixels, %d views of %d x %d need %zu", capacity_pixels, n_views, Ws / s,
-                    Hs / s, pixels);
-    if (int rs = check_ready(p)) return rs;
-    DeviceGuard g(p->device);
-    // the sample grid as the 1-sample render's whole frame: its plan, never the split form
-    const och::DevFrame f = make_frame(p, cams, n_views, rgba, nullptr, Hs, 0, 1);
-    int ts;
-    och::Schedule sc = timed_schedule(p, ts);
-    if (ts) return ts;
-    use_plan(p, f, false, false, sc);
-    if (int us = use_tiles(p, f, false, sc)) return us;
-    OCH_HIP(och::launch_render_ssaa(p->dev(), f, sc, s == 2 ? 1 : s == 4 ? 2 : 3, p->stream()));
-    return timed_done(p, sc, true);
+    return render_ssaa_views(p, cams, n_views, nullptr, s, rgba, capacity_pixels);
 }
 
 OCH_API int och_light_check(const och_light *l)
@@ -1993,15 +2080,9 @@ int render_lit_views(och_gpu_pool *p, const och_camera *cams, int n_views, const
     // every refusal comes before anything is written or launched
     if (!p || !cams || !light || (!rgba && !masks && !codes)) return fail(OCH_E_INVALID, "NULL argument");
     if (int ls = och_light_check(light)) return ls;
-    if (codes && (p->n_voxels > OCH_CODE_MAX_VOXELS || !p->d_code_table.d))
-        return fail(OCH_E_INVALID, "lit codes need a palette (och_gpu_set_palette) of at most %d voxel ids",
-                    OCH_CODE_MAX_VOXELS);
-    if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
-    if (row_chunk <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards)
-        return fail(OCH_E_INVALID, "bad sharding (%d, %d, %d)", row_chunk, shard, n_shards);
-    if (int vs = och::check_views(cams, n_views)) return vs;
+    if (int cs = codes ? needs_code_palette(p, "lit codes") : OCH_OK) return cs;
+    if (int fs = frame_args(cams, n_views, row_chunk, shard, n_shards)) return fs;
     const int W = cams[0].width, H = cams[0].height;
-    if ((uint64_t)W * H * n_views >= (1ull << 32)) return fail(OCH_E_INVALID, "frame too large");
     const size_t pixels = (size_t)n_views * p->slice_rows(H, row_chunk, n_shards) * W;
     if (capacity_pixels < pixels)
         return fail(OCH_E_INVALID, "the buffer holds %zu pixels, %d slices of %d x %d need %zu", capacity_pixels, n_views,
@@ -2009,16 +2090,9 @@ int render_lit_views(och_gpu_pool *p, const och_camera *cams, int n_views, const
     if (int rs = check_ready(p)) return rs;
     DeviceGuard g(p->device);
     const och::DevFrame f = make_frame(p, cams, n_views, rgba, nullptr, row_chunk, shard, n_shards);
-    int ts;
-    och::Schedule sc = timed_schedule(p, ts);
-    if (ts) return ts;
-    use_plan(p, f, false, false, sc);            // the primary render's plan of this grid, never its split form
-    if (int us = use_tiles(p, f, false, sc)) return us;
-    if (codes)
-        OCH_HIP(och::launch_render_lit_codes(p->dev(), f, sc, *light, codes, p->stream()));
-    else
-        OCH_HIP(och::launch_render_lit(p->dev(), f, sc, *light, masks, p->stream()));
-    return timed_done(p, sc, true);
+    // the primary render's plan of this grid, never its split form
+    if (codes) return CAMERA_LAUNCH(p, f, false, false, och::launch_render_lit_codes(p->dev(), f, sc, *light, codes, p->stream()));
+    return CAMERA_LAUNCH(p, f, false, false, och::launch_render_lit(p->dev(), f, sc, *light, masks, p->stream()));
 }
 
 }  // namespace
@@ -2059,10 +2133,7 @@ OCH_API int och_gpu_shade_lit_unshard_views_dev(och_gpu_pool *p, const uint16_t 
 {
     OCH_ENTRY();
     if (int ls = och_light_check(light)) return ls;
-    if (!p || !gathered || !frames || width <= 0 || height <= 0 || row_chunk <= 0 || n_shards <= 0 || n_views < 1)
-        return fail(OCH_E_INVALID, "bad unshard arguments");
-    if (!p->d_code_table.d)
-        return fail(OCH_E_INVALID, "no code table: set a palette of at most %d voxel ids", OCH_CODE_MAX_VOXELS);
+    if (int as = unshard_args(p, gathered, frames, width, height, row_chunk, n_shards, n_views, true)) return as;
     DeviceGuard g(p->device);
     OCH_HIP(och::launch_shade_lit_unshard(gathered, frames, p->d_code_table.d, width, height, row_chunk, n_shards,
                                           p->slice_rows(height, row_chunk, n_shards), n_views,
@@ -2079,49 +2150,19 @@ OCH_API int och_gpu_render_lit(och_gpu_pool *p, const och_camera *cam, const och
     if (int ls = och_light_check(light)) return ls;
     if (int vs = och::check_views(cam, 1)) return vs;
     if (int rs = check_ready(p)) return rs;
-    // refused before the staging buffer is sized; the device form checks again
-    const size_t pixels = (size_t)cam->width * (size_t)cam->height;
-    if (capacity_pixels < pixels)
-        return fail(OCH_E_INVALID, "rgba holds %zu pixels, %d x %d need %zu", capacity_pixels, cam->width, cam->height,
-                    pixels);
-    DeviceGuard g(p->device);
-    int st = ensure_scratch(p, pixels * 4 + 4);
-    if (st != OCH_OK) return st;
-    st = och_gpu_render_lit_views_dev(p, cam, 1, light, reinterpret_cast<uint32_t *>(p->scratch.d), pixels, cam->height, 0, 1);
-    if (st != OCH_OK) return st;
-    OCH_HIP(hipMemcpyAsync(rgba, p->scratch.d, pixels * 4, hipMemcpyDeviceToHost, p->stream()));
-    OCH_HIP(hipStreamSynchronize(p->stream()));
-    return OCH_OK;
+    size_t pixels;
+    if (int cs = host_capacity(capacity_pixels, cam->width, cam->height, pixels)) return cs;
+    return to_host(p, pixels, 4, rgba,
+                   [&](uint32_t *o) { return och_gpu_render_lit_views_dev(p, cam, 1, light, o, pixels, cam->height, 0, 1); });
 }
 
 OCH_API int och_gpu_render_lit_ssaa_views_dev(och_gpu_pool *p, const och_camera *cams, int n_views, const och_light *light,
                                               int s, uint32_t *rgba, size_t capacity_pixels)
 {
     OCH_ENTRY();
-    // every refusal comes before anything is written or launched
     if (!p || !cams || !light || !rgba) return fail(OCH_E_INVALID, "NULL argument");
-    if (int ls = och_light_check(light)) return ls;
-    if (s != 2 && s != 4 && s != 8) return fail(OCH_E_INVALID, "samples per axis %d: must be 2, 4 or 8", s);
-    if (n_views < 1 || n_views > OCH_MAX_VIEWS) return fail(OCH_E_INVALID, "n_views %d outside 1..%d", n_views, OCH_MAX_VIEWS);
-    if (int vs = och::check_views(cams, n_views)) return vs;
-    const int Ws = cams[0].width, Hs = cams[0].height;
-    if (Ws % s || Hs % s) return fail(OCH_E_INVALID, "sample grid %d x %d is not a multiple of %d", Ws, Hs, s);
-    if ((uint64_t)Ws * Hs * n_views >= (1ull << 32)) return fail(OCH_E_INVALID, "frame too large");
-    const size_t pixels = (size_t)n_views * (Ws / s) * (Hs / s);
-    if (capacity_pixels < pixels)
-        return fail(OCH_E_INVALID, "rgba holds %zu pixels, %d views of %d x %d need %zu", capacity_pixels, n_views, Ws / s,
-                    Hs / s, pixels);
-    if (int rs = check_ready(p)) return rs;
-    DeviceGuard g(p->device);
-    // the sample grid as the 1-sample render's whole frame: its plan, never the split form
-    const och::DevFrame f = make_frame(p, cams, n_views, rgba, nullptr, Hs, 0, 1);
-    int ts;
-    och::Schedule sc = timed_schedule(p, ts);
-    if (ts) return ts;
-    use_plan(p, f, false, false, sc);
-    if (int us = use_tiles(p, f, false, sc)) return us;
-    OCH_HIP(och::launch_render_lit_ssaa(p->dev(), f, sc, *light, s == 2 ? 1 : s == 4 ? 2 : 3, p->stream()));
-    return timed_done(p, sc, true);
+    if (int ls = och_light_check(light)) return ls;      // before the s check
+    return render_ssaa_views(p, cams, n_views, light, s, rgba, capacity_pixels);
 }
 
 OCH_API int och_gpu_render_lit_ssaa(och_gpu_pool *p, const och_camera *cam, const och_light *light, int s, uint32_t *rgba,
@@ -2130,24 +2171,12 @@ OCH_API int och_gpu_render_lit_ssaa(och_gpu_pool *p, const och_camera *cam, cons
     OCH_ENTRY();
     if (!p || !cam || !light || !rgba) return fail(OCH_E_INVALID, "NULL argument");
     if (int ls = och_light_check(light)) return ls;
-    if (s != 2 && s != 4 && s != 8) return fail(OCH_E_INVALID, "samples per axis %d: must be 2, 4 or 8", s);
-    if (int vs = och::check_views(cam, 1)) return vs;
-    if (cam->width % s || cam->height % s)
-        return fail(OCH_E_INVALID, "sample grid %d x %d is not a multiple of %d", cam->width, cam->height, s);
+    if (int as = ssaa_args(cam, 1, s)) return as;
     if (int rs = check_ready(p)) return rs;
-    // refused before the staging buffer is sized; the device form checks again
-    const size_t pixels = (size_t)(cam->width / s) * (size_t)(cam->height / s);
-    if (capacity_pixels < pixels)
-        return fail(OCH_E_INVALID, "rgba holds %zu pixels, %d x %d need %zu", capacity_pixels, cam->width / s,
-                    cam->height / s, pixels);
-    DeviceGuard g(p->device);
-    int st = ensure_scratch(p, pixels * 4 + 4);
-    if (st != OCH_OK) return st;
-    st = och_gpu_render_lit_ssaa_views_dev(p, cam, 1, light, s, reinterpret_cast<uint32_t *>(p->scratch.d), pixels);
-    if (st != OCH_OK) return st;
-    OCH_HIP(hipMemcpyAsync(rgba, p->scratch.d, pixels * 4, hipMemcpyDeviceToHost, p->stream()));
-    OCH_HIP(hipStreamSynchronize(p->stream()));
-    return OCH_OK;
+    size_t pixels;
+    if (int cs = host_capacity(capacity_pixels, cam->width / s, cam->height / s, pixels)) return cs;
+    return to_host(p, pixels, 4, rgba,
+                   [&](uint32_t *o) { return och_gpu_render_lit_ssaa_views_dev(p, cam, 1, light, s, o, pixels); });
 }
 
 OCH_API int och_gpu_render_steps_dev(och_gpu_pool *p, const och_camera *cams, int n_views, int n_steps,
@@ -2156,11 +2185,7 @@ OCH_API int och_gpu_render_steps_dev(och_gpu_pool *p, const och_camera *cams, in
 {
     OCH_ENTRY();
     if (!p || !cams || !streams || !frames) return fail(OCH_E_INVALID, "NULL argument");
-    if (n_steps < 0 || n_buffers < 1) return fail(OCH_E_INVALID, "n_steps %d / n_buffers %d", n_steps, n_buffers);
-    if ((start_events == nullptr) != (stop_events == nullptr))
-        return fail(OCH_E_INVALID, "start_events and stop_events: both or neither");
-    for (int b = 0; b < n_buffers; ++b)
-        if (!frames[b]) return fail(OCH_E_INVALID, "frames[%d] is NULL", b);
+    if (int as = loop_args(n_steps, n_buffers, start_events, stop_events, frames)) return as;
     // The frame loop of update_image (ORT/test_och_h_octree.cpp:437-457), one
     // launch per frame, issued here rather than by the caller's interpreter.
     // The pool's stream is restored afterwards, also after a failure.
@@ -2181,11 +2206,7 @@ OCH_API int och_gpu_render_lit_steps_dev(och_gpu_pool *p, const och_camera *cams
     OCH_ENTRY();
     if (!p || !cams || !light || !streams || !frames) return fail(OCH_E_INVALID, "NULL argument");
     if (int ls = och_light_check(light)) return ls;
-    if (n_steps < 0 || n_buffers < 1) return fail(OCH_E_INVALID, "n_steps %d / n_buffers %d", n_steps, n_buffers);
-    if ((start_events == nullptr) != (stop_events == nullptr))
-        return fail(OCH_E_INVALID, "start_events and stop_events: both or neither");
-    for (int b = 0; b < n_buffers; ++b)
-        if (!frames[b]) return fail(OCH_E_INVALID, "frames[%d] is NULL", b);
+    if (int as = loop_args(n_steps, n_buffers, start_events, stop_events, frames)) return as;
     if (int vs = och::check_views(cams, n_views)) return vs;
     // och_gpu_render_steps_dev's loop, each frame a lit frame as one shard
     const size_t pixels = (size_t)n_views * (size_t)cams[0].width * (size_t)cams[0].height;
@@ -2232,9 +2253,7 @@ int och::sharded_steps(och_gpu_pool *p, och_comm *comm, const och_camera *cams, 
     if (codes && shades && !p->d_code_table.d)
         return fail(OCH_E_INVALID, "no code table: set a palette of at most %d voxel ids", OCH_CODE_MAX_VOXELS);
     // lit codes: the rendering rank needs the palette too (render_lit_views would refuse mid-window)
-    if (codes && light && (p->n_voxels > OCH_CODE_MAX_VOXELS || !p->d_code_table.d))
-        return fail(OCH_E_INVALID, "lit codes need a palette (och_gpu_set_palette) of at most %d voxel ids",
-                    OCH_CODE_MAX_VOXELS);
+    if (int cs = codes && light ? needs_code_palette(p, "lit codes") : OCH_OK) return cs;
     const int W = cams[0].width, H = cams[0].height;
     const size_t pixels = (size_t)n_views * p->slice_rows(H, row_chunk, n_ranks) * W;
     const size_t bytes = pixels * (codes ? (light ? 2 : 1) : 4);
@@ -2318,10 +2337,7 @@ OCH_API int och_gpu_shade_unshard_views_dev(och_gpu_pool *p, const uint8_t *gath
                                             int height, int row_chunk, int n_shards, int n_views)
 {
     OCH_ENTRY();
-    if (!p || !gathered || !frames || width <= 0 || height <= 0 || row_chunk <= 0 || n_shards <= 0 || n_views < 1)
-        return fail(OCH_E_INVALID, "bad unshard arguments");
-    if (!p->d_code_table.d)
-        return fail(OCH_E_INVALID, "no code table: set a palette of at most %d voxel ids", OCH_CODE_MAX_VOXELS);
+    if (int as = unshard_args(p, gathered, frames, width, height, row_chunk, n_shards, n_views, true)) return as;
     DeviceGuard g(p->device);
     OCH_HIP(och::launch_shade_unshard(gathered, frames, p->d_code_table.d, width, height, row_chunk, n_shards,
                                       p->slice_rows(height, row_chunk, n_shards), n_views,
@@ -2341,8 +2357,7 @@ OCH_API int och_gpu_unshard_views_dev(och_gpu_pool *p, const uint32_t *gathered,
                                       int height, int row_chunk, int n_shards, int n_views)
 {
     OCH_ENTRY();
-    if (!p || !gathered || !frames || width <= 0 || height <= 0 || row_chunk <= 0 || n_shards <= 0 || n_views < 1)
-        return fail(OCH_E_INVALID, "bad unshard arguments");
+    if (int as = unshard_args(p, gathered, frames, width, height, row_chunk, n_shards, n_views, false)) return as;
     DeviceGuard g(p->device);
     OCH_HIP(och::launch_unshard(gathered, frames, width, height, row_chunk, n_shards,
                                 p->slice_rows(height, row_chunk, n_shards), n_views,
@@ -2361,39 +2376,21 @@ OCH_API int och_gpu_render(och_gpu_pool *p, const och_camera *cam, uint32_t *rgb
 {
     OCH_ENTRY();
     if (!p || !cam || !rgba) return fail(OCH_E_INVALID, "NULL argument");
-    DeviceGuard g(p->device);
-    const size_t bytes = (size_t)cam->width * cam->height * 4;
-    int st = ensure_scratch(p, bytes);
-    if (st != OCH_OK) return st;
-    st = och_gpu_render_dev(p, cam, reinterpret_cast<uint32_t *>(p->scratch.d), cam->height, 0, 1);
-    if (st != OCH_OK) return st;
-    OCH_HIP(hipMemcpyAsync(rgba, p->scratch.d, bytes, hipMemcpyDeviceToHost, p->stream()));
-    OCH_HIP(hipStreamSynchronize(p->stream()));
-    return OCH_OK;
+    // no capacity argument, and a scratch of exactly the frame
+    return to_host(p, (size_t)cam->width * cam->height, 0, rgba,
+                   [&](uint32_t *scratch) { return och_gpu_render_dev(p, cam, scratch, cam->height, 0, 1); });
 }
 
 OCH_API int och_gpu_render_ssaa(och_gpu_pool *p, const och_camera *cam, int s, uint32_t *rgba, size_t capacity_pixels)
 {
     OCH_ENTRY();
     if (!p || !cam || !rgba) return fail(OCH_E_INVALID, "NULL argument");
-    if (s != 2 && s != 4 && s != 8) return fail(OCH_E_INVALID, "samples per axis %d: must be 2, 4 or 8", s);
-    if (int vs = check_views(cam, 1)) return vs;
-    if (cam->width % s || cam->height % s)
-        return fail(OCH_E_INVALID, "sample grid %d x %d is not a multiple of %d", cam->width, cam->height, s);
+    if (int as = ssaa_args(cam, 1, s)) return as;
     if (int rs = check_ready(p)) return rs;
-    // refused before the staging buffer is sized; the device form checks again
-    const size_t pixels = (size_t)(cam->width / s) * (size_t)(cam->height / s);
-    if (capacity_pixels < pixels)
-        return fail(OCH_E_INVALID, "rgba holds %zu pixels, %d x %d need %zu", capacity_pixels, cam->width / s,
-                    cam->height / s, pixels);
-    DeviceGuard g(p->device);
-    int st = ensure_scratch(p, pixels * 4 + 4);
-    if (st != OCH_OK) return st;
-    st = och_gpu_render_ssaa_views_dev(p, cam, 1, s, reinterpret_cast<uint32_t *>(p->scratch.d), pixels);
-    if (st != OCH_OK) return st;
-    OCH_HIP(hipMemcpyAsync(rgba, p->scratch.d, pixels * 4, hipMemcpyDeviceToHost, p->stream()));
-    OCH_HIP(hipStreamSynchronize(p->stream()));
-    return OCH_OK;
+    size_t pixels;
+    if (int cs = host_capacity(capacity_pixels, cam->width / s, cam->height / s, pixels)) return cs;
+    return to_host(p, pixels, 4, rgba,
+                   [&](uint32_t *scratch) { return och_gpu_render_ssaa_views_dev(p, cam, 1, s, scratch, pixels); });
 }
 
 OCH_API int och_pool_pack(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, int index_base,

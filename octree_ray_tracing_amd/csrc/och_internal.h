@@ -195,6 +195,9 @@ hipError_t launch_trace_bounce_batch(const DevPool &p, const float *origin, int 
                                      uint32_t n, int32_t *hit_dir, uint32_t *hit_voxel, uint32_t *hit_time,
                                      int32_t *bounce_dir, uint32_t *bounce_voxel, uint32_t *bounce_time,
                                      uint32_t *push_count, const Schedule &sc, hipStream_t stream);
+// Every camera launch below (launch_render*) refuses, with hipErrorInvalidValue,
+// a view count outside 1..OCH_MAX_VIEWS and a schedule without a tile table of
+// its block size -- one place, camera_args and tiles_fit in och_kernels.hip.
 hipError_t launch_render_bounce(const DevPool &p, const DevFrame &f, const Schedule &sc, hipStream_t stream);
 hipError_t launch_raygen(const och_camera &cam, float *dirs, hipStream_t stream);
 hipError_t launch_render(const DevPool &p, const DevFrame &f, const Schedule &sc, hipStream_t stream);
@@ -223,9 +226,11 @@ hipError_t launch_shade_lit_unshard(const uint16_t *gathered, uint32_t *frames, 
                                     int height, int row_chunk, int n_shards, int slice_rows, int n_views,
                                     const int32_t *owner, int sun_shade, int ao_shade, hipStream_t stream);
 // Supersampled lit frames (k_trace_lit_ssaa): launch_render_ssaa's sample grid
-// and output, every sample launch_render_lit's frame colour under light.  One
-// shard's whole frame, width and height multiples of s, block <= 1024;
-// sc.bounce_compact and sc.order as for launch_render_lit.
+// and output (the same whole_frame_samples refusal, the same resolve), every
+// sample launch_render_lit's frame colour under light, from the passes the two
+// lit kernels share (lit_queue, lit_secondary; k_trace_lit keeps lit_primary's
+// pass and block_slots' scan written out).  block <= 1024,
+// as for every lit launch; sc.bounce_compact and sc.order as for launch_render_lit.
 hipError_t launch_render_lit_ssaa(const DevPool &p, const DevFrame &f, const Schedule &sc, const och_light &light,
                                   int log2_s, hipStream_t stream);
 // The split planner's counting render: each pixel's walked PUSH count (16 bits)

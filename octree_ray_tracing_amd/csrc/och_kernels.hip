@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "och_internal.h"
 
 // Every launch here clears the thread's last HIP error first and reports
@@ -1274,6 +1276,22 @@ __device__ __forceinline__ uint32_t block_sum(uint32_t v)
     return v;
 }
 
+// The s x s resolve of the supersampled kernels: colour is this lane's sample (0 in a
+// lane without one), word its output word (~0u without one).  R | B and G | A as 16-bit
+// sums over the block, the per-channel mean rounded half up, stored by the block's
+// top-left lane.  lane_xor needs all 64 lanes: call it where every lane of the wave is
+// back -- outside any divergent loop, and in a kernel with barriers behind the last one.
+template <int kLog2S>
+__device__ __forceinline__ void ssaa_resolve(uint32_t *out, uint32_t word, uint32_t lane, uint32_t colour)
+{
+    constexpr uint32_t kS = 1u << kLog2S;
+    const uint32_t rb = block_sum<kLog2S>(colour & 0x00FF00FFu), ga = block_sum<kLog2S>((colour >> 8) & 0x00FF00FFu);
+    if (word != ~0u && (lane & (kS - 1u)) == 0 && ((lane >> 3) & (kS - 1u)) == 0) {
+        constexpr uint32_t half = (kS * kS / 2u) * 0x00010001u;
+        out[word] = (((rb + half) >> (2 * kLog2S)) & 0x00FF00FFu) | ((((ga + half) >> (2 * kLog2S)) & 0x00FF00FFu) << 8);
+    }
+}
+
 // Supersampled frames (och_gpu_render_ssaa_views_dev): the
 // cameras are the sample grid, s x s samples (s = 1 << kLog2S = 2, 4, 8) per
 // output pixel, each the colour k_trace_grid's FrameSink would store; the
@@ -1289,7 +1307,6 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_ssaa(DevPool P, Cam
                                                                   uint32_t stamp_cap)
 {
     extern __shared__ uint32_t lds_stack[];
-    constexpr uint32_t kS = 1u << kLog2S;
     const uint64_t t0 = stamps ? realtime() : 0;
     const uint32_t blk = blockIdx.x;                // the tile table holds the launch order
     const uint32_t lane = threadIdx.x & 63u;
@@ -1309,12 +1326,7 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_ssaa(DevPool P, Cam
             colour = pixel_colour(ray_result<kPacked, kAsmLoad>(r, P), K.palette, K.n_voxels);
         }
     }
-    // every lane is back: R | B and G | A as 16-bit sums over the block
-    const uint32_t rb = block_sum<kLog2S>(colour & 0x00FF00FFu), ga = block_sum<kLog2S>((colour >> 8) & 0x00FF00FFu);
-    if (word != ~0u && (lane & (kS - 1u)) == 0 && ((lane >> 3) & (kS - 1u)) == 0) {
-        constexpr uint32_t half = (kS * kS / 2u) * 0x00010001u;
-        K.out[word] = (((rb + half) >> (2 * kLog2S)) & 0x00FF00FFu) | ((((ga + half) >> (2 * kLog2S)) & 0x00FF00FFu) << 8);
-    }
+    ssaa_resolve<kLog2S>(K.out, word, lane, colour);    // every lane is back
     if (stamps) stamp(stamps, stamp_cap, t0, 64);
 }
 
@@ -1339,12 +1351,36 @@ __device__ __forceinline__ void bounce_in_place(const DevPool &P, const Sink &K,
     K.put_secondary(out, payload, ray_result<kPacked, kAsmLoad>(r, P));
 }
 
+// Block scan of the lanes that want a queue slot: each wave's count (ballot +
+// popcount) through LDS (blocks of at most 16 waves), one barrier, then this
+// lane's slot -- the wanting lanes before it, in thread order.  total: the
+// block's wanting lanes; holding: its waves with at least one (config 5's
+// compact = 2 weighs the two; the lit kernels ignore it).  Every thread of the
+// block calls it (the barrier).
+__device__ __forceinline__ uint32_t block_slots(bool want, uint32_t nb, uint32_t lane, uint32_t wave, uint32_t &total,
+                                                uint32_t &holding)
+{
+    __shared__ uint32_t wave_count[16];
+    const uint64_t bal = __ballot(want);
+    if (lane == 0) wave_count[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t base = 0;
+    total = 0;
+    holding = 0;
+    for (uint32_t w = 0; w < (nb >> 6); ++w) {
+        const uint32_t cnt = wave_count[w];
+        base += w < wave ? cnt : 0u;
+        total += cnt;
+        holding += cnt != 0u;
+    }
+    return base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+}
+
 template <class Src, class Sink, int kPacked, bool kCount>
 __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_bounce(DevPool P, Src S, Sink K, int compact, const uint32_t *__restrict__ order,
                                uint32_t *__restrict__ cost, uint64_t *stamps, uint32_t stamp_cap)
 {
     extern __shared__ uint32_t lds_stack[];
-    __shared__ uint32_t wave_count[16];
     const uint64_t c0 = cost ? __builtin_amdgcn_s_memtime() : 0;
     uint32_t blk = blockIdx.x;                      // a tile table holds the launch order
     if constexpr (!Src::kTileTable) blk = order ? order[blockIdx.x] : blockIdx.x;
@@ -1357,6 +1393,11 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_bounce(DevPool P, S
     uint32_t out = 0, payload = 0;
     bool want = false;
     bool miss;
+    // every exit: the block's cost (the planning launch) and the wave's stamp
+    const auto finish = [&](uint64_t rays) {
+        if (cost && threadIdx.x == 0) cost[blk] = (uint32_t)(__builtin_amdgcn_s_memtime() - c0);
+        if (stamps) stamp(stamps, stamp_cap, t0, rays);
+    };
     if (wave_base + (threadIdx.x & 63u) < S.count() &&
         S.get_wave_culled(wave_base, threadIdx.x & 63u, P, kCount ? P.cull == 2 : P.cull != 0, o, d, out, miss)) {
         if (miss) {                                 // proven before setup: the MISS, no secondary ray
@@ -1372,31 +1413,15 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_bounce(DevPool P, S
                 bounce_in_place<kPacked, kCount>(P, K, stack, nb, o2, d2, out, payload);
         }
     }
-    if (compact == 0) {
-        if (cost && threadIdx.x == 0) cost[blk] = (uint32_t)(__builtin_amdgcn_s_memtime() - c0);
-        if (stamps) stamp(stamps, stamp_cap, t0, 0);
-        return;
-    }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t bal = __ballot(want);
-    if (lane == 0) wave_count[wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t base = 0, total = 0, holding = 0;
-    for (uint32_t w = 0; w < (nb >> 6); ++w) {
-        const uint32_t cnt = wave_count[w];
-        base += w < wave ? cnt : 0u;
-        total += cnt;
-        holding += cnt != 0u;
-    }
+    if (compact == 0) return finish(0);
+    uint32_t total, holding;
+    const uint32_t q = block_slots(want, nb, threadIdx.x & 63u, threadIdx.x >> 6, total, holding);
     if (compact == 2 && (total + 63u) / 64u >= holding) {
         // the queue would not free a wave (block-uniform): in place
         if (want) bounce_in_place<kPacked, kCount>(P, K, stack, nb, o2, d2, out, payload);
-        if (cost && threadIdx.x == 0) cost[blk] = (uint32_t)(__builtin_amdgcn_s_memtime() - c0);
-        if (stamps) stamp(stamps, stamp_cap, t0, 0);
-        return;
+        return finish(0);
     }
     if (want) {
-        const uint32_t q = base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
         queue[0 * nb + q] = fbits(o2[0]);
         queue[1 * nb + q] = fbits(o2[1]);
         queue[2 * nb + q] = fbits(o2[2]);
@@ -1423,8 +1448,7 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_bounce(DevPool P, S
         ray_trace<kPacked, kCount, true, kAsmLoad>(r, P, so, sd, stack, nb);
         K.put_secondary(sout, spay, ray_result<kPacked, kAsmLoad>(r, P));
     }
-    if (cost && threadIdx.x == 0) cost[blk] = (uint32_t)(__builtin_amdgcn_s_memtime() - c0);
-    if (stamps) stamp(stamps, stamp_cap, t0, total);
+    finish(total);
 }
 
 // Lit frames (och_gpu_render_lit_views_dev): a face hit's
@@ -1524,6 +1548,76 @@ struct LitCodeSink {
 constexpr uint32_t kLitQueueWords = 6;
 constexpr uint32_t kLitNoPixel = 0xFFu;        // state of a slot without a hit pixel (in-place form)
 
+// The lit kernels' queue (SoA, nb words per plane; planes 0..2 hold the secondary origin):
+// behind the stacks' word plane, not in it, so it outlives the secondary walks (launch_tiles).
+__device__ __forceinline__ uint32_t *lit_queue(uint32_t *lds_stack, uint32_t stack, const DevPool &P, uint32_t nb)
+{
+    return lds_stack + (stack - 4u * threadIdx.x - (uint32_t)(uintptr_t)(const lds_word *)lds_stack) / 4u +
+           ((uint32_t)P.depth + 1u) * nb;
+}
+
+// The lit kernels' primary pass (k_trace_bounce's): false in a lane without a
+// pixel; else out is the pixel's token and h1 its primary record (the MISS
+// when the sky is proven before setup).  want: a face hit -- then p is its
+// secondary origin and state its direction, with bits 4 and 5 of the mask
+// already set when the face is turned away from the sun (no sun ray).
+template <int kPacked>
+__device__ __forceinline__ bool lit_primary(const DevPool &P, const CameraSource &S, const och_light &L, uint32_t wave_base,
+                                            uint32_t lane, uint32_t stack, uint32_t nb, uint32_t &out, Hit &h1, bool &want,
+                                            uint32_t &state, float *p)
+{
+    float o[3], d[3], d2[3];
+    bool miss;
+    want = false;
+    state = kLitNoPixel;
+    h1 = Hit{OCH_EXIT, 0u, P.miss_bits, 0u};
+    if (!(wave_base + lane < S.count() && S.get_wave_culled(wave_base, lane, P, P.cull != 0, o, d, out, miss))) return false;
+    if (miss) return true;                          // proven before setup: the sky
+    Ray r;
+    ray_trace<kPacked, false, true, kAsmLoad>(r, P, o, d, stack, nb, !P.cam_cull);
+    h1 = ray_result<kPacked, kAsmLoad>(r, P);
+    want = h1.dir < OCH_EXIT;
+    if (want) {
+        bounce_ray(o, d, h1, P.half_voxel, p, d2);
+        state = (uint32_t)h1.dir;
+        if ((L.flags & OCH_LIGHT_SUN) && !lit_faces_sun(L, state)) state |= 0x30u << 8;   // self-shadowed
+    }
+    return true;
+}
+
+// The lit kernels' secondary pass over `total` queued pixels, their state words
+// in plane state_plane: the block's rays as one flat list, ray kind major, dealt
+// over its lanes in rounds of nb; a ray's bit is ORed into its pixel's state
+// word.  Returns the rays in the list.  Lanes leave the loop at different times:
+// nothing that needs the whole wave (lane_xor, a barrier) belongs inside it.
+template <int kPacked>
+__device__ __forceinline__ uint32_t lit_secondary(const DevPool &P, const och_light &L, uint32_t *queue, uint32_t state_plane,
+                                                  uint32_t stack, uint32_t nb, uint32_t total)
+{
+    const uint32_t first = (L.flags & OCH_LIGHT_SUN) ? 0u : 1u;
+    const uint32_t kinds = ((L.flags & OCH_LIGHT_SUN) ? 1u : 0u) + ((L.flags & OCH_LIGHT_AO) ? 4u : 0u);
+    // ray j of the list: kind first + j / total of queued pixel j % total
+    for (uint32_t j = threadIdx.x; j < kinds * total; j += nb) {
+        uint32_t pix = j, kind = first;
+        while (pix >= total) {
+            pix -= total;
+            ++kind;
+        }
+        const uint32_t st = queue[state_plane * nb + pix];   // the direction and bit 5 are final; other lanes OR bits 0..4
+        if ((st & 0xFFu) == kLitNoPixel || (kind == 0 && (st & (0x20u << 8)) != 0)) continue;   // self-shadowed: no ray
+        float so[3], sd[3];
+        so[0] = ffrom(queue[0 * nb + pix]);
+        so[1] = ffrom(queue[1 * nb + pix]);
+        so[2] = ffrom(queue[2 * nb + pix]);
+        lit_ray_dir(L, kind, st & 0xFFu, sd);
+        Ray r;
+        ray_trace<kPacked, false, true, kAsmLoad>(r, P, so, sd, stack, nb);
+        const uint32_t bit = lit_ray_bit(L, kind, ray_result<kPacked, kAsmLoad>(r, P));
+        if (bit) atomicOr(&queue[state_plane * nb + pix], bit << 8);
+    }
+    return kinds * total;
+}
+
 // The primary pass is k_trace_bounce's.  Then the block's hit pixels go into an
 // LDS queue (SoA, kLitQueueWords per thread) that lies behind the parent
 // stacks, not in them: it is read again after the secondary walks, which use
@@ -1548,16 +1642,15 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_lit(DevPool P, Came
     const uint32_t blk = blockIdx.x;                // the tile table holds the launch order
     const uint32_t nb = blockDim.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t stack = stack_column(lds_stack, P.depth);
-    // the queue starts where the stacks' word plane ends (launch_lit sizes both)
-    uint32_t *queue = lds_stack + (stack - 4u * threadIdx.x - (uint32_t)(uintptr_t)(const lds_word *)lds_stack) / 4u +
-                      ((uint32_t)P.depth + 1u) * nb;
+    uint32_t *queue = lit_queue(lds_stack, stack, P, nb);
     const uint32_t wave_base = blk * nb + (threadIdx.x & ~63u);
-    const uint32_t first = (L.flags & OCH_LIGHT_SUN) ? 0u : 1u;
-    const uint32_t kinds = ((L.flags & OCH_LIGHT_SUN) ? 1u : 0u) + ((L.flags & OCH_LIGHT_AO) ? 4u : 0u);
     float o[3], d[3], p[3], d2[3];
     uint32_t out = 0, payload = 0, state = kLitNoPixel;
     bool want = false;
     bool miss;
+    // lit_primary's pass and block_slots' scan, written out: as calls they cost this
+    // kernel SGPR spills the text below does not have (profiles/camera_refactor/INDEX.md).
+    // A change to either helper is a change here too.
     if (wave_base + lane < S.count() && S.get_wave_culled(wave_base, lane, P, P.cull != 0, o, d, out, miss)) {
         if (miss) {                                 // proven before setup: the sky
             K.put_plain(out, K.payload(Hit{OCH_EXIT, 0u, P.miss_bits, 0u}));
@@ -1599,32 +1692,14 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_lit(DevPool P, Came
     }
     if (want || !compact) queue[5 * nb + q] = state;
     __syncthreads();
-    // ray j of the list: kind first + j / total of queued pixel j % total
-    for (uint32_t j = threadIdx.x; j < kinds * total; j += nb) {
-        uint32_t pix = j, kind = first;
-        while (pix >= total) {
-            pix -= total;
-            ++kind;
-        }
-        const uint32_t st = queue[5 * nb + pix];    // the direction and bit 5 are final; other lanes OR bits 0..4
-        if ((st & 0xFFu) == kLitNoPixel || (kind == 0 && (st & (0x20u << 8)) != 0)) continue;   // self-shadowed: no ray
-        float so[3], sd[3];
-        so[0] = ffrom(queue[0 * nb + pix]);
-        so[1] = ffrom(queue[1 * nb + pix]);
-        so[2] = ffrom(queue[2 * nb + pix]);
-        lit_ray_dir(L, kind, st & 0xFFu, sd);
-        Ray r;
-        ray_trace<kPacked, false, true, kAsmLoad>(r, P, so, sd, stack, nb);
-        const uint32_t bit = lit_ray_bit(L, kind, ray_result<kPacked, kAsmLoad>(r, P));
-        if (bit) atomicOr(&queue[5 * nb + pix], bit << 8);
-    }
+    const uint32_t rays = lit_secondary<kPacked>(P, L, queue, 5u, stack, nb, total);
     __syncthreads();
     if (threadIdx.x < total) {
         const uint32_t st = queue[5 * nb + threadIdx.x];
         if ((st & 0xFFu) != kLitNoPixel)
             K.put_lit(queue[3 * nb + threadIdx.x], queue[4 * nb + threadIdx.x], (st >> 8) & 0xFFu, L);
     }
-    if (stamps) stamp(stamps, stamp_cap, t0, kinds * total);
+    if (stamps) stamp(stamps, stamp_cap, t0, rays);
 }
 
 // Words per thread of k_trace_lit_ssaa's sample queue: the secondary origin (3)
@@ -1635,67 +1710,36 @@ constexpr uint32_t kLitSsaaQueueWords = 4;
 // the cameras are the sample grid as for k_trace_ssaa, every sample the colour
 // k_trace_lit's frame sink would store, the output word their per-channel mean.
 // The primary pass, the queue behind the stacks, the kind-major ray list and
-// the OR into the state word are k_trace_lit's.  What differs is the way back:
-// a sample's lane keeps its plain colour and its queue slot q in registers, and
-// after the last barrier reads its finished mask from slot q and shades its own
-// colour -- so the queue carries neither the colour nor an output index, and
-// every lane holds its sample's final colour when the wave reaches block_sum,
-// which runs behind the barrier, outside the secondary loop (lane_xor needs all
-// 64 lanes).  Lanes without a sample add 0; blocks are whole (k_trace_ssaa).
+// the OR into the state word are k_trace_lit's (lit_primary, lit_queue,
+// lit_secondary).  What differs is the way back: a sample's lane keeps its plain
+// colour and its queue slot q in registers, and after the last barrier reads its
+// finished mask from slot q and shades its own colour -- so the queue carries
+// neither the colour nor an output index, and every lane holds its sample's
+// final colour when the wave reaches ssaa_resolve, behind that barrier and
+// outside lit_secondary's loop.  Lanes without a sample add 0; blocks are whole.
 // compact as in k_trace_lit; both forms write the same bytes.
 template <int kPacked, int kLog2S>
 __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_lit_ssaa(DevPool P, CameraSource S, FrameSink K, och_light L, int compact,
                                                                       uint64_t *stamps, uint32_t stamp_cap)
 {
     extern __shared__ uint32_t lds_stack[];
-    __shared__ uint32_t wave_count[16];
-    constexpr uint32_t kS = 1u << kLog2S;
     const uint64_t t0 = stamps ? realtime() : 0;
     const uint32_t blk = blockIdx.x;                // the tile table holds the launch order
     const uint32_t nb = blockDim.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t stack = stack_column(lds_stack, P.depth);
-    // the queue starts where the stacks' word plane ends (launch_lit_ssaa_as sizes both)
-    uint32_t *queue = lds_stack + (stack - 4u * threadIdx.x - (uint32_t)(uintptr_t)(const lds_word *)lds_stack) / 4u +
-                      ((uint32_t)P.depth + 1u) * nb;
+    uint32_t *queue = lit_queue(lds_stack, stack, P, nb);
     const uint32_t wave_base = blk * nb + (threadIdx.x & ~63u);
-    const uint32_t first = (L.flags & OCH_LIGHT_SUN) ? 0u : 1u;
-    const uint32_t kinds = ((L.flags & OCH_LIGHT_SUN) ? 1u : 0u) + ((L.flags & OCH_LIGHT_AO) ? 4u : 0u);
-    float o[3], d[3], p[3], d2[3];
-    uint32_t out, word = ~0u, colour = 0, state = kLitNoPixel;
-    bool want = false;
-    bool miss;
-    if (wave_base + lane < S.count() && S.get_wave_culled(wave_base, lane, P, P.cull != 0, o, d, out, miss)) {
+    float p[3];
+    uint32_t out, word = ~0u, colour = 0, state;
+    bool want;
+    Hit h1;
+    if (lit_primary<kPacked>(P, S, L, wave_base, lane, stack, nb, out, h1, want, state, p)) {
         // this sample's output word: view * W * H + Y * W + X
         word = S.sample_word(wave_base, lane, kLog2S);
-        if (miss) {                                 // proven before setup: the sky
-            colour = pixel_colour(Hit{OCH_EXIT, 0u, P.miss_bits, 0u}, K.palette, K.n_voxels);
-        } else {
-            Ray r;
-            ray_trace<kPacked, false, true, kAsmLoad>(r, P, o, d, stack, nb, !P.cam_cull);
-            const Hit h1 = ray_result<kPacked, kAsmLoad>(r, P);
-            want = h1.dir < OCH_EXIT;
-            colour = pixel_colour(h1, K.palette, K.n_voxels);
-            if (want) {
-                bounce_ray(o, d, h1, P.half_voxel, p, d2);
-                state = (uint32_t)h1.dir;
-                if ((L.flags & OCH_LIGHT_SUN) && !lit_faces_sun(L, state)) state |= 0x30u << 8;   // self-shadowed
-            }
-        }
+        colour = pixel_colour(h1, K.palette, K.n_voxels);
     }
-    uint32_t q = threadIdx.x, total = nb;
-    if (compact) {
-        const uint64_t bal = __ballot(want);
-        if (lane == 0) wave_count[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t base = 0;
-        total = 0;
-        for (uint32_t w = 0; w < (nb >> 6); ++w) {
-            const uint32_t cnt = wave_count[w];
-            base += w < wave ? cnt : 0u;
-            total += cnt;
-        }
-        q = base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-    }
+    uint32_t q = threadIdx.x, total = nb, holding;
+    if (compact) q = block_slots(want, nb, lane, wave, total, holding);
     if (want) {
         queue[0 * nb + q] = fbits(p[0]);
         queue[1 * nb + q] = fbits(p[1]);
@@ -1703,35 +1747,12 @@ __global__ __attribute__((amdgpu_num_sgpr(80))) void k_trace_lit_ssaa(DevPool P,
     }
     if (want || !compact) queue[3 * nb + q] = state;
     __syncthreads();
-    // ray j of the list: kind first + j / total of queued sample j % total
-    for (uint32_t j = threadIdx.x; j < kinds * total; j += nb) {
-        uint32_t pix = j, kind = first;
-        while (pix >= total) {
-            pix -= total;
-            ++kind;
-        }
-        const uint32_t st = queue[3 * nb + pix];    // the direction and bit 5 are final; other lanes OR bits 0..4
-        if ((st & 0xFFu) == kLitNoPixel || (kind == 0 && (st & (0x20u << 8)) != 0)) continue;   // self-shadowed: no ray
-        float so[3], sd[3];
-        so[0] = ffrom(queue[0 * nb + pix]);
-        so[1] = ffrom(queue[1 * nb + pix]);
-        so[2] = ffrom(queue[2 * nb + pix]);
-        lit_ray_dir(L, kind, st & 0xFFu, sd);
-        Ray r;
-        ray_trace<kPacked, false, true, kAsmLoad>(r, P, so, sd, stack, nb);
-        const uint32_t bit = lit_ray_bit(L, kind, ray_result<kPacked, kAsmLoad>(r, P));
-        if (bit) atomicOr(&queue[3 * nb + pix], bit << 8);
-    }
+    const uint32_t rays = lit_secondary<kPacked>(P, L, queue, 3u, stack, nb, total);
     __syncthreads();
     // the masks are final: a hit sample's lane takes its own from its slot
     if (want) colour = lit_shade(colour, (queue[3 * nb + q] >> 8) & 0xFFu, L);
-    // every lane is here: R | B and G | A as 16-bit sums over the block
-    const uint32_t rb = block_sum<kLog2S>(colour & 0x00FF00FFu), ga = block_sum<kLog2S>((colour >> 8) & 0x00FF00FFu);
-    if (word != ~0u && (lane & (kS - 1u)) == 0 && ((lane >> 3) & (kS - 1u)) == 0) {
-        constexpr uint32_t half = (kS * kS / 2u) * 0x00010001u;
-        K.out[word] = (((rb + half) >> (2 * kLog2S)) & 0x00FF00FFu) | ((((ga + half) >> (2 * kLog2S)) & 0x00FF00FFu) << 8);
-    }
-    if (stamps) stamp(stamps, stamp_cap, t0, kinds * total);
+    ssaa_resolve<kLog2S>(K.out, word, lane, colour);    // every lane is here, behind the last barrier
+    if (stamps) stamp(stamps, stamp_cap, t0, rays);
 }
 
 __global__ __launch_bounds__(256) void k_raygen(och_camera C, float *__restrict__ dirs)
@@ -1889,7 +1910,7 @@ __global__ __launch_bounds__(256) void k_scatter_slots(const uint32_t *__restric
 // Per lane: parents of levels 1..depth-1 in slots 1..depth-1, plus a spare
 // slot below (the miss POP's read) and above (the hit descent's write); the
 // word plane, and below it the idx plane (stack_column), for a dynamic LDS
-// area that starts at most kStaticLds bytes in (k_trace_bounce's wave counts).
+// area that starts at most kStaticLds bytes in (block_slots' wave counts).
 constexpr size_t kStaticLds = 64;
 size_t stack_bytes(int depth, int block)
 {
@@ -2009,6 +2030,64 @@ CameraSource camera_source(const DevPool &p, const DevFrame &f, const Schedule &
     return src;
 }
 
+// What every camera launch starts from: the frame's rays and its RGBA8 sink
+// (launches with a sink of their own use only src).  False -- the launch is
+// refused -- for a view count the source cannot hold and, where the kernel
+// scans its waves through 16 count words (the lit kernels), for a block above 16 waves.
+struct CameraArgs {
+    CameraSource src;
+    FrameSink sink;
+};
+
+bool camera_args(const DevPool &p, const DevFrame &f, const Schedule &sc, bool wave_scan, CameraArgs &c)
+{
+    if (f.n_views < 1 || f.n_views > kMaxViews) return false;
+    if (wave_scan && (uint32_t)sc.block > 1024u) return false;
+    c.src = camera_source(p, f, sc);
+    c.sink = FrameSink{f.out, f.palette, f.n_voxels};
+    return true;
+}
+
+// The supersampled kernels take the sample grid as one shard's whole frame
+// (slice rows for rows), its width and height multiples of s = 1 << log2_s.
+bool whole_frame_samples(const DevFrame &f, int log2_s)
+{
+    if (f.n_shards != 1 || f.shard != 0 || f.row_chunk != f.cams[0].height || f.slice_rows != f.cams[0].height)
+        return false;
+    const int s = 1 << log2_s;
+    return f.cams[0].width % s == 0 && f.cams[0].height % s == 0;
+}
+
+// A supersampled launch's run-time (packed, log2_s) as template arguments (std::integral_constant).
+template <class Launch>
+hipError_t with_layout_and_samples(const DevPool &p, int log2_s, Launch launch)
+{
+    const auto samples = [&](auto layout) {
+        switch (log2_s) {
+        case 1: return launch(layout, std::integral_constant<int, 1>{});
+        case 2: return launch(layout, std::integral_constant<int, 2>{});
+        case 3: return launch(layout, std::integral_constant<int, 3>{});
+        default: return hipErrorInvalidValue;
+        }
+    };
+    return p.packed ? samples(std::integral_constant<int, 1>{}) : samples(std::integral_constant<int, 0>{});
+}
+
+// The launch of a camera kernel other than the grid's: the tile table's workgroups,
+// never a split plan (split_tile maps lanes to rays differently).  LDS: the parent
+// stacks and, behind them, queue_words words per thread (the lit kernels' queues,
+// which must outlive the secondary walks).
+template <class... Params, class... Args>
+hipError_t launch_tiles(const Schedule &sc, int depth, uint32_t queue_words, hipStream_t stream,
+                        void (*kernel)(Params...), const Args &...args)
+{
+    const uint32_t block = (uint32_t)sc.block;
+    if (!tiles_fit(sc, sc.block) || sc.split_tasks) return hipErrorInvalidValue;
+    const size_t lds = stack_bytes(depth, sc.block) + (size_t)queue_words * block * sizeof(uint32_t);
+    OCH_LAUNCH_TIMED(sc, kernel, dim3(sc.tiles_grid), dim3(block), lds, stream, args...);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t occupancy_blocks_per_cu(int kind, int block, int depth, int *blocks)
@@ -2070,138 +2149,57 @@ hipError_t launch_raygen(const och_camera &cam, float *dirs, hipStream_t stream)
 
 hipError_t launch_render(const DevPool &p, const DevFrame &f, const Schedule &sc, hipStream_t stream)
 {
-    if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
-    const CameraSource src = camera_source(p, f, sc);
-    return launch<CameraSource, FrameSink, false>(p, src, FrameSink{f.out, f.palette, f.n_voxels}, src.count(), sc,
-                                                  stream);
+    CameraArgs c;
+    if (!camera_args(p, f, sc, false, c)) return hipErrorInvalidValue;
+    return launch<CameraSource, FrameSink, false>(p, c.src, c.sink, c.src.count(), sc, stream);
 }
-
-namespace {
-
-template <int kPacked, int kLog2S>
-hipError_t launch_ssaa_as(const DevPool &p, const CameraSource &s, const FrameSink &k, const Schedule &sc,
-                          hipStream_t stream)
-{
-    const uint32_t block = (uint32_t)sc.block;
-    // a split plan never reaches this kernel (split_tile maps lanes to rays differently)
-    if (!tiles_fit(sc, (int)block) || sc.split_tasks) return hipErrorInvalidValue;
-    OCH_LAUNCH_TIMED(sc, (k_trace_ssaa<kPacked, kLog2S>), dim3(sc.tiles_grid), dim3(block),
-                     stack_bytes(p.depth, (int)block), stream, p, s, k, sc.stamps, sc.stamp_cap);
-    return hipGetLastError();
-}
-
-template <int kPacked>
-hipError_t launch_ssaa_layout(const DevPool &p, const CameraSource &s, const FrameSink &k, const Schedule &sc, int log2_s,
-                              hipStream_t stream)
-{
-    switch (log2_s) {
-    case 1: return launch_ssaa_as<kPacked, 1>(p, s, k, sc, stream);
-    case 2: return launch_ssaa_as<kPacked, 2>(p, s, k, sc, stream);
-    case 3: return launch_ssaa_as<kPacked, 3>(p, s, k, sc, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-}  // namespace
 
 hipError_t launch_render_ssaa(const DevPool &p, const DevFrame &f, const Schedule &sc, int log2_s, hipStream_t stream)
 {
-    if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
-    // the sample grid as one shard's whole frame: the kernel takes slice rows for rows
-    if (f.n_shards != 1 || f.shard != 0 || f.row_chunk != f.cams[0].height || f.slice_rows != f.cams[0].height)
-        return hipErrorInvalidValue;
-    const int s = 1 << log2_s;
-    if (f.cams[0].width % s || f.cams[0].height % s) return hipErrorInvalidValue;
-    const CameraSource src = camera_source(p, f, sc);
-    const FrameSink k{f.out, f.palette, f.n_voxels};
-    return p.packed ? launch_ssaa_layout<1>(p, src, k, sc, log2_s, stream)
-                    : launch_ssaa_layout<0>(p, src, k, sc, log2_s, stream);
+    CameraArgs c;
+    if (!camera_args(p, f, sc, false, c) || !whole_frame_samples(f, log2_s)) return hipErrorInvalidValue;
+    return with_layout_and_samples(p, log2_s, [&](auto packed, auto log2s) {
+        return launch_tiles(sc, p.depth, 0u, stream, k_trace_ssaa<decltype(packed)::value, decltype(log2s)::value>, p, c.src,
+                            c.sink, sc.stamps, sc.stamp_cap);
+    });
 }
-
-namespace {
-
-// LDS of a supersampled lit launch: the parent stacks and, behind them, the
-// sample queue (k_trace_lit_ssaa), which must outlive the secondary walks.
-template <int kPacked, int kLog2S>
-hipError_t launch_lit_ssaa_as(const DevPool &p, const CameraSource &s, const FrameSink &k, const och_light &light,
-                              const Schedule &sc, hipStream_t stream)
-{
-    const uint32_t block = (uint32_t)sc.block;
-    const size_t lds = stack_bytes(p.depth, (int)block) + (size_t)kLitSsaaQueueWords * block * sizeof(uint32_t);
-    // a split plan never reaches this kernel (split_tile maps lanes to rays differently)
-    if (!tiles_fit(sc, (int)block) || sc.split_tasks) return hipErrorInvalidValue;
-    OCH_LAUNCH_TIMED(sc, (k_trace_lit_ssaa<kPacked, kLog2S>), dim3(sc.tiles_grid), dim3(block), lds, stream, p, s, k,
-                     light, sc.bounce_compact, sc.stamps, sc.stamp_cap);
-    return hipGetLastError();
-}
-
-template <int kPacked>
-hipError_t launch_lit_ssaa_layout(const DevPool &p, const CameraSource &s, const FrameSink &k, const och_light &light,
-                                  const Schedule &sc, int log2_s, hipStream_t stream)
-{
-    switch (log2_s) {
-    case 1: return launch_lit_ssaa_as<kPacked, 1>(p, s, k, light, sc, stream);
-    case 2: return launch_lit_ssaa_as<kPacked, 2>(p, s, k, light, sc, stream);
-    case 3: return launch_lit_ssaa_as<kPacked, 3>(p, s, k, light, sc, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-}  // namespace
 
 hipError_t launch_render_lit_ssaa(const DevPool &p, const DevFrame &f, const Schedule &sc, const och_light &light,
                                   int log2_s, hipStream_t stream)
 {
-    if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
-    if ((uint32_t)sc.block > 1024u) return hipErrorInvalidValue;          // wave_count holds 16 waves
-    // the sample grid as one shard's whole frame: the kernel takes slice rows for rows
-    if (f.n_shards != 1 || f.shard != 0 || f.row_chunk != f.cams[0].height || f.slice_rows != f.cams[0].height)
-        return hipErrorInvalidValue;
-    const int s = 1 << log2_s;
-    if (f.cams[0].width % s || f.cams[0].height % s) return hipErrorInvalidValue;
-    const CameraSource src = camera_source(p, f, sc);
-    const FrameSink k{f.out, f.palette, f.n_voxels};
-    return p.packed ? launch_lit_ssaa_layout<1>(p, src, k, light, sc, log2_s, stream)
-                    : launch_lit_ssaa_layout<0>(p, src, k, light, sc, log2_s, stream);
+    CameraArgs c;
+    if (!camera_args(p, f, sc, true, c) || !whole_frame_samples(f, log2_s)) return hipErrorInvalidValue;
+    return with_layout_and_samples(p, log2_s, [&](auto packed, auto log2s) {
+        return launch_tiles(sc, p.depth, kLitSsaaQueueWords, stream,
+                            k_trace_lit_ssaa<decltype(packed)::value, decltype(log2s)::value>, p, c.src, c.sink, light,
+                            sc.bounce_compact, sc.stamps, sc.stamp_cap);
+    });
 }
 
 hipError_t launch_render_push(const DevPool &p, const DevFrame &f, const Schedule &sc, uint16_t *push, hipStream_t stream)
 {
-    if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
     DevPool q = p;
     q.cull = 2;                                 // a counting launch culls only at 2: the PUSHes the render walks
-    const CameraSource src = camera_source(q, f, sc);
-    return launch<CameraSource, PushSink, true>(q, src, PushSink{push}, src.count(), sc, stream);
+    CameraArgs c;
+    if (!camera_args(q, f, sc, false, c)) return hipErrorInvalidValue;
+    return launch<CameraSource, PushSink, true>(q, c.src, PushSink{push}, c.src.count(), sc, stream);
 }
 
 hipError_t launch_render_bounce(const DevPool &p, const DevFrame &f, const Schedule &sc, hipStream_t stream)
 {
-    if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
-    const CameraSource src = camera_source(p, f, sc);
-    return launch_bounce<CameraSource, BounceFrameSink, false>(
-        p, src, BounceFrameSink{FrameSink{f.out, f.palette, f.n_voxels}}, src.count(), sc, stream);
+    CameraArgs c;
+    if (!camera_args(p, f, sc, false, c)) return hipErrorInvalidValue;
+    return launch_bounce<CameraSource, BounceFrameSink, false>(p, c.src, BounceFrameSink{c.sink}, c.src.count(), sc, stream);
 }
 
 namespace {
 
-// LDS of a lit launch: the parent stacks and, behind them, the pixel queue
-// (k_trace_lit), which must outlive the secondary walks.
 template <class Sink>
 hipError_t launch_lit(const DevPool &p, const CameraSource &s, const Sink &k, const och_light &light, const Schedule &sc,
                       hipStream_t stream)
 {
-    const uint32_t block = (uint32_t)sc.block;
-    const size_t lds = stack_bytes(p.depth, (int)block) + (size_t)kLitQueueWords * block * sizeof(uint32_t);
-    // a split plan never reaches this kernel (split_tile maps lanes to rays differently)
-    if (!tiles_fit(sc, (int)block) || sc.split_tasks) return hipErrorInvalidValue;
-    const dim3 grid(sc.tiles_grid);
-    if (p.packed)
-        OCH_LAUNCH_TIMED(sc, (k_trace_lit<Sink, 1>), grid, dim3(block), lds, stream, p, s, k, light,
-                         sc.bounce_compact, sc.stamps, sc.stamp_cap);
-    else
-        OCH_LAUNCH_TIMED(sc, (k_trace_lit<Sink, 0>), grid, dim3(block), lds, stream, p, s, k, light,
-                         sc.bounce_compact, sc.stamps, sc.stamp_cap);
-    return hipGetLastError();
+    return launch_tiles(sc, p.depth, kLitQueueWords, stream, p.packed ? k_trace_lit<Sink, 1> : k_trace_lit<Sink, 0>, p, s, k,
+                        light, sc.bounce_compact, sc.stamps, sc.stamp_cap);
 }
 
 }  // namespace
@@ -2209,29 +2207,27 @@ hipError_t launch_lit(const DevPool &p, const CameraSource &s, const Sink &k, co
 hipError_t launch_render_lit(const DevPool &p, const DevFrame &f, const Schedule &sc, const och_light &light,
                              uint8_t *masks, hipStream_t stream)
 {
-    if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
-    if ((uint32_t)sc.block > 1024u) return hipErrorInvalidValue;          // wave_count holds 16 waves
-    const CameraSource src = camera_source(p, f, sc);
-    if (masks) return launch_lit(p, src, LitMaskSink{masks}, light, sc, stream);
-    return launch_lit(p, src, LitFrameSink{FrameSink{f.out, f.palette, f.n_voxels}}, light, sc, stream);
+    CameraArgs c;
+    if (!camera_args(p, f, sc, true, c)) return hipErrorInvalidValue;
+    if (masks) return launch_lit(p, c.src, LitMaskSink{masks}, light, sc, stream);
+    return launch_lit(p, c.src, LitFrameSink{c.sink}, light, sc, stream);
 }
 
 hipError_t launch_render_lit_codes(const DevPool &p, const DevFrame &f, const Schedule &sc, const och_light &light,
                                    uint16_t *codes, hipStream_t stream)
 {
-    if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
-    if ((uint32_t)sc.block > 1024u) return hipErrorInvalidValue;          // wave_count holds 16 waves
-    const CameraSource src = camera_source(p, f, sc);
-    return launch_lit(p, src, LitCodeSink{codes, f.n_voxels}, light, sc, stream);
+    CameraArgs c;
+    if (!camera_args(p, f, sc, true, c)) return hipErrorInvalidValue;
+    return launch_lit(p, c.src, LitCodeSink{codes, f.n_voxels}, light, sc, stream);
 }
 
 hipError_t launch_render_codes(const DevPool &p, const DevFrame &f, const Schedule &sc, bool bounce, hipStream_t stream)
 {
-    if (f.n_views < 1 || f.n_views > kMaxViews) return hipErrorInvalidValue;
-    const CameraSource src = camera_source(p, f, sc);
+    CameraArgs c;
+    if (!camera_args(p, f, sc, false, c)) return hipErrorInvalidValue;
     const CodeSink k{f.codes, f.n_voxels};
-    if (bounce) return launch_bounce<CameraSource, BounceCodeSink, false>(p, src, BounceCodeSink{k}, src.count(), sc, stream);
-    return launch<CameraSource, CodeSink, false>(p, src, k, src.count(), sc, stream);
+    if (bounce) return launch_bounce<CameraSource, BounceCodeSink, false>(p, c.src, BounceCodeSink{k}, c.src.count(), sc, stream);
+    return launch<CameraSource, CodeSink, false>(p, c.src, k, c.src.count(), sc, stream);
 }
 
 hipError_t launch_shade_unshard(const uint8_t *gathered, uint32_t *frames, const uint32_t *table, int width, int height,

@@ -127,3 +127,21 @@ def test_mask_wait_states():
     assert mask_check("\tv_add_co_u32_e32 v1, vcc, v2, v3\n\tv_addc_co_u32_e32 v4, vcc, v5, v6, vcc\n") == []
     # a scalar write of the mask in between replaces the VALU's; a label resets
     assert mask_check("\tv_cmp_ge_f32_e32 vcc, v23, v21\n\ts_mov_b64 vcc, -1\n\tv_cndmask_b32_e32 v1, v1, v2, vcc\n") == []
+
+
+def test_resource_table_reads_each_kernel_and_refuses_a_missing_body():
+    """--resources: a kernel's row holds its own metadata entry's fields (fields sort before
+    and after .name) and its instruction count without comment, directive and label lines;
+    a metadata name without a function body is an error, not a row of zeros."""
+    import pytest
+    text = ("\t.text\n_Z1kv:\n\t.loc 1 2 3\n\ts_nop 0 ; note\n.LBB0_1:\n\tv_mov_b32_e32 v0, 0\n\ts_endpgm\n.Lfunc_end0:\n")
+    meta = ("amdhsa.kernels:\n  - .agpr_count:     0\n    .group_segment_fixed_size: 64\n    .name:           {name}\n"
+            "    .private_segment_fixed_size: 0\n    .sgpr_count:     78\n    .sgpr_spill_count: 3\n"
+            "    .vgpr_count:     45\n    .vgpr_spill_count: 0\n")
+    row = isa_check.resource_table(text + meta.format(name="_Z1kv"))["_Z1kv"]
+    assert row["instructions"] == 3 and len(row["text"]) == 12
+    assert {k: row[k] for k in isa_check.RESOURCE_FIELDS} == {
+        "sgpr_count": 78, "vgpr_count": 45, "sgpr_spill_count": 3, "vgpr_spill_count": 0,
+        "private_segment_fixed_size": 0, "group_segment_fixed_size": 64}
+    with pytest.raises(SystemExit):
+        isa_check.resource_table(text + meta.format(name="_Z1jv"))

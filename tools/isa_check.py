@@ -33,7 +33,7 @@ Exit status 0 and a one-line summary when every kernel passes; 1 with the
 offending instruction otherwise.  Run by the csrc Makefile (`make isa-check`),
 __graft_entry__.build() and tests/test_isa_check.py.
 
-Usage: python tools/isa_check.py [--source och_kernels.hip] [--asm file.s] [-D NAME=VALUE ...]
+Usage: python tools/isa_check.py [--source och_kernels.hip] [--asm file.s] [-D NAME=VALUE ...] [--resources]
 """
 from __future__ import annotations
 
@@ -271,6 +271,29 @@ def kernel_resources(asm: str):
     return out
 
 
+RESOURCE_FIELDS = ("sgpr_count", "vgpr_count", "sgpr_spill_count", "vgpr_spill_count", "private_segment_fixed_size",
+                   "group_segment_fixed_size")
+
+
+def resource_table(asm: str):
+    """{kernel name: RESOURCE_FIELDS from the code object's metadata, "instructions": the
+    kernel's instruction count, "text": a hash of its instruction text} -- comment,
+    directive (.loc, alignment) and label-only lines dropped; for comparing two builds."""
+    import hashlib
+    fns, out = functions(asm), {}
+    # one metadata entry per kernel, "  - .agpr_count: ..." to the next (fields in alphabetical order)
+    for blk in re.split(r"^  - (?=\.)", asm.split("amdhsa.kernels:", 1)[-1], flags=re.M)[1:]:
+        name = re.search(r"^\s+\.name:\s+(\S+)", blk, re.M).group(1)
+        row = {k: int(m.group(1)) for k in RESOURCE_FIELDS if (m := re.search(rf"\.{k}:\s+(\d+)", blk))}
+        ins = [t for l in fns.get(name, []) if (t := l.split(";")[0].strip()) and not t.startswith(".")]
+        if not ins:
+            raise SystemExit(f"isa_check: no function body for the kernel {name} named in the metadata")
+        row["instructions"] = len(ins)
+        row["text"] = hashlib.sha1("\n".join(ins).encode()).hexdigest()[:12]
+        out[name] = row
+    return out
+
+
 def waves_per_simd(sgpr: int, vgpr: int) -> int:
     """Waves a SIMD admits for these registers (MI355X_MICROARCH.md: residency,
     register files): SGPRs in granules of 16 plus 16 from an 800-entry file,
@@ -285,8 +308,12 @@ def main(argv=None) -> int:
     ap.add_argument("--source", default=str(CSRC / "och_kernels.hip"))
     ap.add_argument("--asm", default=None, help="check this assembly file instead of compiling")
     ap.add_argument("-D", dest="defines", action="append", default=[])
+    ap.add_argument("--resources", action="store_true", help="print every kernel's resource_table row as JSON and exit")
     a = ap.parse_args(argv)
     asm = Path(a.asm).read_text() if a.asm else compile_asm(Path(a.source), a.defines)
+    if a.resources:
+        print(json.dumps(resource_table(asm), indent=1, sort_keys=True))
+        return 0
     fns = functions(asm)
     checked, problems, loads = [], [], 0
     for name, lines in fns.items():
