@@ -1,8 +1,10 @@
 /* Stand-alone host check of och_build_voxels (use_gpu = 0): small lists and a
  * grid, each built and read back voxel by voxel with och_pool_at against a
- * last-wins replay of the records.  Meant to be linked against the builder's
- * host code compiled with AddressSanitizer + UndefinedBehaviorSanitizer
- * (tools/voxel_builder_sanitize.sh); needs no GPU.  Exit status 0 = all equal. */
+ * last-wins replay of the records; then och_build_terrain's host path at depths
+ * 6 and 7.  Meant to be linked against the builders' host code (csrc/och_builder.cpp
+ * with och_dag.h and och_voxel_build.h) compiled with AddressSanitizer +
+ * UndefinedBehaviorSanitizer (tools/voxel_builder_sanitize.sh); needs no GPU.
+ * Exit status 0 = all equal. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -128,6 +130,46 @@ int main(void)
     och_host_pool_free(&pool);
     p.depth = 22;
     CHECK(och_build_voxels(&p, &pool) == OCH_E_INVALID, "depth 22 was accepted");
+
+    /* the host terrain builder: one and two levels above the 32^3 bricks (reduce_grid
+     * over the brick roots) and the leaf-code map, as a DAG and as an expanded tree;
+     * the pool does not depend on the thread count, and the expanded tree has
+     * exactly the nodes the DAG build counted */
+    for (int depth = 6; depth <= 7; ++depth) {
+        uint64_t tree_nodes = 0;
+        for (int dedup = 1; dedup >= 0; --dedup) {
+            och_host_pool built[2];
+            static const int thread_counts[2] = {1, 3};
+            int ok = 1;
+            for (int t = 0; t < 2; ++t) {
+                och_terrain_params tp;
+                memset(&tp, 0, sizeof tp);
+                tp.depth = depth;
+                tp.tunnels = 1;
+                tp.dedup = dedup;
+                tp.threads = thread_counts[t];
+                const int st = och_build_terrain(&tp, &built[t]);
+                CHECK(st == OCH_OK, "terrain depth %d dedup %d threads %d: status %d (%s)", depth, dedup, tp.threads, st,
+                      och_last_error());
+                if (st != OCH_OK) built[t].nodes = NULL;
+                ok = ok && st == OCH_OK;
+            }
+            if (ok) {
+                CHECK(built[0].n_nodes == built[1].n_nodes && built[0].root == built[1].root &&
+                          !memcmp(built[0].nodes, built[1].nodes, (size_t)built[0].n_nodes * 32),
+                      "terrain depth %d dedup %d: 1 and 3 threads differ (%u, %u nodes)", depth, dedup, built[0].n_nodes,
+                      built[1].n_nodes);
+                CHECK(built[0].tree_nodes == built[1].tree_nodes && built[0].solid_voxels == built[1].solid_voxels,
+                      "terrain depth %d dedup %d: statistics differ between 1 and 3 threads", depth, dedup);
+                if (dedup) tree_nodes = built[0].tree_nodes;
+                else
+                    CHECK(built[0].n_nodes == tree_nodes && built[0].tree_nodes == tree_nodes,
+                          "terrain depth %d: the expanded tree has %u nodes, tree_nodes %llu / %llu", depth, built[0].n_nodes,
+                          (unsigned long long)built[0].tree_nodes, (unsigned long long)tree_nodes);
+            }
+            for (int t = 0; t < 2; ++t) och_host_pool_free(&built[t]);
+        }
+    }
 
     printf(failures ? "voxel_builder_host_check: %d failures\n" : "voxel_builder_host_check: ok\n", failures);
     return failures != 0;
