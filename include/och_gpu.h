@@ -708,6 +708,42 @@ typedef struct och_voxel_params {
 } och_voxel_params;
 OCH_API int och_build_voxels(const och_voxel_params *params, och_host_pool *out);
 
+/* A batch of voxel edits applied to an existing pool.  Let V be the pool's
+ * voxels (every (x, y, z) where och_pool_at is non-zero) and V' be V after the
+ * records, applied in order as h_octree::set calls (a later record wins, id 0
+ * removes, a coordinate outside [0, dim) is ignored, ids are any uint32).  The
+ * result is the canonical pool of V' in och_build_voxels' form, slot for slot
+ * the pool och_build_voxels gives for V listed in any order followed by the
+ * records; its statistics are those of the result.  GPU and host path give the
+ * same bytes.
+ * The input pool need not be canonical: only nodes reachable from root are
+ * read; duplicates, any slot order, unused or garbage slots and reachable
+ * all-zero nodes (which count as no node) are accepted, so n = 0 canonicalises
+ * an editor's slot array (och_editor_nodes).  A node must lie at one height.
+ * Refused before *out is touched -- OCH_E_INVALID: depth outside 1..21,
+ * n >= 2^31, on_device without use_gpu, nodes NULL with n_nodes > 0, records
+ * NULL with n > 0, root > n_nodes, an interior node's child word > n_nodes, a
+ * node reachable at two heights.  OCH_E_CAPACITY: the caller's capacity is too
+ * small.  OCH_E_NOMEM, OCH_E_NODEV, OCH_E_HIP as the builders.
+ * Every call uploads, adopts, renumbers and returns the whole pool in host
+ * memory; nothing stays on the device between calls.
+ * OCH_BUILD_TRACE=1 prints phase times ("edit gpu " / "edit host "). */
+typedef struct och_edit_params {
+    const uint32_t *nodes;  /* the pool to edit, host memory: n_nodes x 8, 1-based (h_octree form) */
+    uint32_t n_nodes;
+    uint32_t root;          /* 0 = a world without voxels */
+    int32_t depth;          /* 1..21 */
+    const void *records;    /* n x 4 uint32 (x, y, z, id), as OCH_VOXELS_LIST */
+    uint64_t n;             /* < 2^31; 0 = canonicalise only */
+    int32_t on_device;      /* records are device memory (use_gpu = 1 only), writes complete */
+    int32_t use_gpu, threads;
+    uint32_t capacity;      /* node ids to reserve, id 0 included; 0 = the bound: the reachable input
+                               nodes + one id per row of the records' own tree (the level counts of
+                               the unique in-range keys, id 0 included) + 1.  Less is enough when
+                               nodes are shared: the distinct nodes of both trees + 1 on the GPU */
+} och_edit_params;
+OCH_API int och_edit_voxels(const och_edit_params *params, och_host_pool *out);
+
 /* The packed device layout (OCH_OPT_LAYOUT 1) of a pool, on the host: node 0
  * is zero padding, ids are breadth-first per level, interior slots hold
  * child_id | child_mask << 24, leaf-level slots voxel ids; *out_root =

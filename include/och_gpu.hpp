@@ -240,6 +240,15 @@ inline host_pool build_voxels(const och_voxel_params &params)
     return p;
 }
 
+// A batch of set() records applied to an existing 1-based pool (och_edit_params):
+// the canonical pool of its voxels after the records, as build_voxels returns it.
+inline host_pool edit_voxels(const och_edit_params &params)
+{
+    host_pool p;
+    check(och_edit_voxels(&params, p.out()), "och_edit_voxels");
+    return p;
+}
+
 // Every GPU of the node from one host thread: a pool replica
 // per device, row chunks dealt round-robin, one RCCL all-gather, shading on
 // every device.  frames(rank) is device rank's [views][H][W] RGBA8 copy.

@@ -71,6 +71,13 @@ class VoxelParams(C.Structure):
                 ("on_device", C.c_int32), ("use_gpu", C.c_int32), ("threads", C.c_int32), ("capacity", C.c_uint32)]
 
 
+class EditParams(C.Structure):
+    """och_edit_params: a pool and the records to apply to it, for och_edit_voxels."""
+    _fields_ = [("nodes", C.c_void_p), ("n_nodes", C.c_uint32), ("root", C.c_uint32), ("depth", C.c_int32),
+                ("records", C.c_void_p), ("n", C.c_uint64), ("on_device", C.c_int32), ("use_gpu", C.c_int32),
+                ("threads", C.c_int32), ("capacity", C.c_uint32)]
+
+
 class HostPool(C.Structure):
     _fields_ = [("nodes", C.POINTER(C.c_uint32)), ("n_nodes", C.c_uint32), ("root", C.c_uint32),
                 ("depth", C.c_int32), ("index_base", C.c_int32), ("solid_voxels", C.c_uint64),
@@ -150,6 +157,7 @@ PROTOTYPES = {
     "och_gpu_shade_unshard_views_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "och_build_terrain": (C.c_int, [C.POINTER(TerrainParams), C.POINTER(HostPool)]),
     "och_build_voxels": (C.c_int, [C.POINTER(VoxelParams), C.POINTER(HostPool)]),
+    "och_edit_voxels": (C.c_int, [C.POINTER(EditParams), C.POINTER(HostPool)]),
     "och_host_pool_free": (None, [C.POINTER(HostPool)]),
     "och_pool_pack": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "och_pool_at": (_u32, [_P, _u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

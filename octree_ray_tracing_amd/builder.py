@@ -15,7 +15,7 @@ from pathlib import Path
 
 import numpy as np
 
-from ._lib import HostPool, TerrainParams, VoxelParams, call
+from ._lib import EditParams, HostPool, OchError, TerrainParams, VoxelParams, call
 
 
 @dataclass
@@ -119,6 +119,43 @@ def _build(name: str, params) -> NodePool:
 VOXELS_LIST, VOXELS_GRID_U8, VOXELS_GRID_U32 = 0, 1, 2
 
 
+def _device_records(voxels, use_gpu: bool, who: str):
+    """A CUDA tensor of records as (tensor to keep alive, device pointer, n), its writes complete."""
+    if not use_gpu:
+        raise ValueError(f"{who}: a device tensor needs use_gpu=True")
+    import torch
+
+    if voxels.dim() != 2 or voxels.shape[1] != 4 or voxels.dtype not in (torch.int32, torch.uint32):
+        raise ValueError(f"{who}: a device list is an (n, 4) int32 / uint32 tensor, not "
+                         f"{tuple(voxels.shape)} {voxels.dtype}")
+    if voxels.device.index != torch.cuda.current_device():
+        raise ValueError(f"{who}: the tensor is on {voxels.device}, the current device is "
+                         f"{torch.cuda.current_device()}")
+    voxels = voxels.contiguous()
+    torch.cuda.current_stream().synchronize()      # the build reads on a stream of its own
+    return voxels, voxels.data_ptr(), voxels.shape[0]
+
+
+def _host_records(voxels: np.ndarray, who: str) -> np.ndarray:
+    """An (n, 4) integer array of any width as contiguous uint32 records."""
+    if voxels.dtype.kind not in "iu":
+        raise ValueError(f"{who}: records are integers, not {voxels.dtype}")
+    if voxels.dtype.itemsize != 4:
+        wide = voxels.astype(np.int64)
+        if wide.size and not (0 <= wide[:, 3].min() and wide[:, 3].max() <= 0xFFFFFFFF):
+            raise ValueError(f"{who}: a voxel id outside uint32")
+        outside = ((wide[:, :3] < 0) | (wide[:, :3] > 0xFFFFFFFF)).any(axis=1)
+        wide[outside, :3] = 0xFFFFFFFF         # outside any tree: ignored
+        voxels = wide.astype(np.uint32)
+    return np.ascontiguousarray(voxels).view(np.uint32)
+
+
+def _capacity(capacity, who: str) -> int:
+    if not 0 <= int(capacity) <= 0xFFFFFFFF:
+        raise ValueError(f"{who}: capacity {capacity} outside uint32")
+    return int(capacity)
+
+
 def build_voxels(voxels, depth: int | None = None, use_gpu: bool = False, threads: int = 0, capacity: int = 0) -> NodePool:
     """A DAG from the caller's voxels (och_build_voxels), the same canonical pool whatever the path,
     the record order or the input kind.
@@ -133,32 +170,12 @@ def build_voxels(voxels, depth: int | None = None, use_gpu: bool = False, thread
         voxels = voxels.numpy()
     on_device = hasattr(voxels, "is_cuda")
     if on_device:
-        if not use_gpu:
-            raise ValueError("build_voxels: a device tensor needs use_gpu=True")
-        import torch
-
-        if voxels.dim() != 2 or voxels.shape[1] != 4 or voxels.dtype not in (torch.int32, torch.uint32):
-            raise ValueError(f"build_voxels: a device list is an (n, 4) int32 / uint32 tensor, not "
-                             f"{tuple(voxels.shape)} {voxels.dtype}")
-        if voxels.device.index != torch.cuda.current_device():
-            raise ValueError(f"build_voxels: the tensor is on {voxels.device}, the current device is "
-                             f"{torch.cuda.current_device()}")
-        voxels = voxels.contiguous()
-        torch.cuda.current_stream().synchronize()      # the build reads on a stream of its own
-        kind, n, ptr = VOXELS_LIST, voxels.shape[0], voxels.data_ptr()
+        voxels, ptr, n = _device_records(voxels, use_gpu, "build_voxels")
+        kind = VOXELS_LIST
     else:
         voxels = np.asarray(voxels)
         if voxels.ndim == 2 and voxels.shape[1] == 4:
-            if voxels.dtype.kind not in "iu":
-                raise ValueError(f"build_voxels: records are integers, not {voxels.dtype}")
-            if voxels.dtype.itemsize != 4:
-                wide = voxels.astype(np.int64)
-                if wide.size and not (0 <= wide[:, 3].min() and wide[:, 3].max() <= 0xFFFFFFFF):
-                    raise ValueError("build_voxels: a voxel id outside uint32")
-                outside = ((wide[:, :3] < 0) | (wide[:, :3] > 0xFFFFFFFF)).any(axis=1)
-                wide[outside, :3] = 0xFFFFFFFF         # outside any tree: ignored
-                voxels = wide.astype(np.uint32)
-            voxels = np.ascontiguousarray(voxels).view(np.uint32)
+            voxels = _host_records(voxels, "build_voxels")
             kind, n = VOXELS_LIST, voxels.shape[0]
         elif voxels.ndim == 3:
             side = voxels.shape[0]
@@ -176,10 +193,59 @@ def build_voxels(voxels, depth: int | None = None, use_gpu: bool = False, thread
         ptr = voxels.ctypes.data
     if depth is None:
         raise ValueError("build_voxels: a record list needs depth")
-    if not 0 <= int(capacity) <= 0xFFFFFFFF:
-        raise ValueError(f"build_voxels: capacity {capacity} outside uint32")
-    params = VoxelParams(int(depth), kind, ptr, int(n), int(on_device), int(bool(use_gpu)), int(threads), int(capacity))
+    params = VoxelParams(int(depth), kind, ptr, int(n), int(on_device), int(bool(use_gpu)), int(threads),
+                         _capacity(capacity, "build_voxels"))
     return _build("och_build_voxels", params)
+
+
+def edit_voxels(tree, voxels, use_gpu: bool = False, threads: int = 0, capacity: int = 0) -> NodePool:
+    """A batch of voxel edits applied to an existing world (och_edit_voxels): the canonical pool of the
+    tree's voxels after the records, the pool build_voxels gives for those voxels followed by the
+    records, slot for slot, whatever the path.
+
+    tree is a NodePool with index_base 1 or a (nodes, root, depth) tuple in that form; it need not be
+    canonical (an Editor's nodes() will do: only what the root reaches is read).  voxels is a record
+    list as build_voxels takes it, on the host or, with use_gpu=True, a CUDA tensor; no records
+    canonicalise the tree.  capacity = node ids to reserve, 0 = the reachable nodes + the rows of the
+    records' own tree + 1."""
+    if isinstance(tree, NodePool):
+        if tree.index_base != 1:
+            raise OchError(-1, "och_edit_voxels", "a pool with index_base 1 (h_octree form), not an och::octree pool")
+        tree = (tree.nodes, tree.root, tree.depth)
+    nodes, root, depth = tree
+    nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 8)
+    if hasattr(voxels, "is_cuda") and not voxels.is_cuda:
+        voxels = voxels.numpy()
+    on_device = hasattr(voxels, "is_cuda")
+    if on_device:
+        voxels, ptr, n = _device_records(voxels, use_gpu, "edit_voxels")
+    else:
+        voxels = np.asarray(voxels)
+        if voxels.ndim != 2 or voxels.shape[1] != 4:
+            raise ValueError(f"edit_voxels: an (n, 4) record list, not shape {voxels.shape}")
+        voxels = _host_records(voxels, "edit_voxels")
+        ptr, n = voxels.ctypes.data, voxels.shape[0]
+    if not 0 <= int(root) <= 0xFFFFFFFF:
+        raise ValueError(f"edit_voxels: root {root} outside uint32")
+    params = EditParams(nodes.ctypes.data, nodes.shape[0], int(root), int(depth), ptr, int(n), int(on_device),
+                        int(bool(use_gpu)), int(threads), _capacity(capacity, "edit_voxels"))
+    return _build("och_edit_voxels", params)
+
+
+def box_records(lo, hi, id: int) -> np.ndarray:
+    """The (n, 4) uint32 records (x, y, z, id) of the box lo <= (x, y, z) < hi, x fastest, then y, then z:
+    one brush stroke for edit_voxels (the reference's is box_records(c - 20, c + 20, v)).  An empty box
+    gives (0, 4).  A coordinate below 0 wraps to one outside any tree, which an edit ignores."""
+    if not 0 <= int(id) <= 0xFFFFFFFF:
+        raise ValueError(f"box_records: id {id} outside uint32")
+    lo, hi = np.asarray(lo, np.int64).reshape(3), np.asarray(hi, np.int64).reshape(3)
+    nx, ny, nz = (int(v) for v in np.maximum(hi - lo, 0))
+    rec = np.empty((nz, ny, nx, 4), np.uint32)
+    rec[..., 0] = (lo[0] + np.arange(nx)).astype(np.uint32)[None, None, :]
+    rec[..., 1] = (lo[1] + np.arange(ny)).astype(np.uint32)[None, :, None]
+    rec[..., 2] = (lo[2] + np.arange(nz)).astype(np.uint32)[:, None, None]
+    rec[..., 3] = int(id)
+    return rec.reshape(-1, 4)
 
 
 def occupied_box(nodes: np.ndarray, root: int, depth: int, index_base: int = 1):

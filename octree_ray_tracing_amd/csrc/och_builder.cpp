@@ -1,9 +1,11 @@
 // och_builder.cpp -- the builders' C-ABI entries (och_build_terrain,
-// och_build_voxels, och_host_pool_free) and the terrain builder: the demo
-// terrain's canonical DAG, built bottom-up in parallel.  The DAG stores, their
-// kernels and the renumbering are och_dag.h's; the voxel builder, which builds
-// the same DAG from a caller's voxels, is och_voxel_build.h.  One translation
-// unit: both headers are included here and nowhere else.
+// och_build_voxels, och_edit_voxels, och_host_pool_free) and the terrain
+// builder: the demo terrain's canonical DAG, built bottom-up in parallel.  The
+// DAG stores, their kernels and the renumbering are och_dag.h's; the voxel
+// builder, which builds the same DAG from a caller's voxels, is
+// och_voxel_build.h; the batch editor, which applies a list of edits to an
+// existing pool, is och_voxel_edit.h.  One translation unit: the headers are
+// included here and nowhere else.
 //
 // The reference builds its tree by recursive create_volume + per-voxel
 // h_octree::set edits (ORT/test_och_h_octree.cpp:651-695, :767-787;
@@ -32,6 +34,7 @@
 #include "och_dag.h"
 #include "och_terrain.h"
 #include "och_voxel_build.h"
+#include "och_voxel_edit.h"
 
 namespace {
 
@@ -519,6 +522,36 @@ OCH_API int och_build_voxels(const och_voxel_params *params, och_host_pool *out)
                              : build_voxels_host(P, P.threads > 0 ? P.threads : default_threads(), &nodes, &n_out, root, vs, phase);
     if (st != OCH_OK) return report_build(st, "voxel builder", "allocation failed");
     phase(P.use_gpu ? "gpu, whole" : "renumber");
+    return finish_pool(out, nodes, n_out, root, 1, P.depth, vs, t_start);
+}
+
+OCH_API int och_edit_voxels(const och_edit_params *params, och_host_pool *out)
+{
+    if (!params || !out) return och::report(OCH_E_INVALID, "och_edit_voxels: null argument");
+    const och_edit_params &P = *params;
+    if (P.depth < 1 || P.depth > kMaxVoxelDepth)
+        return och::report(OCH_E_INVALID, "och_edit_voxels: depth must be 1..21 (a Morton key of 3 * depth bits and the "
+                                          "out-of-range bit fill 64 bits)");
+    if (P.n >= (1ull << 31)) return och::report(OCH_E_INVALID, "och_edit_voxels: a list holds fewer than 2^31 records");
+    if (P.on_device && !P.use_gpu) return och::report(OCH_E_INVALID, "och_edit_voxels: device records need use_gpu = 1");
+    if (!P.nodes && P.n_nodes) return och::report(OCH_E_INVALID, "och_edit_voxels: nodes is null");
+    if (!P.records && P.n) return och::report(OCH_E_INVALID, "och_edit_voxels: records is null");
+    if (P.root > P.n_nodes) return och::report(OCH_E_INVALID, "och_edit_voxels: root lies past the pool's end");
+    const auto t_start = std::chrono::steady_clock::now();
+    PhaseTimer phase{P.use_gpu ? "edit gpu " : "edit host ", 4};
+    // *out is written only by finish_pool: a refused edit leaves it as it was
+    BuildStats vs;
+    uint32_t root = 0, n_out = 0;
+    uint32_t *nodes = nullptr;
+    const int st = P.use_gpu ? edit_voxels_gpu(P, &nodes, &n_out, root, vs)
+                             : edit_voxels_host(P, P.threads > 0 ? P.threads : default_threads(), &nodes, &n_out, root, phase);
+    if (st == OCH_E_INVALID) return st;   // reported where it was found
+    if (st != OCH_OK) return report_build(st, "voxel editor", "allocation failed");
+    phase(P.use_gpu ? "gpu, whole" : "renumber");
+    if (!P.use_gpu) {
+        pool_stats(nodes, n_out, root, P.depth, vs);
+        phase("statistics");
+    }
     return finish_pool(out, nodes, n_out, root, 1, P.depth, vs, t_start);
 }
 

@@ -12,8 +12,9 @@
 // harmless for tracing, impossible to renumber.
 //
 // Included by och_builder.cpp only (one translation unit, hence the unnamed
-// namespace): the terrain builder there and the voxel builder
-// (och_voxel_build.h) are written on top of this file and share nothing else.
+// namespace): the terrain builder there, the voxel builder (och_voxel_build.h)
+// and, on top of that one, the batch editor (och_voxel_edit.h) are written on
+// top of this file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
@@ -419,7 +420,7 @@ struct GpuStore {
     uint32_t *next;                  // id counter, starts at 1 (0 = empty)
     uint32_t *table;                 // tmask + 1 slots: 0, kCand | node index (this level), or an id
     uint32_t *leaf_id;               // 2^24 leaf codes -> id
-    uint32_t *overflow;              // 1: capacity exhausted, 2: table exhausted, 4: a row outside its level (k_vox_rows)
+    uint32_t *overflow;              // 1: capacity exhausted, 2: table exhausted, 4: a row outside its level (k_vox_rows, k_edit_rows)
     unsigned long long *tree_nodes;  // kCounters partial counts of expanded-tree nodes, 128 B apart
     uint32_t cap, tmask;
 };
@@ -556,21 +557,24 @@ __global__ __launch_bounds__(256) void k_intern(GpuStore S, GpuLevel L, uint32_t
 // a wavefront whose row equals its first lane's leave the probe to that lane
 // and take its rep value through the registers, so one slot sees a wavefront's
 // worth fewer compare-and-swaps while the claim is still invisible to others.
+// kEmptyRows (the voxel editor's rows): a row of zeros is no node, its rep
+// value is 0 and it never probes or claims a table slot.
+template <bool kEmptyRows>
 __global__ __launch_bounds__(256) void k_intern_rows(GpuStore S, GpuLevel L, uint32_t *__restrict__ rep,
                                                      uint32_t *__restrict__ slot)
 {
     const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = idx < L.count;
     uint32_t c[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (live) gather(S, L, idx, c);
+    const bool any = live && gather(S, L, idx, c);
     // lane 0 of a wavefront is live whenever any of its lanes is (idx ascends)
     bool follows = live && (threadIdx.x & 63u) != 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) follows &= __shfl(c[k], 0) == c[k];
     uint32_t r = 0;
     if (live) slot[idx] = kNoSlot;
-    if (live && !follows) r = probe_node(S, L, idx, c, slot);
-    const uint32_t lead = __shfl(r, 0);   // an id or kCand | index, both final for an equal row
+    if (live && !follows && (!kEmptyRows || any)) r = probe_node(S, L, idx, c, slot);
+    const uint32_t lead = __shfl(r, 0);   // an id or kCand | index (or 0), all final for an equal row
     if (live) rep[idx] = follows ? lead : r;
 }
 
@@ -679,11 +683,19 @@ __global__ __launch_bounds__(256) void k_bfs_output(const uint32_t *__restrict__
     out[q] = (level[v] == 0 || !c) ? c : newid[c];
 }
 
+// The renumbered pool where renumber_gpu left it on the device (the scope's
+// memory), for a caller that goes on there: ids lo .. lo + level_counts[l] - 1
+// are the nodes at depth l, lo = 1 + the counts before it.
+struct DevicePool {
+    const uint32_t *nodes = nullptr;   // n_out x 8
+    std::vector<uint32_t> level_counts;
+};
+
 // The store's nodes reachable from root (!= 0), renumbered breadth-first and
 // 1-based on the device (k_bfs_*), with buffers of the build's scope.
 // *out: malloc'd n_out x 8 words, as renumber().
 int renumber_gpu(const GpuStore &S, uint32_t used, uint32_t root, int depth, GpuScope &G, uint32_t **out, uint32_t *n_out,
-                 bool trace)
+                 bool trace, DevicePool *dev = nullptr)
 {
     const auto t_bfs = std::chrono::steady_clock::now();
     const hipStream_t st = G.st;
@@ -705,6 +717,7 @@ int renumber_gpu(const GpuStore &S, uint32_t used, uint32_t root, int depth, Gpu
     uint32_t off = 0, f = 1;
     for (int l = 1; l < depth && f; ++l) {
         const uint32_t nc = 8 * f, next = off + f;
+        if (dev) dev->level_counts.push_back(f);
         hipLaunchKernelGGL(k_bfs_first, blocks(nc), dim3(256), 0, st, S.nodes, d_order + off, f, d_first);
         hipLaunchKernelGGL(k_bfs_mark, blocks(nc), dim3(256), 0, st, S.nodes, d_order + off, f, d_first, d_mark);
         GPU_TRY(hipGetLastError());
@@ -720,6 +733,10 @@ int renumber_gpu(const GpuStore &S, uint32_t used, uint32_t root, int depth, Gpu
         f = tail[0] + tail[1];
     }
     const uint32_t n = off + f;
+    if (dev) {
+        dev->level_counts.push_back(f);
+        dev->nodes = d_out;
+    }
     hipLaunchKernelGGL(k_bfs_output, blocks((size_t)n * 8), dim3(256), 0, st, S.nodes, S.level, d_order, d_newid, n, d_out);
     GPU_TRY(hipGetLastError());
     uint32_t *nodes = static_cast<uint32_t *>(std::malloc((size_t)n * 32));

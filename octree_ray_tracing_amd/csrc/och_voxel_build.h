@@ -316,7 +316,7 @@ int build_voxels_gpu(const och_voxel_params &P, uint32_t **out, uint32_t *n_out,
         hipLaunchKernelGGL(k_vox_rows, blocks(n_in), dim3(256), 0, st, d_keys[cur], d_words[cur], n_in, d_flags, d_pos, n_rows,
                            d_rows, d_keys[cur ^ 1], S.overflow);
         GpuLevel L{d_rows, 0, 0, n_rows, h, 1};
-        hipLaunchKernelGGL(k_intern_rows, blocks(n_rows), dim3(256), 0, st, S, L, d_rep, d_slot);
+        hipLaunchKernelGGL(k_intern_rows<false>, blocks(n_rows), dim3(256), 0, st, S, L, d_rep, d_slot);
         hipLaunchKernelGGL(k_settle, blocks(n_rows), dim3(256), 0, st, S, n_rows, d_rep, d_slot, d_words[cur ^ 1], nullptr);
         GPU_TRY(hipGetLastError());
         cur ^= 1;
