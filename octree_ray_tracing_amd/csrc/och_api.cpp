@@ -1,1048 +1,24 @@
-// och_api.cpp -- the C ABI (include/och_gpu.h): pools, RCPPS capture, camera
-// constants, synchronous and asynchronous trace / render entry points.
-#include <hip/hip_runtime.h>
-#include <immintrin.h>
-
+// och_api.cpp -- the C ABI's launches (include/och_gpu.h): per-launch timing,
+// the plan and tile table a camera launch takes, the trace, batch, render,
+// supersampled, lit and code entries with their argument checks, the planning
+// renders (och_gpu_plan_*, och_gpu_chunk_costs), the row deal, the unshard and
+// shade entries and the frame loops, single and sharded.  The pool itself, its
+// settings and the error text are och_pool.cpp; the planners' arithmetic is
+// och_plan.cpp, the tile table's och_tiles.cpp, the RCPPS table's och_rcp.cpp.
 #include <algorithm>
-#include <atomic>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <mutex>
-#include <string>
-#include <unordered_map>
-#include <utility>
-#include <vector>
 
-#include "och_host.h"
+#include "och_plan.h"
+#include "och_pool.h"
 
+using och::check_ready;
 using och::check_views;
 using och::DevBuf;
 using och::DeviceGuard;
+using och::ensure_scratch;
 using och::fail;
-
-namespace {
-
-constexpr uint32_t kIdLimit = 1u << 24;   // packed ids are 24 bits
-
-thread_local std::string g_error;
-
-}  // namespace
-
-int och::fail(int status, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_error = buf;
-    return status;
-}
-
-namespace {
-
-thread_local const char *t_entry = nullptr;     // outermost C-ABI entry of this thread
-
-// The first pending HIP error a launcher cleared since the last reset, process
-// wide (the frame group issues from one thread per device), and how many.
-struct Discarded {
-    std::mutex m;
-    int code = 0;
-    int count = 0;
-    std::string what;
-};
-
-Discarded &discarded()
-{
-    static Discarded d;
-    return d;
-}
-
-// ------------------------------------------------------------ RCPPS capture
-
-inline uint32_t rcpps_native(uint32_t x)
-{
-    const __m128 r = _mm_rcp_ps(_mm_castsi128_ps(_mm_set1_epi32((int)x)));
-    return (uint32_t)_mm_cvtsi128_si32(_mm_castps_si128(r));
-}
-
-struct HostRcp {
-    int status = OCH_OK;
-    int log2_entries = 0;
-    std::vector<uint32_t> lut;
-    std::string error;
-};
-
-const HostRcp &host_rcp()
-{
-    static HostRcp cap;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        const uint32_t n = 1u << 23;
-        std::vector<uint32_t> full(n);
-        for (uint32_t m = 0; m < n; m += 4) {
-            const __m128i x = _mm_set_epi32((int)(0xBF800000u | (m + 3)), (int)(0xBF800000u | (m + 2)),
-                                            (int)(0xBF800000u | (m + 1)), (int)(0xBF800000u | m));
-            _mm_storeu_si128((__m128i *)&full[m], _mm_castps_si128(_mm_rcp_ps(_mm_castsi128_ps(x))));
-        }
-        // Smallest k such that the result only depends on the top k mantissa bits.
-        int k = 23;
-        for (int cand = 8; cand <= 23; ++cand) {
-            const uint32_t block = 1u << (23 - cand);
-            bool ok = true;
-            for (uint32_t m = 0; m < n && ok; ++m) ok = full[m] == full[m & ~(block - 1)];
-            if (ok) { k = cand; break; }
-        }
-        cap.log2_entries = k;
-        cap.lut.resize(1u << k);
-        for (uint32_t i = 0; i < (1u << k); ++i) cap.lut[i] = full[(size_t)i << (23 - k)];
-        // Check the exponent model on every exponent (negative inputs, as the tracer uses).
-        for (uint32_t e = 0; e < 256 && cap.status == OCH_OK; ++e)
-            for (uint32_t m = 0; m < n; m += (e == 127 ? 1u : 997u)) {
-                const uint32_t x = 0x80000000u | (e << 23) | m;
-                if (e == 255 && m) continue;   // NaN payload handling is not used by the tracer
-                const uint32_t want = rcpps_native(x);
-                const uint32_t got = och_rcp_from_lut(x, cap.lut.data(), k);
-                if (want != got) {
-                    cap.status = OCH_E_RCP_MODEL;
-                    char buf[160];
-                    snprintf(buf, sizeof buf, "host RCPPS(0x%08x) = 0x%08x, table model gives 0x%08x", x, want, got);
-                    cap.error = buf;
-                    break;
-                }
-            }
-    });
-    return cap;
-}
-
-// One cost-planned launch order (och_gpu_plan_views, och_gpu_plan_batch_tiled)
-// and the launch it was planned for (frame_key, batch_key).
-struct LaunchPlan {
-    DevBuf<uint32_t> order;         // OCH_OPT_TILE_ORDER = 2
-    DevBuf<uint32_t> order_xcd;     // OCH_OPT_TILE_ORDER = 3: grouped per XCD
-    uint32_t blocks = 0;            // entries of the current plan (its launch's grid)
-    std::vector<uint32_t> h_order, h_order_xcd;   // the host's copies: tile tables bake them in (use_tiles)
-    uint64_t serial = 0;            // och_gpu_pool::plan_serial when the plan was made (tile-table keys)
-    int64_t key[9] = {};
-    // no plan until a new one is in place: later launches run in natural order
-    void invalidate() { key[0] = -1; }
-    bool matches(const int64_t k[9]) const { return order.d && std::memcmp(k, key, sizeof key) == 0; }
-};
-
-// The primary plan's split form (OCH_OPT_SPLIT, plan_split): the heavy tiles'
-// split waves first, then the plan's other workgroups, and the waves' task
-// rows; valid with plans[0]'s key while params matches the options it was
-// made with
-struct SplitPlan {
-    DevBuf<uint32_t> order, tasks;
-    std::vector<uint32_t> h_order, h_tasks;       // the host's copies (use_tiles)
-    uint32_t n = 0, extra = 0, tiles = 0;
-    int params[3] = {0, 0, 0};      // threshold, segments, level
-    void invalidate() { n = extra = tiles = params[0] = params[1] = params[2] = 0; }
-};
-
-// One camera launch as the kernels run it (och::plan::tile_table), on the
-// device, and the launch it was made for.  The pool keeps the last few: a frame
-// loop's geometry, sharding and plan stay the same from frame to frame, so
-// after the first frame a launch only looks its table up.
-struct TileTable {
-    DevBuf<uint64_t> d;
-    uint32_t n = 0, grid = 0, block = 0;
-    int64_t key[12] = {};
-    uint64_t used = 0;              // och_gpu_pool::tile_clock at the last launch; 0 = empty
-};
-
-}  // namespace
-
-// ------------------------------------------------------------ pool object
-
-struct och_gpu_pool {
-    int device = 0;
-    DevBuf<uint32_t> d_nodes;       // with one padding node in front for 1-based pools
-    uint32_t n_nodes = 0;           // nodes in d_nodes
-    uint32_t root = 0;
-    int depth = 0;
-    int index_base = 1;
-    float miss_t = INFINITY;
-    DevBuf<uint32_t> d_lut;         // .d: the pool has an RCPPS table
-    int lut_log2 = 0;
-    uint32_t rcp_xlo = 0, rcp_xspan = 0;   // DevPool::rcp_xlo / rcp_xspan of the uploaded table
-    double lut_error = INFINITY;    // maximum relative error of the table (lut_max_rel_error)
-    DevBuf<uint32_t> d_palette;
-    uint32_t n_voxels = 0;
-    DevBuf<uint32_t> d_code_table;  // .d: OCH_CODE_* -> RGBA8 (256 words), when n_voxels <= OCH_CODE_MAX_VOXELS
-    hipStream_t own_stream = nullptr;
-    hipStream_t ext_stream = nullptr;
-    bool use_ext = false;           // och_gpu_set_stream called: ext_stream (NULL = null stream)
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    bool timed = false;
-    // schedule (och_gpu_set_option)
-    int opt_block = 64;
-    uint64_t *stamps = nullptr;
-    uint32_t stamp_cap = 0;
-    // host mirror of the uploaded nodes (user numbering), for validating edits
-    std::vector<uint32_t> mirror;
-    // packed layout (see och_internal.h DevPool)
-    DevBuf<uint32_t> d_packed;      // .d: a packed layout exists
-    uint32_t packed_root = 0;
-    uint32_t packed_nodes = 0;
-    bool packed_by_slot = false;    // d_packed numbered like d_nodes (editor flushes)
-    uint64_t serial = 0;            // process-unique, never reused (och::pool_serial)
-    uint64_t last_writer = 0;       // editor id of the last och::pool_commit, 0 otherwise
-    bool torn = false;              // a failed editor flush left the slots half written (och::pool_mark_torn)
-    int opt_layout = 1;
-    int opt_tile_order = 0;
-    int opt_bounce_compact = 1;
-    int opt_cull = 1;
-    int opt_timing = 1;                        // OCH_OPT_TIMING
-    int opt_plan = 10;                         // OCH_OPT_PLAN (shape of och_gpu_plan_views' order)
-    int opt_split = 0;                         // OCH_OPT_SPLIT: heavy-tile threshold, % of the costliest tile (0 off)
-    int opt_split_segs = 4;                    // OCH_OPT_SPLIT_SEGS: lanes per heavy tile's ray (2, 4, 8, 16)
-    int opt_split_level = 6;                   // OCH_OPT_SPLIT_LEVEL: the level whose cells are the segments
-    hipEvent_t next_ev_start = nullptr;        // och_gpu_set_launch_events: the next launch's events
-    hipEvent_t next_ev_stop = nullptr;
-    // bounding box of the pool's voxels (voxel units, [lo, hi)), for the cull
-    bool box_any = false;
-    int32_t box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
-    // host-call staging
-    DevBuf<char> scratch;
-    // editor flush staging (och::pool_scatter_slots): pinned host + device, grown on demand
-    uint32_t *h_stage = nullptr;
-    size_t stage_words = 0;
-    DevBuf<uint32_t> d_stage;
-    // cost-planned launch orders (och_gpu_plan_views, OCH_OPT_TILE_ORDER = 2)
-    // [0] primary frames (grid kernel), [1] config-5 frames (bounce kernel),
-    // [2] tiled trace batches (och_gpu_plan_batch_tiled)
-    LaunchPlan plans[3];
-    SplitPlan split;
-    uint64_t plan_serial = 0;                 // counts the plans made (och_gpu_plan_views)
-    TileTable tile_tables[8];                 // camera launches' tile tables (use_tiles), least recently used out first
-    uint64_t tile_clock = 0;
-    // row deal (och_gpu_set_row_deal): for frames of deal_h rows in chunks of
-    // deal_chunk over deal_n shards, chunk g belongs to a chosen shard instead
-    // of g % n; slices hold deal_max chunks (the largest shard's, the rest padded)
-    int deal_h = 0, deal_chunk = 0, deal_n = 0, deal_max = 0;
-    uint64_t deal_serial = 0;                 // changes with every deal (plan keys)
-    DevBuf<int32_t> d_chunk_map;              // [deal_n][deal_max] global chunk, -1 = padding
-    std::vector<int32_t> h_chunk_map;         // and the host's copy (tile tables)
-    DevBuf<int32_t> d_owner;                  // [n_chunks] shard << 16 | local chunk
-    std::vector<int32_t> deal_table;          // the chunk -> shard table as set
-    bool deal_for(int H, int rc, int n) const { return deal_n && H == deal_h && rc == deal_chunk && n == deal_n; }
-    int slice_rows(int H, int rc, int n) const { return deal_for(H, rc, n) ? deal_max * rc : och_shard_rows(H, rc, n); }
-
-    hipStream_t stream() const { return use_ext ? ext_stream : own_stream; }
-
-    // No packed layout: launches walk the raw one until a new one is in place.
-    hipError_t drop_packed()
-    {
-        packed_nodes = 0;
-        packed_by_slot = false;
-        return d_packed.release();
-    }
-
-    och::Schedule schedule() const
-    {
-        och::Schedule sc = {};          // no order, no cost output, no split, no events
-        sc.block = opt_block;
-        sc.tile_order = opt_tile_order;
-        sc.bounce_compact = opt_bounce_compact;
-        sc.stamps = stamps;
-        sc.stamp_cap = stamp_cap;
-        return sc;
-    }
-
-    och::DevPool dev() const
-    {
-        och::DevPool p;
-        const bool pk = opt_layout == 1 && d_packed.d;
-        p.nodes = pk ? d_packed.d : d_nodes.d;
-        p.n_slots = 8u * (pk ? packed_nodes : n_nodes);
-        p.packed = pk ? 1 : 0;
-        p.lut = d_lut.d;
-        p.rcp_xlo = rcp_xlo;
-        p.rcp_xspan = rcp_xspan;
-        p.root = pk ? packed_root : root;
-        p.depth = depth;
-        p.lut_shift = 23 - lut_log2;
-        uint32_t mb;
-        std::memcpy(&mb, &miss_t, 4);
-        p.miss_bits = mb;
-        p.half_voxel = std::ldexp(1.0F, -(depth + 1));
-        p.dim_lo = 1u << (23 - depth);
-        p.dim_span = (1u << 22) - p.dim_lo;
-        // 1 + k / 2^depth is an exact float for depth <= 22
-        p.cull = box_any ? opt_cull : 0;
-        p.cam_cull = lut_error <= och::kCameraCullRcpError ? 1 : 0;
-        for (int a = 0; a < 3; ++a) {
-            p.cull_lo[a] = 1.0F + std::ldexp((float)box_lo[a], -depth);
-            p.cull_hi[a] = 1.0F + std::ldexp((float)box_hi[a], -depth);
-        }
-        return p;
-    }
-};
-
-namespace {
-
-int ensure_scratch(och_gpu_pool *p, size_t bytes)
-{
-    OCH_HIP(p->scratch.reserve(bytes));
-    return OCH_OK;
-}
-
-// Launches refuse a pool that a failed editor flush left half written: its
-// slots may name nodes that were never uploaded.
-int check_ready(const och_gpu_pool *p)
-{
-    if (p->torn)
-        return fail(OCH_E_INVALID, "pool left half written by a failed och_editor_flush: flush the editor again");
-    if (!p->d_lut.d) return fail(OCH_E_RCP_MODEL, "no RCPPS table on this pool (call och_gpu_set_rcp_lut)");
-    return OCH_OK;
-}
-
-// Walk every reachable (node, level) pair once and check that interior slots
-// name nodes inside the pool, so no kernel can read out of bounds.
-int validate_pool(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, int base)
-{
-    if (depth < 1 || depth > 22) return fail(OCH_E_INVALID, "depth %d outside 1..22", depth);
-    if (n_nodes == 0) return fail(OCH_E_INVALID, "empty node array");
-    if ((uint64_t)n_nodes + 1 >= (1ull << 29)) return fail(OCH_E_INVALID, "pool of %u nodes exceeds 2^29", n_nodes);
-    auto in_range = [&](uint32_t v) { return base == 1 ? (v >= 1 && v <= n_nodes) : (v < n_nodes); };
-    if (base == 1 && root == 0) return OCH_OK;   // empty h_octree: every ray misses
-    if (!in_range(root)) return fail(OCH_E_INVALID, "root %u outside the pool", root);
-    std::vector<uint32_t> seen(n_nodes, 0);
-    std::vector<uint32_t> cur{root}, next;
-    seen[root - base] |= 1u << 1;
-    for (int level = 1; level < depth; ++level) {
-        next.clear();
-        for (uint32_t v : cur) {
-            const uint32_t *c = nodes + (size_t)(v - base) * 8;
-            for (int k = 0; k < 8; ++k) {
-                if (!c[k]) continue;
-                if (!in_range(c[k]) || (base == 0 && c[k] == 0))
-                    return fail(OCH_E_INVALID, "node %u (level %d) slot %d names %u, outside the pool", v, level, k, c[k]);
-                uint32_t &s = seen[c[k] - base];
-                if (!(s & (1u << (level + 1)))) {
-                    s |= 1u << (level + 1);
-                    next.push_back(c[k]);
-                }
-            }
-        }
-        cur.swap(next);
-    }
-    return OCH_OK;
-}
-
-}  // namespace
-
-// Bounding box of the voxels: one post-order walk over the (node, level)
-// pairs, each box memoised in node-local voxel units (a DAG shares subtrees;
-// a node the caller's table shares between levels gets one entry per level).
-bool och::occupied_box(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, int base, int32_t lo[3],
-                       int32_t hi[3])
-{
-    struct Box {
-        int32_t lo[3], hi[3];
-        bool empty() const { return lo[0] >= hi[0]; }
-    };
-    if ((base == 1 && root == 0) || n_nodes == 0) return false;
-    std::vector<uint8_t> memo_level(n_nodes, 0);     // level + 1 of memo[i], 0 = none
-    std::vector<Box> memo(n_nodes);
-    std::unordered_map<uint64_t, Box> extra;
-    auto walk = [&](auto &self, uint32_t v, int level) -> Box {
-        const uint32_t i = v - base;
-        const uint64_t key = ((uint64_t)i << 5) | (uint64_t)level;
-        if (memo_level[i] == level + 1) return memo[i];
-        if (memo_level[i]) {
-            auto it = extra.find(key);
-            if (it != extra.end()) return it->second;
-        }
-        Box b{{INT32_MAX, INT32_MAX, INT32_MAX}, {INT32_MIN, INT32_MIN, INT32_MIN}};
-        const int32_t half = 1 << (depth - level - 1);   // a child's size in voxels
-        const uint32_t *c = nodes + (size_t)i * 8;
-        for (int k = 0; k < 8; ++k) {
-            if (!c[k]) continue;
-            Box cb{{0, 0, 0}, {1, 1, 1}};                // leaf level: the voxel itself
-            if (level + 1 < depth) {
-                cb = self(self, c[k], level + 1);
-                if (cb.empty()) continue;
-            }
-            for (int a = 0; a < 3; ++a) {
-                const int32_t off = ((k >> a) & 1) * half;
-                b.lo[a] = std::min(b.lo[a], off + cb.lo[a]);
-                b.hi[a] = std::max(b.hi[a], off + cb.hi[a]);
-            }
-        }
-        if (b.lo[0] == INT32_MAX) b = Box{{0, 0, 0}, {0, 0, 0}};
-        if (!memo_level[i]) {
-            memo_level[i] = (uint8_t)(level + 1);
-            memo[i] = b;
-        } else {
-            extra.emplace(key, b);
-        }
-        return b;
-    };
-    const Box b = walk(walk, root, 0);
-    if (b.empty()) return false;
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = b.lo[a];
-        hi[a] = b.hi[a];
-    }
-    return true;
-}
-
-namespace {
-
-void set_box(och_gpu_pool *p, const uint32_t *nodes, uint32_t n_nodes)
-{
-    p->box_any = och::occupied_box(nodes, n_nodes, p->root, p->depth, p->index_base, p->box_lo, p->box_hi);
-}
-
-// Packed layout: every reachable (node, level) pair gets a breadth-first id
-// (1-based; 0 is a zero padding node).  Interior slots become
-// child_id | child_mask << 24, leaf-level slots keep the voxel ids.  A node
-// the caller's table shares between levels (h_octree hash-conses by content
-// alone) is simply emitted once per level.  Returns false when more than
-// 2^24 - 1 ids would be needed.
-bool pack_pool(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, int base,
-               std::vector<uint32_t> &out, uint32_t &packed_root)
-{
-    auto mask_of = [&](uint32_t v) {
-        const uint32_t *c = nodes + (size_t)(v - base) * 8;
-        uint32_t m = 0;
-        for (int k = 0; k < 8; ++k) m |= (uint32_t)(c[k] != 0) << k;
-        return m;
-    };
-    out.assign(8, 0u);                               // padding node 0
-    if (base == 1 && root == 0) {
-        packed_root = 0;
-        return true;
-    }
-    // id of (v, level): first_level[v] / first_id[v] hold the common case, a
-    // map holds the rare extra levels.
-    std::vector<uint8_t> first_level(n_nodes, 0);
-    std::vector<uint32_t> first_id(n_nodes, 0);
-    std::unordered_map<uint64_t, uint32_t> extra;
-    std::vector<uint32_t> order_v;
-    std::vector<uint8_t> order_l;
-    uint32_t next = 1;
-    auto id_of = [&](uint32_t v, int level, bool create) -> uint32_t {
-        const uint32_t i = v - base;
-        if (first_level[i] == level) return first_id[i];
-        if (first_level[i] == 0) {
-            if (!create) return 0;
-            first_level[i] = (uint8_t)level;
-            first_id[i] = next;
-            order_v.push_back(v);
-            order_l.push_back((uint8_t)level);
-            return next++;
-        }
-        const uint64_t key = ((uint64_t)i << 5) | (uint64_t)level;
-        auto it = extra.find(key);
-        if (it != extra.end()) return it->second;
-        if (!create) return 0;
-        extra.emplace(key, next);
-        order_v.push_back(v);
-        order_l.push_back((uint8_t)level);
-        return next++;
-    };
-    id_of(root, 1, true);
-    for (size_t q = 0; q < order_v.size(); ++q) {        // breadth-first: order grows as we go
-        const int level = order_l[q];
-        if (level >= depth) continue;
-        const uint32_t *c = nodes + (size_t)(order_v[q] - base) * 8;
-        for (int k = 0; k < 8; ++k)
-            if (c[k]) id_of(c[k], level + 1, true);
-        if (next > kIdLimit) return false;
-    }
-    out.resize((size_t)next * 8, 0u);
-    for (size_t q = 0; q < order_v.size(); ++q) {
-        const uint32_t v = order_v[q];
-        const int level = order_l[q];
-        const uint32_t *c = nodes + (size_t)(v - base) * 8;
-        uint32_t *o = out.data() + (q + 1) * 8;
-        for (int k = 0; k < 8; ++k) {
-            if (!c[k]) continue;
-            o[k] = level == depth ? c[k] : (id_of(c[k], level + 1, false) | (mask_of(c[k]) << 24));
-        }
-    }
-    packed_root = 1u | (mask_of(root) << 24);
-    return true;
-}
-
-int upload_packed(och_gpu_pool *p, const uint32_t *nodes, uint32_t n_nodes)
-{
-    std::vector<uint32_t> packed;
-    uint32_t proot = 0;
-    OCH_HIP(p->drop_packed());
-    if (!pack_pool(nodes, n_nodes, p->root, p->depth, p->index_base, packed, proot))
-        return OCH_OK;   // raw only
-    OCH_HIP(p->d_packed.upload(packed));
-    p->packed_root = proot;
-    p->packed_nodes = (uint32_t)(packed.size() / 8);
-    return OCH_OK;
-}
-
-// Largest relative error |r * x - 1| of the table model over x in [-2, -1):
-// entry k serves the mantissa bin [k, k + 1) / 2^L, so the extremes are at
-// the bin's ends.  Non-finite or zero entries count as an infinite error.
-double lut_max_rel_error(const uint32_t *lut, int log2_entries)
-{
-    const uint32_t n = 1u << log2_entries;
-    double worst = 0.0;
-    for (uint32_t k = 0; k < n; ++k) {
-        float r;
-        std::memcpy(&r, &lut[k], 4);
-        if (!std::isfinite(r) || r == 0.0F) return INFINITY;
-        const double lo = -(1.0 + (double)k / n), hi = -(1.0 + (double)(k + 1) / n);
-        worst = std::max({worst, std::fabs((double)r * lo - 1.0), std::fabs((double)r * hi - 1.0)});
-    }
-    return worst;
-}
-
-int upload_lut(och_gpu_pool *p, const uint32_t *lut, int log2_entries)
-{
-    if (!lut || log2_entries < 1 || log2_entries > 23) return fail(OCH_E_INVALID, "bad RCPPS table");
-    OCH_HIP(p->d_lut.release());       // no table until the new one is in place
-    // The device table holds every entry + (127 << 23): the kernels' RCPPS of
-    // x = -|d| is then entry - (x's exponent bits) wherever the model's result
-    // exponent ent_e + 127 - e stays in 1..254 and the entry is negative -- for
-    // e in [max(1, max_e - 127), min_e + 126] over this table's entries (och_kernels.hip
-    // rcpps); other x, and every x of a table with a non-negative entry, take
-    // the model itself.
-    const uint32_t n = 1u << log2_entries;
-    std::vector<uint32_t> adj(n);
-    int min_e = 255, max_e = 0;
-    bool negative = true;
-    for (uint32_t k = 0; k < n; ++k) {
-        const int e = (int)((lut[k] >> 23) & 0xFFu);
-        min_e = std::min(min_e, e);
-        max_e = std::max(max_e, e);
-        negative = negative && (lut[k] >> 31) != 0;
-        adj[k] = lut[k] + (127u << 23);
-    }
-    const int e_lo = std::max(1, max_e - 127), e_hi = std::min(254, min_e + 126);
-    p->rcp_xlo = (uint32_t)e_lo << 23;
-    p->rcp_xspan = negative && e_hi >= e_lo ? (uint32_t)(e_hi - e_lo + 1) << 23 : 0u;
-    OCH_HIP(p->d_lut.upload(adj));
-    p->lut_log2 = log2_entries;
-    // camera_proven_miss budgets the table's error; a coarser table leaves
-    // every camera ray to the exact ray_cull
-    p->lut_error = lut_max_rel_error(lut, log2_entries);
-    return OCH_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-OCH_API int och_abi_version(void) { return OCH_GPU_ABI_VERSION; }
-
-OCH_API const char *och_last_error(void) { return g_error.c_str(); }
-
-OCH_API int och_discarded_error(int *hip_error, int *count, char *what, size_t what_cap, int reset)
-{
-    auto &d = discarded();
-    std::lock_guard<std::mutex> lk(d.m);
-    if (hip_error) *hip_error = d.code;
-    if (count) *count = d.count;
-    if (what && what_cap) snprintf(what, what_cap, "%s", d.what.c_str());
-    if (reset) {
-        d.code = d.count = 0;
-        d.what.clear();
-    }
-    return OCH_OK;
-}
-
-OCH_API int och_device_list(int *devices, int capacity, int *count)
-{
-    if (!count || (capacity > 0 && !devices)) return fail(OCH_E_INVALID, "NULL argument");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) n = 0;
-    int gfx950 = 0;
-    for (int i = 0; i < n; ++i) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, i) == hipSuccess && std::strncmp(prop.gcnArchName, "gfx950", 6) == 0) {
-            if (gfx950 < capacity) devices[gfx950] = i;
-            ++gfx950;
-        }
-    }
-    *count = gfx950;
-    return OCH_OK;
-}
-
-OCH_API int och_device_count(int *count)
-{
-    if (!count) return fail(OCH_E_INVALID, "count is NULL");
-    return och_device_list(nullptr, 0, count);
-}
-
-OCH_API uint32_t och_rcp_from_lut(uint32_t x, const uint32_t *lut, int log2_entries)
-{
-    const uint32_t sign = x & 0x80000000u, e = (x >> 23) & 0xFFu;
-    if (e == 0) return sign | 0x7F800000u;
-    if (e == 0xFFu) return (x & 0x7FFFFFu) ? (x | 0x400000u) : sign;
-    const uint32_t ent = lut[(x & 0x7FFFFFu) >> (23 - log2_entries)];
-    const int ne = (int)((ent >> 23) & 0xFFu) + 127 - (int)e;
-    return ne <= 0 ? sign : (sign | ((uint32_t)ne << 23) | (ent & 0x7FFFFFu));
-}
-
-OCH_API int och_rcp_lut_error(const uint32_t *lut, int log2_entries, double *max_rel_error)
-{
-    if (!lut || !max_rel_error || log2_entries < 1 || log2_entries > 23) return fail(OCH_E_INVALID, "bad RCPPS table");
-    *max_rel_error = lut_max_rel_error(lut, log2_entries);
-    return OCH_OK;
-}
-
-OCH_API int och_host_rcp_lut(uint32_t *lut, int *log2_entries)
-{
-    const HostRcp &c = host_rcp();
-    if (c.status != OCH_OK) return fail(c.status, "%s", c.error.c_str());
-    if (lut) std::memcpy(lut, c.lut.data(), c.lut.size() * sizeof(uint32_t));
-    if (log2_entries) *log2_entries = c.log2_entries;
-    return OCH_OK;
-}
-
-OCH_API int och_gpu_pool_create(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, int index_base,
-                                float miss_t, int device, och_gpu_pool **out)
-{
-    if (!nodes || !out) return fail(OCH_E_INVALID, "nodes/out is NULL");
-    if (index_base != 0 && index_base != 1) return fail(OCH_E_INVALID, "index_base must be 0 or 1");
-    *out = nullptr;
-    int st = validate_pool(nodes, n_nodes, root, depth, index_base);
-    if (st != OCH_OK) return st;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(OCH_E_NODEV, "no HIP device visible");
-    if (device < 0) OCH_HIP(hipGetDevice(&device));
-    if (device >= ndev) return fail(OCH_E_NODEV, "device %d of %d", device, ndev);
-    DeviceGuard g(device);
-    if (!g.ok) return fail(OCH_E_HIP, "hipSetDevice(%d) failed", device);
-
-    och_gpu_pool *p = new och_gpu_pool;
-    static std::atomic<uint64_t> next_serial{1};
-    p->serial = next_serial.fetch_add(1);
-    p->device = device;
-    p->depth = depth;
-    p->index_base = index_base;
-    p->miss_t = miss_t;
-    p->root = root;
-    p->n_nodes = n_nodes + (uint32_t)index_base;   // padding node 0 for 1-based pools
-    auto bail = [&](int s) { och_gpu_pool_destroy(p); return s; };
-    if (p->d_nodes.reserve((size_t)p->n_nodes * 8) != hipSuccess)
-        return bail(fail(OCH_E_NOMEM, "hipMalloc(%zu) failed", (size_t)p->n_nodes * 32));
-    if (index_base == 1 && hipMemset(p->d_nodes.d, 0, 32) != hipSuccess) return bail(fail(OCH_E_HIP, "hipMemset failed"));
-    if (hipMemcpy(p->d_nodes.d + 8 * index_base, nodes, (size_t)n_nodes * 32, hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(OCH_E_HIP, "node upload failed"));
-    p->mirror.assign(nodes, nodes + (size_t)n_nodes * 8);
-    set_box(p, nodes, n_nodes);
-    st = upload_packed(p, nodes, n_nodes);
-    if (st != OCH_OK) return bail(st);
-    if (hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        // timing only: no system-scope release at the timed kernel's end
-        hipEventCreateWithFlags(&p->ev_start, hipEventDisableSystemFence) != hipSuccess ||
-        hipEventCreateWithFlags(&p->ev_stop, hipEventDisableSystemFence) != hipSuccess)
-        return bail(fail(OCH_E_HIP, "stream/event creation failed"));
-    const HostRcp &rc = host_rcp();
-    if (rc.status == OCH_OK) {
-        st = upload_lut(p, rc.lut.data(), rc.log2_entries);
-        if (st != OCH_OK) return bail(st);
-    }
-    // A host whose RCPPS does not fit the model leaves the pool without a table:
-    // tracing then fails with OCH_E_RCP_MODEL until och_gpu_set_rcp_lut is called.
-    *out = p;
-    return OCH_OK;
-}
-
-OCH_API int och_gpu_pool_destroy(och_gpu_pool *p)
-{
-    if (!p) return OCH_OK;
-    DeviceGuard g(p->device);
-    if (p->own_stream) (void)hipStreamSynchronize(p->own_stream);
-    if (p->use_ext) (void)hipStreamSynchronize(p->ext_stream);
-    if (p->h_stage) (void)hipHostFree(p->h_stage);
-    // all device memory is held in DevBufs, freed by delete below (on the pool's device: g)
-    if (p->ev_start) (void)hipEventDestroy(p->ev_start);
-    if (p->ev_stop) (void)hipEventDestroy(p->ev_stop);
-    if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
-    delete p;
-    return OCH_OK;
-}
-
-OCH_API int och_gpu_pool_info(const och_gpu_pool *p, och_pool_info *info)
-{
-    if (!p || !info) return fail(OCH_E_INVALID, "pool/info is NULL");
-    info->device_bytes = (uint64_t)p->n_nodes * 32;
-    info->n_nodes = p->n_nodes;
-    info->root = p->root;
-    info->depth = p->depth;
-    info->index_base = p->index_base;
-    info->miss_t = p->miss_t;
-    info->rcp_log2_entries = p->d_lut.d ? p->lut_log2 : 0;
-    info->device = p->device;
-    return OCH_OK;
-}
-
-OCH_API int och_gpu_pool_update(och_gpu_pool *p, uint32_t first, uint32_t count, const uint32_t *nodes, uint32_t root)
-{
-    OCH_ENTRY();
-    if (!p || (count && !nodes)) return fail(OCH_E_INVALID, "pool/nodes is NULL");
-    if (p->torn) return fail(OCH_E_INVALID, "pool left half written by a failed och_editor_flush: flush the editor again");
-    const uint32_t n_user = p->n_nodes - (uint32_t)p->index_base;
-    const uint32_t lo = p->index_base == 1 ? 1u : 0u;
-    if (count && (first < lo || (uint64_t)first - lo + count > n_user))
-        return fail(OCH_E_INVALID, "update [%u, +%u) outside the pool", first, count);
-    // Apply to the host mirror and re-validate everything reachable from the
-    // new root before any byte reaches the device (h_octree::set keeps the
-    // pool consistent, ORT/och_h_octree.h:176-237; a bad edit must not fault).
-    const size_t off = (size_t)(first - lo) * 8;
-    std::vector<uint32_t> saved(p->mirror.begin() + off, p->mirror.begin() + off + (size_t)count * 8);
-    std::memcpy(p->mirror.data() + off, nodes, (size_t)count * 32);
-    const int st = validate_pool(p->mirror.data(), n_user, root, p->depth, p->index_base);
-    if (st != OCH_OK) {
-        std::memcpy(p->mirror.data() + off, saved.data(), saved.size() * 4);
-        return st;
-    }
-    // slots are rewritten in place: kernels of frames in flight on any stream
-    // may still walk them (as the editor's flush)
-    int ds = och::pool_drain(p);
-    if (ds != OCH_OK) return ds;
-    DeviceGuard g(p->device);
-    if (count)
-        OCH_HIP(hipMemcpyAsync(p->d_nodes.d + 8 * (size_t)(first - lo + p->index_base), p->mirror.data() + off,
-                               (size_t)count * 32, hipMemcpyHostToDevice, p->stream()));
-    OCH_HIP(hipStreamSynchronize(p->stream()));
-    p->root = root;
-    p->last_writer = 0;
-    set_box(p, p->mirror.data(), n_user);
-    return upload_packed(p, p->mirror.data(), n_user);
-}
-
-}  // extern "C"
-
-int och::report(int status, const char *msg) { return fail(status, "%s", msg); }
-
-// ------------------------------------------------------------ discarded errors
-
-
-och::EntryScope::EntryScope(const char *name) : prev(t_entry)
-{
-    if (!t_entry) t_entry = name;
-}
-
-och::EntryScope::~EntryScope() { t_entry = prev; }
-
-void och::clear_pending_error(const char *launcher)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return;
-    Discarded &d = discarded();
-    std::lock_guard<std::mutex> lk(d.m);
-    if (d.count++ == 0) {
-        char buf[320];
-        snprintf(buf, sizeof buf, "%s (%d) pending at %s, cleared by %s", hipGetErrorName(e), (int)e,
-                 t_entry ? t_entry : "an internal call", launcher);
-        d.code = (int)e;
-        d.what = buf;
-    }
-}
-
-uint64_t och::pool_serial(const och_gpu_pool *p) { return p ? p->serial : 0; }
-void *och::pool_stream(const och_gpu_pool *p) { return p ? static_cast<void *>(p->stream()) : nullptr; }
-int och::pool_palette_size(const och_gpu_pool *p, int *n)
-{
-    if (!p || !n) return fail(OCH_E_INVALID, "NULL argument");
-    *n = (int)p->n_voxels;
-    return OCH_OK;
-}
-uint64_t och::pool_last_writer(const och_gpu_pool *p) { return p ? p->last_writer : 0; }
-
-int och::pool_drain(och_gpu_pool *p)
-{
-    if (!p) return fail(OCH_E_INVALID, "pool is NULL");
-    DeviceGuard g(p->device);
-    // Every stream, not just the pool's: bench and frame code rotate the pool
-    // over several streams with frames in flight, and a kernel still walking a
-    // slot that is rewritten in place could read a torn DAG.
-    OCH_HIP(hipDeviceSynchronize());
-    return OCH_OK;
-}
-
-int och::pool_write_slots(och_gpu_pool *p, uint32_t first, uint32_t count, const uint32_t *raw,
-                          const uint32_t *packed, bool full)
-{
-    if (!p || p->index_base != 1 || (count && !raw)) return fail(OCH_E_INVALID, "bad editor flush");
-    if ((uint64_t)first + count > p->n_nodes || (full && (first != 0 || count != p->n_nodes)))
-        return fail(OCH_E_INVALID, "editor window [%u, +%u) outside the pool", first, count);
-    if (packed && p->n_nodes > kIdLimit) return fail(OCH_E_INVALID, "packed ids exceed 24 bits");
-    if (packed && !full && (!p->d_packed.d || !p->packed_by_slot))
-        return fail(OCH_E_INVALID, "packed buffer is not in editor numbering");
-    DeviceGuard g(p->device);
-    p->last_writer = 0;                 // until pool_commit: a failed flush forces a full rewrite
-    // mirror and raw device slots: slot 0 is the padding node, never written
-    const uint32_t lo = first ? first : 1;
-    const uint32_t skip = lo - first;
-    if (count > skip) {
-        const size_t n = (size_t)(count - skip) * 8;
-        std::memcpy(p->mirror.data() + (size_t)(lo - 1) * 8, raw + (size_t)skip * 8, n * 4);
-        OCH_HIP(hipMemcpy(p->d_nodes.d + (size_t)lo * 8, raw + (size_t)skip * 8, n * 4, hipMemcpyHostToDevice));
-    }
-    if (!packed) return OCH_OK;
-    if (full && (!p->d_packed.d || !p->packed_by_slot || p->packed_nodes != p->n_nodes)) {
-        OCH_HIP(p->drop_packed());
-        OCH_HIP(p->d_packed.reserve((size_t)p->n_nodes * 8));
-        p->packed_nodes = p->n_nodes;
-        p->packed_by_slot = true;
-    }
-    if (count)
-        OCH_HIP(hipMemcpy(p->d_packed.d + (size_t)first * 8, packed, (size_t)count * 32, hipMemcpyHostToDevice));
-    return OCH_OK;
-}
-
-int och::pool_scatter_slots(och_gpu_pool *p, const uint32_t *ids, uint32_t count, const uint32_t *raw,
-                            const uint32_t *packed)
-{
-    if (!p || p->index_base != 1 || (count && (!ids || !raw))) return fail(OCH_E_INVALID, "bad editor flush");
-    if (packed && (!p->d_packed.d || !p->packed_by_slot))
-        return fail(OCH_E_INVALID, "packed buffer is not in editor numbering");
-    if (count == 0) return OCH_OK;
-    for (uint32_t i = 0; i < count; ++i)
-        if (ids[i] == 0 || ids[i] >= p->n_nodes) return fail(OCH_E_INVALID, "editor slot %u outside the pool", ids[i]);
-    DeviceGuard g(p->device);
-    p->last_writer = 0;                 // until pool_commit
-    // staging: [ids | raw | packed]
-    const size_t words = (size_t)count * (packed ? 17 : 9);
-    const size_t cap = std::max<size_t>(words, 1 << 16);
-    if (words > p->stage_words) {
-        if (p->h_stage) OCH_HIP(hipHostFree(p->h_stage));
-        p->h_stage = nullptr;
-        p->stage_words = 0;
-        OCH_HIP(hipHostMalloc(&p->h_stage, cap * 4, hipHostMallocDefault));
-        p->stage_words = cap;
-    }
-    OCH_HIP(p->d_stage.reserve(cap));
-    std::memcpy(p->h_stage, ids, (size_t)count * 4);
-    std::memcpy(p->h_stage + count, raw, (size_t)count * 32);
-    if (packed) std::memcpy(p->h_stage + 9 * (size_t)count, packed, (size_t)count * 32);
-    for (uint32_t i = 0; i < count; ++i)       // host mirror (user numbering, slot s at row s - 1)
-        std::memcpy(p->mirror.data() + (size_t)(ids[i] - 1) * 8, raw + (size_t)i * 8, 32);
-    const hipStream_t s = p->stream();
-    uint32_t *stage = p->d_stage.d;
-    OCH_HIP(hipMemcpyAsync(stage, p->h_stage, words * 4, hipMemcpyHostToDevice, s));
-    OCH_HIP(och::launch_scatter_slots(stage, stage + count, packed ? stage + 9 * (size_t)count : nullptr,
-                                      count, p->d_nodes.d, packed ? p->d_packed.d : nullptr, s));
-    OCH_HIP(hipStreamSynchronize(s));
-    return OCH_OK;
-}
-
-int och::pool_commit(och_gpu_pool *p, uint32_t root, uint32_t packed_root, bool packed, uint64_t writer,
-                     const int32_t *box_lo, const int32_t *box_hi)
-{
-    if (!p || p->index_base != 1) return fail(OCH_E_INVALID, "bad editor flush");
-    if (packed && (!p->d_packed.d || !p->packed_by_slot))
-        return fail(OCH_E_INVALID, "packed buffer is not in editor numbering");
-    DeviceGuard g(p->device);
-    if (!packed) OCH_HIP(p->drop_packed());
-    p->root = root;
-    p->packed_root = packed ? packed_root : 0;
-    p->box_any = box_lo && box_hi;
-    for (int a = 0; a < 3; ++a) {
-        p->box_lo[a] = p->box_any ? box_lo[a] : 0;
-        p->box_hi[a] = p->box_any ? box_hi[a] : 0;
-    }
-    p->last_writer = writer;
-    p->torn = false;
-    return OCH_OK;
-}
-
-int och::pool_mark_torn(och_gpu_pool *p)
-{
-    if (!p) return OCH_E_INVALID;
-    DeviceGuard g(p->device);
-    (void)hipDeviceSynchronize();
-    (void)p->drop_packed();
-    p->packed_root = 0;
-    p->root = 0;
-    p->box_any = false;
-    p->last_writer = 0;
-    p->torn = true;
-    return OCH_OK;
-}
-
-// ------------------------------------------------------------ launch planning
-// The pure planners: vectors and integers in and out, no HIP call, no pool; external
-// linkage, so that a host program can call them (tests/test_plan_host.py pins them).
-namespace och {
-namespace plan {
-
-// The stable costliest-first permutation of the workgroups.
-std::vector<uint32_t> by_cost(const std::vector<uint32_t> &costs)
-{
-    std::vector<uint32_t> order(costs.size());
-    for (uint32_t i = 0; i < order.size(); ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return costs[a] > costs[b]; });
-    return order;
-}
-
-// The launch order from the costliest-first list (OCH_OPT_PLAN): 0 = all
-// workgroups costliest first; P in 1..99 = the costliest P % first, then the
-// rest in natural order (the tails a frame ends on start early, while the bulk
-// keeps the raster order's mix of sky and terrain tiles); 100 = alternate the
-// costliest and the cheapest left.  Default 10: with frames in flight, every
-// frame starting all its costly tiles at once cost 3.5 % over long runs
-// (profiles/r03/ab/plan_*).
-void shape(std::vector<uint32_t> &order, int mode)
-{
-    const size_t n = order.size();
-    if (mode <= 0 || n < 2) return;
-    std::vector<uint32_t> out;
-    out.reserve(n);
-    if (mode >= 100) {
-        for (size_t i = 0, j = n - 1; i <= j && j < n; ++i, --j) {
-            out.push_back(order[i]);
-            if (j != i) out.push_back(order[j]);
-            if (j == 0) break;
-        }
-    } else {
-        const size_t head = n * (size_t)mode / 100;
-        std::vector<uint8_t> taken(n, 0);
-        for (size_t i = 0; i < head; ++i) {
-            out.push_back(order[i]);
-            taken[order[i]] = 1;
-        }
-        for (uint32_t b = 0; b < n; ++b)
-            if (!taken[b]) out.push_back(b);
-    }
-    order.swap(out);
-}
-
-// Grouped per XCD (OCH_OPT_TILE_ORDER = 3): workgroup slot i runs on XCD
-// i % 8, so deal 64x64-pixel supertiles over the XCDs (each XCD's L2 then
-// holds the nodes of its own neighbouring tiles) and keep the costliest-
-// first order within each XCD's list.  Workgroup b starts at tile b * (block / 64).
-std::vector<uint32_t> group_by_xcd(const std::vector<uint32_t> &order, uint32_t tiles_x, uint32_t tiles_y, uint32_t block)
-{
-    const uint32_t stx = (tiles_x + 7) / 8, sty = (tiles_y + 7) / 8;
-    std::vector<std::vector<uint32_t>> lists(8);
-    for (uint32_t b : order) {
-        const uint32_t tile = b * (block / 64), view = tile / (tiles_x * tiles_y), t = tile % (tiles_x * tiles_y);
-        const uint32_t super = (view * sty + (t / tiles_x) / 8) * stx + (t % tiles_x) / 8;
-        lists[super % 8].push_back(b);
-    }
-    std::vector<uint32_t> grouped;
-    grouped.reserve(order.size());
-    std::vector<size_t> at(8, 0);
-    while (grouped.size() < order.size())
-        for (uint32_t x = 0; x < 8 && grouped.size() < order.size(); ++x) {
-            uint32_t from = x;
-            if (at[x] == lists[x].size())       // this XCD's list ran dry: the fullest other list
-                for (uint32_t y = 0; y < 8; ++y)
-                    if (lists[y].size() - at[y] > lists[from].size() - at[from]) from = y;
-            grouped.push_back(lists[from][at[from]++]);
-        }
-    return grouped;
-}
-
-// A split tile's rays longer than this % of its longest walk over
-// OCH_OPT_SPLIT_SEGS lanes; the others take one lane and walk whole
-// (tools/split_model.c: 30 % keeps the critical path of splitting every ray
-// and adds almost no work).
-constexpr int kSplitRayPct = 30;
-
-// The split form of a primary plan (OCH_OPT_SPLIT).  The tiles
-// whose planning cost reaches opt_split % of the costliest one's are split:
-// one counting render gives every pixel's walked PUSHes, a tile's rays longer
-// than kSplitRayPct % of its longest get opt_split_segs lanes each (segment
-// lanes), the others one, and its rays are packed, costliest first, into
-// waves of 64 lanes with every lane of a ray in one wave (their records merge
-// through that wave's LDS).  Rows of d_split_tasks: the tile, then 64 lane
-// tasks (pixel | seg << 6 | log2(S) << 10, ~0 idle).  The order: the split
-// waves (1 << 31 | row), then the plan's other workgroups in its order.
-// Block 64 only (workgroup = tile), packed layout, tiles < 2^24, and a split
-// level above the leaves; otherwise no split plan.
-
-// One tile's waves, 64 lane tasks each, from its pixels' PUSHes (-1: outside the frame).
-std::vector<uint32_t> pack_split_tile(const int cnt[64], int S)
-{
-    const int log2s = __builtin_ctz((unsigned)S), mx = std::max(0, *std::max_element(cnt, cnt + 64));
-    auto long_ray = [&](int l) { return cnt[l] * 100 > kSplitRayPct * mx; };
-    std::vector<std::pair<int, int>> rays;                  // (estimated lane cost, pixel)
-    for (int l = 0; l < 64; ++l)
-        if (cnt[l] >= 0) rays.push_back({long_ray(l) ? cnt[l] / S : cnt[l], l});
-    std::stable_sort(rays.begin(), rays.end(), [](const auto &a, const auto &b) { return a.first > b.first; });
-    std::vector<uint32_t> waves, used;                      // 64 words per wave, idle at first; lanes taken
-    for (const auto &r : rays) {
-        const uint32_t l = (uint32_t)r.second, lanes = long_ray(r.second) ? (uint32_t)S : 1u;
-        size_t w = 0;
-        while (w < used.size() && used[w] + lanes > 64) ++w;
-        if (w == used.size()) {
-            used.push_back(0);
-            waves.resize(waves.size() + 64, ~0u);
-        }
-        for (uint32_t s = 0; s < lanes; ++s)
-            waves[w * 64 + used[w]++] = l | s << 6 | (uint32_t)(lanes > 1 ? log2s : 0) << 10;
-    }
-    return waves;
-}
-
-struct Split {
-    std::vector<uint32_t> order, tasks;
-    uint32_t tiles = 0, extra = 0;      // heavy tiles; waves - heavy tiles
-};
-
-// The heavy tiles (pct % of the costliest, at most max(1, n / 16): a bound on the
-// planner's work), their waves, and the split order; push: slices of rows x W.
-Split split_order(const std::vector<uint16_t> &push, int W, int rows, const std::vector<uint32_t> &by_cost,
-                  const std::vector<uint32_t> &order, const std::vector<uint32_t> &c, int pct, int S)
-{
-    Split sp;
-    const uint32_t n = (uint32_t)order.size();
-    if (pct <= 0 || n == 0) return sp;
-    const double thr = (double)c[by_cost[0]] * pct / 100.0;
-    const uint32_t cap = std::max(1u, n / 16);
-    const uint32_t tiles_x = (uint32_t)(W + 7) / 8, per_view = tiles_x * (uint32_t)((rows + 7) / 8);
-    std::vector<uint8_t> heavy(n, 0);
-    for (uint32_t k = 0; k < n && k < cap && (double)c[by_cost[k]] >= thr; ++k, ++sp.tiles) {
-        const uint32_t t = by_cost[k];
-        heavy[t] = 1;
-        const uint32_t view = t / per_view, tt = t % per_view, ty = tt / tiles_x, tx = tt % tiles_x;
-        int cnt[64];
-        for (int l = 0; l < 64; ++l) {
-            const uint32_t col = tx * 8 + (uint32_t)(l % 8), srow = ty * 8 + (uint32_t)(l / 8);
-            cnt[l] = col < (uint32_t)W && srow < (uint32_t)rows ? push[((size_t)view * rows + srow) * W + col] : -1;
-        }
-        const std::vector<uint32_t> waves = pack_split_tile(cnt, S);
-        for (size_t w = 0; w < waves.size(); w += 64) {
-            sp.order.push_back(0x80000000u | (uint32_t)(sp.tasks.size() / 65));
-            sp.tasks.push_back(t);
-            sp.tasks.insert(sp.tasks.end(), waves.begin() + w, waves.begin() + w + 64);
-        }
-    }
-    sp.extra = (uint32_t)sp.order.size() - sp.tiles;
-    for (uint32_t b : order)
-        if (!heavy[b]) sp.order.push_back(b);
-    return sp;
-}
-
-// A workgroup's time spread over its per_block tiles (natural 8x8-tile order), a
-// tile's over its 8 rows, summed per chunk of row_chunk rows (och_gpu_chunk_costs).
-std::vector<float> spread_chunk_costs(const std::vector<uint32_t> &c, int n_views, int W, int H, uint32_t per_block,
-                                      int row_chunk)
-{
-    const uint32_t tiles_x = (uint32_t)(W + 7) / 8, tiles_y = (uint32_t)(H + 7) / 8;
-    const uint32_t tiles = (uint32_t)n_views * tiles_x * tiles_y;
-    std::vector<double> acc((H + row_chunk - 1) / row_chunk, 0.0);
-    for (uint32_t b = 0; b < c.size(); ++b)
-        for (uint32_t t = b * per_block; t < std::min(tiles, (b + 1) * per_block); ++t) {
-            const uint32_t ty = (t % (tiles_x * tiles_y)) / tiles_x;
-            const int r0 = (int)ty * 8, r1 = std::min(H, r0 + 8);
-            for (int r = r0; r < r1; ++r) acc[r / row_chunk] += (double)c[b] / per_block / (r1 - r0);
-        }
-    return std::vector<float>(acc.begin(), acc.end());
-}
-
-}  // namespace plan
-}  // namespace och
+using och::LaunchPlan;
+using och::SplitPlan;
+using och::TileTable;
 
 int och::check_views(const och_camera *cams, int n_views)
 {
@@ -1102,214 +78,6 @@ och::DevFrame make_frame(const och_gpu_pool *p, const och_camera *cams, int n_vi
     f.chunk_map = dealt ? p->d_chunk_map.d + (size_t)shard * p->deal_max : nullptr;
     return f;
 }
-
-// A planning render: launch(sc) in natural order, sc.cost naming n_words words preset to
-// 0xFFFFFFFF that every launched workgroup overwrites with its duration; c receives them.
-// frame: the camera frame the launch renders (bounce: by the config-5 kernel), for its tile table.
-int use_tiles(och_gpu_pool *p, const och::DevFrame &f, bool bounce, och::Schedule &sc);
-
-template <class Launch>
-int cost_render(och_gpu_pool *p, uint32_t *cost, uint32_t n_words, std::vector<uint32_t> &c, Launch launch,
-                const och::DevFrame *frame = nullptr, bool bounce = false)
-{
-    och::Schedule sc = p->schedule();
-    sc.tile_order = 0;
-    sc.cost = cost;
-    if (frame)
-        if (int ts = use_tiles(p, *frame, bounce, sc)) return ts;
-    OCH_HIP(hipMemsetAsync(cost, 0xFF, (size_t)n_words * 4, p->stream()));
-    OCH_HIP(launch(sc));
-    c.resize(n_words);
-    OCH_HIP(hipMemcpyAsync(c.data(), cost, (size_t)n_words * 4, hipMemcpyDeviceToHost, p->stream()));
-    OCH_HIP(hipStreamSynchronize(p->stream()));
-    return OCH_OK;
-}
-
-extern "C" {   // the render path's pieces, defined with the entries below inside extern "C": declared so here
-och::Schedule timed_schedule(och_gpu_pool *p, int &st);
-int timed_done(och_gpu_pool *p, const och::Schedule &sc, bool launched);
-void use_plan(const och_gpu_pool *p, const och::DevFrame &f, bool bounce, bool split, och::Schedule &sc);
-}
-
-// One camera launch of frame f: the schedule with the launch's timing, the plan of
-// this geometry (split: its split form too), the tile table, the launch, the timing's
-// end.  CAMERA_LAUNCH's launch expression takes the schedule as `sc`; a failure names it.
-template <class Launch>
-int camera_launch(och_gpu_pool *p, const och::DevFrame &f, bool bounce, bool split, const char *what, Launch launch)
-{
-    int ts;
-    och::Schedule sc = timed_schedule(p, ts);
-    if (ts) return ts;
-    use_plan(p, f, bounce, split, sc);
-    if (int us = use_tiles(p, f, bounce, sc)) return us;
-    const hipError_t e = launch(sc);
-    if (e != hipSuccess) return fail(OCH_E_HIP, "%s: %s", what, hipGetErrorString(e));
-    return timed_done(p, sc, true);
-}
-#define CAMERA_LAUNCH(p, f, bounce, split, call) \
-    camera_launch(p, f, bounce, split, #call, [&](const och::Schedule &sc) { return call; })
-
-// A host form: render(scratch) into the pool's scratch (pixels words and `spare`
-// bytes), then the pixels to the caller's rgba, complete on return.
-template <class Render>
-int to_host(och_gpu_pool *p, size_t pixels, size_t spare, uint32_t *rgba, Render render)
-{
-    DeviceGuard g(p->device);
-    int st = ensure_scratch(p, pixels * 4 + spare);
-    if (st != OCH_OK) return st;
-    st = render(reinterpret_cast<uint32_t *>(p->scratch.d));
-    if (st != OCH_OK) return st;
-    OCH_HIP(hipMemcpyAsync(rgba, p->scratch.d, pixels * 4, hipMemcpyDeviceToHost, p->stream()));
-    OCH_HIP(hipStreamSynchronize(p->stream()));
-    return OCH_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-OCH_API int och_gpu_set_rcp_lut(och_gpu_pool *p, const uint32_t *lut, int log2_entries)
-{
-    if (!p) return fail(OCH_E_INVALID, "pool is NULL");
-    DeviceGuard g(p->device);
-    OCH_HIP(hipStreamSynchronize(p->stream()));
-    return upload_lut(p, lut, log2_entries);
-}
-
-OCH_API int och_gpu_set_palette(och_gpu_pool *p, const uint32_t *rgba, uint32_t n_voxels)
-{
-    if (!p || (n_voxels && !rgba)) return fail(OCH_E_INVALID, "pool/palette is NULL");
-    DeviceGuard g(p->device);
-    OCH_HIP(hipStreamSynchronize(p->stream()));
-    OCH_HIP(p->d_palette.release());
-    OCH_HIP(p->d_code_table.release());   // no code table unless this palette fits the codes
-    p->n_voxels = 0;
-    if (n_voxels <= OCH_CODE_MAX_VOXELS) {
-        // Indexed-colour frames: trace_pixel's colour per code
-        // (ORT/test_och_h_octree.cpp:76-84), then config 5's blocked (halved) variants.
-        std::vector<uint32_t> t(256, 0xFFFF00FFu);
-        for (uint32_t c = 0; c < 6 * n_voxels; ++c) t[c] = rgba[c];
-        t[OCH_CODE_INSIDE] = 0xFF07193Fu;
-        t[OCH_CODE_SKY] = 0xFFFEBF00u;
-        for (uint32_t c = 0; c < OCH_CODE_BLOCKED; ++c)
-            t[c | OCH_CODE_BLOCKED] = ((t[c] >> 1) & 0x007F7F7Fu) | (t[c] & 0xFF000000u);
-        OCH_HIP(p->d_code_table.upload(t));
-    }
-    if (!n_voxels) return OCH_OK;
-    OCH_HIP(p->d_palette.reserve((size_t)n_voxels * 6));
-    OCH_HIP(hipMemcpy(p->d_palette.d, rgba, (size_t)n_voxels * 6 * 4, hipMemcpyHostToDevice));
-    p->n_voxels = n_voxels;
-    return OCH_OK;
-}
-
-OCH_API int och_gpu_set_stream(och_gpu_pool *p, void *stream)
-{
-    if (!p) return fail(OCH_E_INVALID, "pool is NULL");
-    p->ext_stream = (hipStream_t)stream;
-    p->use_ext = true;
-    return OCH_OK;
-}
-
-// Option ids retired in round 5 (measured slower on every scene, DESIGN.md
-// §8): 0 schedule (persistent / refill), 2 waves per CU, 3 refill, 7 chunk
-// tiles, 9 merge, 12 per-node skip, 13 column cull.  Their ids stay unused.
-static int retired_option(int option)
-{
-    return fail(OCH_E_INVALID, "option %d was retired (the grid schedule alone remains; DESIGN.md section 8)", option);
-}
-
-OCH_API int och_gpu_set_option(och_gpu_pool *p, int option, int value)
-{
-    if (!p) return fail(OCH_E_INVALID, "pool is NULL");
-    switch (option) {
-    case OCH_OPT_BLOCK:
-        if (value < 64 || value > 1024 || value % 64) return fail(OCH_E_INVALID, "block %d", value);
-        p->opt_block = value;
-        return OCH_OK;
-    case OCH_OPT_LAYOUT:
-        if (value != 0 && value != 1) return fail(OCH_E_INVALID, "layout must be 0 or 1");
-        if (value == 1 && !p->d_packed.d) return fail(OCH_E_INVALID, "pool too large for the packed layout");
-        p->opt_layout = value;
-        return OCH_OK;
-    case OCH_OPT_TILE_ORDER:
-        if (value < 0 || value > 3) return fail(OCH_E_INVALID, "tile order must be 0..3");
-        p->opt_tile_order = value;
-        return OCH_OK;
-    case OCH_OPT_BOUNCE_COMPACT:
-        if (value < 0 || value > 2) return fail(OCH_E_INVALID, "bounce compaction must be 0, 1 or 2");
-        p->opt_bounce_compact = value;
-        return OCH_OK;
-    case OCH_OPT_CULL:
-        if (value < 0 || value > 2) return fail(OCH_E_INVALID, "cull must be 0, 1 or 2");
-        p->opt_cull = value;
-        return OCH_OK;
-    case OCH_OPT_TIMING:
-        if (value < 0 || value > 2) return fail(OCH_E_INVALID, "timing must be 0, 1 or 2");
-        p->opt_timing = value;
-        return OCH_OK;
-    case OCH_OPT_PLAN:
-        if (value < 0 || value > 100) return fail(OCH_E_INVALID, "plan shape must be 0..100");
-        p->opt_plan = value;
-        return OCH_OK;
-    case OCH_OPT_SPLIT:
-        if (value < 0 || value > 100) return fail(OCH_E_INVALID, "split threshold must be 0..100 (%% of the costliest tile)");
-        p->opt_split = value;
-        return OCH_OK;
-    case OCH_OPT_SPLIT_SEGS:
-        if (value != 2 && value != 4 && value != 8 && value != 16) return fail(OCH_E_INVALID, "split segments must be 2, 4, 8 or 16");
-        p->opt_split_segs = value;
-        return OCH_OK;
-    case OCH_OPT_SPLIT_LEVEL:
-        if (value < 1 || value > 21) return fail(OCH_E_INVALID, "split level must be 1..21");
-        p->opt_split_level = value;
-        return OCH_OK;
-    case OCH_OPT_SPLIT_TILES:
-        return fail(OCH_E_INVALID, "OCH_OPT_SPLIT_TILES is read-only");
-    case 0: case 2: case 3: case 7: case 9: case 12: case 13:
-        return retired_option(option);
-    default:
-        return fail(OCH_E_INVALID, "unknown option %d", option);
-    }
-}
-
-OCH_API int och_gpu_get_option(const och_gpu_pool *p, int option, int *value)
-{
-    if (!p || !value) return fail(OCH_E_INVALID, "NULL argument");
-    switch (option) {
-    case OCH_OPT_BLOCK: *value = p->opt_block; return OCH_OK;
-    case OCH_OPT_LAYOUT: *value = (p->opt_layout == 1 && p->d_packed.d) ? 1 : 0; return OCH_OK;
-    case OCH_OPT_TILE_ORDER: *value = p->opt_tile_order; return OCH_OK;
-    case OCH_OPT_BOUNCE_COMPACT: *value = p->opt_bounce_compact; return OCH_OK;
-    case OCH_OPT_CULL: *value = p->opt_cull; return OCH_OK;
-    case OCH_OPT_TIMING: *value = p->opt_timing; return OCH_OK;
-    case OCH_OPT_PLAN: *value = p->opt_plan; return OCH_OK;
-    case OCH_OPT_SPLIT: *value = p->opt_split; return OCH_OK;
-    case OCH_OPT_SPLIT_SEGS: *value = p->opt_split_segs; return OCH_OK;
-    case OCH_OPT_SPLIT_LEVEL: *value = p->opt_split_level; return OCH_OK;
-    case OCH_OPT_SPLIT_TILES: *value = (int)p->split.tiles; return OCH_OK;
-    case 0: case 2: case 3: case 7: case 9: case 12: case 13:
-        return retired_option(option);
-    default: return fail(OCH_E_INVALID, "unknown option %d", option);
-    }
-}
-
-OCH_API int och_gpu_occupancy(const och_gpu_pool *p, int kind, int *blocks_per_cu)
-{
-    if (!p || !blocks_per_cu) return fail(OCH_E_INVALID, "NULL argument");
-    DeviceGuard g(p->device);
-    OCH_HIP(och::occupancy_blocks_per_cu(kind, p->opt_block, p->depth, blocks_per_cu));
-    return OCH_OK;
-}
-
-OCH_API int och_gpu_set_stamp_buffer(och_gpu_pool *p, uint64_t *stamps, uint32_t capacity_waves)
-{
-    if (!p) return fail(OCH_E_INVALID, "pool is NULL");
-    p->stamps = capacity_waves ? stamps : nullptr;
-    p->stamp_cap = stamps ? capacity_waves : 0;
-    return OCH_OK;
-}
-
-namespace {
 
 // Per-launch timing of the traversal kernel (OCH_OPT_TIMING).  1 (default):
 // the dispatch itself records the pool's events (hipExtLaunchKernel, no
@@ -1372,13 +140,152 @@ struct FrameLoopScope {
     }
 };
 
+// The launch order of frame f under OCH_OPT_TILE_ORDER 2 / 3: the pool's plan
+// (och_gpu_plan_views) when it was made for this geometry, else none (natural
+// order).  split: the launch can run the plan's split form (the grid kernel);
+// without it the order stays an unsplit permutation of the frame's grid.
+void use_plan(const och_gpu_pool *p, const och::DevFrame &f, bool bounce, bool split, och::Schedule &sc)
+{
+    const LaunchPlan &plan = p->plans[bounce ? 1 : 0];
+    if (p->opt_tile_order < 2 || !plan.order.d) return;
+    int64_t key[9];
+    frame_key(p, f, bounce, key);
+    if (!plan.matches(key)) return;
+    sc.order = p->opt_tile_order == 3 ? plan.order_xcd.d : plan.order.d;
+    sc.order_n = plan.blocks;
+    // the plan's split form, while the options it was made with hold
+    const SplitPlan &sp = p->split;
+    if (split && !bounce && p->opt_tile_order == 2 && sp.n && p->dev().packed && p->opt_split == sp.params[0] &&
+        p->opt_split_segs == sp.params[1] && p->opt_split_level == sp.params[2]) {
+        sc.order = sp.order.d;
+        sc.order_n = sp.n;
+        sc.split_extra = sp.extra;
+        sc.split_tasks = sp.tasks.d;
+        sc.split_level = (uint32_t)p->opt_split_level;
+    }
+}
+
+// The tile table of frame f's launch under sc (after use_plan): the pool's
+// table of this geometry, block size and launch order, made and uploaded when
+// the pool holds none.  Nothing in it depends on the cameras.  bounce: the
+// config-5 kernel's launch (its own block size).
+int use_tiles(och_gpu_pool *p, const och::DevFrame &f, bool bounce, och::Schedule &sc)
+{
+    const int block = bounce ? std::max(och::kBounceBlock, sc.block) : sc.block;
+    const LaunchPlan &plan = p->plans[bounce ? 1 : 0];
+    // the launch order: the split plan's, the plan's (whole, or grouped per XCD), or none
+    const std::vector<uint32_t> *order = nullptr, *tasks = nullptr;
+    int mode = sc.tile_order == 1 ? 1 : 0;
+    if (sc.split_tasks) {
+        order = &p->split.h_order;
+        tasks = &p->split.h_tasks;
+        mode = 4;
+    } else if (sc.order) {
+        mode = p->opt_tile_order == 3 ? 3 : 2;
+        order = mode == 3 ? &plan.h_order_xcd : &plan.h_order;
+    }
+    const int64_t key[12] = {f.cams[0].width, f.cams[0].height, f.n_views, f.row_chunk, f.shard, f.n_shards,
+                             f.slice_rows, block, mode, f.chunk_map ? (int64_t)p->deal_serial : 0,
+                             order ? (int64_t)plan.serial : 0, bounce ? 1 : 0};
+    TileTable *t = nullptr, *oldest = &p->tile_tables[0];
+    for (TileTable &c : p->tile_tables) {
+        if (c.used && std::memcmp(c.key, key, sizeof key) == 0) t = &c;
+        if (c.used < oldest->used) oldest = &c;
+    }
+    if (!t) {
+        och::plan::TileGeometry g = {f.cams[0].width, f.cams[0].height, f.n_views, f.row_chunk, f.shard, f.n_shards,
+                                     f.slice_rows, block, mode == 1 ? 1 : 0, nullptr};
+        if (f.chunk_map) g.chunk_map = p->h_chunk_map.data() + (size_t)f.shard * p->deal_max;
+        std::vector<uint64_t> table;
+        uint32_t grid = 0;
+        // a plan of another grid (stale, or for another block size) is not this launch's: natural order
+        const uint32_t blocks = (uint32_t)(((uint64_t)f.n_views * ((f.cams[0].width + 7) / 8) * ((f.slice_rows + 7) / 8) * 64 +
+                                            block - 1) / block);
+        if (order && mode != 4 && order->size() != blocks) order = nullptr;
+        const char *why = "";
+        if (int st = och::plan::tile_table(g, order ? order->data() : nullptr, order ? (uint32_t)order->size() : 0u,
+                                           tasks ? tasks->data() : nullptr, tasks ? (uint32_t)tasks->size() : 0u, table,
+                                           grid, &why))
+            return fail(st, "tile table of a %d x %d frame, %d views: %s", g.width, g.height, g.n_views, why);
+        t = oldest;
+        if (t->used) {                          // launches in flight on other streams may read the table it replaces
+            t->used = 0;
+            if (int ds = och::pool_drain(p)) return ds;
+        }
+        OCH_HIP(t->d.upload(table));
+        t->n = (uint32_t)table.size();
+        t->grid = grid;
+        t->block = (uint32_t)block;
+        std::memcpy(t->key, key, sizeof key);
+    }
+    t->used = ++p->tile_clock;
+    sc.tiles = t->d.d;
+    sc.tiles_n = t->n;
+    sc.tiles_grid = t->grid;
+    sc.tiles_block = t->block;
+    return OCH_OK;
+}
+
+// A planning render: launch(sc) in natural order, sc.cost naming n_words words preset to
+// 0xFFFFFFFF that every launched workgroup overwrites with its duration; c receives them.
+// frame: the camera frame the launch renders (bounce: by the config-5 kernel), for its tile table.
+template <class Launch>
+int cost_render(och_gpu_pool *p, uint32_t *cost, uint32_t n_words, std::vector<uint32_t> &c, Launch launch,
+                const och::DevFrame *frame = nullptr, bool bounce = false)
+{
+    och::Schedule sc = p->schedule();
+    sc.tile_order = 0;
+    sc.cost = cost;
+    if (frame)
+        if (int ts = use_tiles(p, *frame, bounce, sc)) return ts;
+    OCH_HIP(hipMemsetAsync(cost, 0xFF, (size_t)n_words * 4, p->stream()));
+    OCH_HIP(launch(sc));
+    c.resize(n_words);
+    OCH_HIP(hipMemcpyAsync(c.data(), cost, (size_t)n_words * 4, hipMemcpyDeviceToHost, p->stream()));
+    OCH_HIP(hipStreamSynchronize(p->stream()));
+    return OCH_OK;
+}
+
+// One camera launch of frame f: the schedule with the launch's timing, the plan of
+// this geometry (split: its split form too), the tile table, the launch, the timing's
+// end.  CAMERA_LAUNCH's launch expression takes the schedule as `sc`; a failure names it.
+template <class Launch>
+int camera_launch(och_gpu_pool *p, const och::DevFrame &f, bool bounce, bool split, const char *what, Launch launch)
+{
+    int ts;
+    och::Schedule sc = timed_schedule(p, ts);
+    if (ts) return ts;
+    use_plan(p, f, bounce, split, sc);
+    if (int us = use_tiles(p, f, bounce, sc)) return us;
+    const hipError_t e = launch(sc);
+    if (e != hipSuccess) return fail(OCH_E_HIP, "%s: %s", what, hipGetErrorString(e));
+    return timed_done(p, sc, true);
+}
+#define CAMERA_LAUNCH(p, f, bounce, split, call) \
+    camera_launch(p, f, bounce, split, #call, [&](const och::Schedule &sc) { return call; })
+
+// A host form: render(scratch) into the pool's scratch (pixels words and `spare`
+// bytes), then the pixels to the caller's rgba, complete on return.
+template <class Render>
+int to_host(och_gpu_pool *p, size_t pixels, size_t spare, uint32_t *rgba, Render render)
+{
+    DeviceGuard g(p->device);
+    int st = ensure_scratch(p, pixels * 4 + spare);
+    if (st != OCH_OK) return st;
+    st = render(reinterpret_cast<uint32_t *>(p->scratch.d));
+    if (st != OCH_OK) return st;
+    OCH_HIP(hipMemcpyAsync(rgba, p->scratch.d, pixels * 4, hipMemcpyDeviceToHost, p->stream()));
+    OCH_HIP(hipStreamSynchronize(p->stream()));
+    return OCH_OK;
+}
+
 }  // namespace
 
-OCH_API int och_gpu_set_launch_events(och_gpu_pool *p, void *start_event, void *stop_event)
+OCH_API int och_gpu_occupancy(const och_gpu_pool *p, int kind, int *blocks_per_cu)
 {
-    if (!p) return fail(OCH_E_INVALID, "pool is NULL");
-    p->next_ev_start = static_cast<hipEvent_t>(start_event);
-    p->next_ev_stop = static_cast<hipEvent_t>(stop_event);
+    if (!p || !blocks_per_cu) return fail(OCH_E_INVALID, "NULL argument");
+    DeviceGuard g(p->device);
+    OCH_HIP(och::occupancy_blocks_per_cu(kind, p->opt_block, p->depth, blocks_per_cu));
     return OCH_OK;
 }
 
@@ -1606,92 +513,6 @@ OCH_API int och_shard_rows(int height, int row_chunk, int n_shards)
 }
 
 namespace {
-
-// The launch order of frame f under OCH_OPT_TILE_ORDER 2 / 3: the pool's plan
-// (och_gpu_plan_views) when it was made for this geometry, else none (natural
-// order).  split: the launch can run the plan's split form (the grid kernel);
-// without it the order stays an unsplit permutation of the frame's grid.
-void use_plan(const och_gpu_pool *p, const och::DevFrame &f, bool bounce, bool split, och::Schedule &sc)
-{
-    const LaunchPlan &plan = p->plans[bounce ? 1 : 0];
-    if (p->opt_tile_order < 2 || !plan.order.d) return;
-    int64_t key[9];
-    frame_key(p, f, bounce, key);
-    if (!plan.matches(key)) return;
-    sc.order = p->opt_tile_order == 3 ? plan.order_xcd.d : plan.order.d;
-    sc.order_n = plan.blocks;
-    // the plan's split form, while the options it was made with hold
-    const SplitPlan &sp = p->split;
-    if (split && !bounce && p->opt_tile_order == 2 && sp.n && p->dev().packed && p->opt_split == sp.params[0] &&
-        p->opt_split_segs == sp.params[1] && p->opt_split_level == sp.params[2]) {
-        sc.order = sp.order.d;
-        sc.order_n = sp.n;
-        sc.split_extra = sp.extra;
-        sc.split_tasks = sp.tasks.d;
-        sc.split_level = (uint32_t)p->opt_split_level;
-    }
-}
-
-// The tile table of frame f's launch under sc (after use_plan): the pool's
-// table of this geometry, block size and launch order, made and uploaded when
-// the pool holds none.  Nothing in it depends on the cameras.  bounce: the
-// config-5 kernel's launch (its own block size).
-int use_tiles(och_gpu_pool *p, const och::DevFrame &f, bool bounce, och::Schedule &sc)
-{
-    const int block = bounce ? std::max(och::kBounceBlock, sc.block) : sc.block;
-    const LaunchPlan &plan = p->plans[bounce ? 1 : 0];
-    // the launch order: the split plan's, the plan's (whole, or grouped per XCD), or none
-    const std::vector<uint32_t> *order = nullptr, *tasks = nullptr;
-    int mode = sc.tile_order == 1 ? 1 : 0;
-    if (sc.split_tasks) {
-        order = &p->split.h_order;
-        tasks = &p->split.h_tasks;
-        mode = 4;
-    } else if (sc.order) {
-        mode = p->opt_tile_order == 3 ? 3 : 2;
-        order = mode == 3 ? &plan.h_order_xcd : &plan.h_order;
-    }
-    const int64_t key[12] = {f.cams[0].width, f.cams[0].height, f.n_views, f.row_chunk, f.shard, f.n_shards,
-                             f.slice_rows, block, mode, f.chunk_map ? (int64_t)p->deal_serial : 0,
-                             order ? (int64_t)plan.serial : 0, bounce ? 1 : 0};
-    TileTable *t = nullptr, *oldest = &p->tile_tables[0];
-    for (TileTable &c : p->tile_tables) {
-        if (c.used && std::memcmp(c.key, key, sizeof key) == 0) t = &c;
-        if (c.used < oldest->used) oldest = &c;
-    }
-    if (!t) {
-        och::plan::TileGeometry g = {f.cams[0].width, f.cams[0].height, f.n_views, f.row_chunk, f.shard, f.n_shards,
-                                     f.slice_rows, block, mode == 1 ? 1 : 0, nullptr};
-        if (f.chunk_map) g.chunk_map = p->h_chunk_map.data() + (size_t)f.shard * p->deal_max;
-        std::vector<uint64_t> table;
-        uint32_t grid = 0;
-        // a plan of another grid (stale, or for another block size) is not this launch's: natural order
-        const uint32_t blocks = (uint32_t)(((uint64_t)f.n_views * ((f.cams[0].width + 7) / 8) * ((f.slice_rows + 7) / 8) * 64 +
-                                            block - 1) / block);
-        if (order && mode != 4 && order->size() != blocks) order = nullptr;
-        const char *why = "";
-        if (int st = och::plan::tile_table(g, order ? order->data() : nullptr, order ? (uint32_t)order->size() : 0u,
-                                           tasks ? tasks->data() : nullptr, tasks ? (uint32_t)tasks->size() : 0u, table,
-                                           grid, &why))
-            return fail(st, "tile table of a %d x %d frame, %d views: %s", g.width, g.height, g.n_views, why);
-        t = oldest;
-        if (t->used) {                          // launches in flight on other streams may read the table it replaces
-            t->used = 0;
-            if (int ds = och::pool_drain(p)) return ds;
-        }
-        OCH_HIP(t->d.upload(table));
-        t->n = (uint32_t)table.size();
-        t->grid = grid;
-        t->block = (uint32_t)block;
-        std::memcpy(t->key, key, sizeof key);
-    }
-    t->used = ++p->tile_clock;
-    sc.tiles = t->d.d;
-    sc.tiles_n = t->n;
-    sc.tiles_grid = t->grid;
-    sc.tiles_block = t->block;
-    return OCH_OK;
-}
 
 // `what` (code frames of some kind) needs the code table of a palette small enough for 1-byte codes.
 static int needs_code_palette(const och_gpu_pool *p, const char *what)
@@ -2067,8 +888,6 @@ OCH_API int och_light_check(const och_light *l)
     return OCH_OK;
 }
 
-}  // extern "C"
-
 namespace {
 
 // och_gpu_render_lit_views_dev / _lit_masks_views_dev / _lit_codes_views_dev:
@@ -2096,8 +915,6 @@ int render_lit_views(och_gpu_pool *p, const och_camera *cams, int n_views, const
 }
 
 }  // namespace
-
-extern "C" {
 
 OCH_API int och_gpu_render_lit_views_dev(och_gpu_pool *p, const och_camera *cams, int n_views, const och_light *light,
                                          uint32_t *rgba_slices, size_t capacity_pixels, int row_chunk, int shard,
@@ -2220,8 +1037,6 @@ OCH_API int och_gpu_render_lit_steps_dev(och_gpu_pool *p, const och_camera *cams
     return st;
 }
 
-}  // extern "C"
-
 int och::sharded_steps(och_gpu_pool *p, och_comm *comm, const och_camera *cams, int n_views, int n_steps,
                        void *const *streams, uint8_t *const *slices, uint8_t *const *gathered, uint32_t *const *frames,
                        int n_buffers, void *const *start_events, void *const *stop_events, int row_chunk, int bounce,
@@ -2299,8 +1114,6 @@ int och::sharded_steps(och_gpu_pool *p, och_comm *comm, const och_camera *cams, 
     }
     return st;
 }
-
-extern "C" {
 
 OCH_API int och_gpu_render_sharded_steps_dev(och_gpu_pool *p, och_comm *comm, const och_camera *cams, int n_views,
                                              int n_steps, void *const *streams, uint8_t *const *slices,
@@ -2392,50 +1205,3 @@ OCH_API int och_gpu_render_ssaa(och_gpu_pool *p, const och_camera *cam, int s, u
     return to_host(p, pixels, 4, rgba,
                    [&](uint32_t *scratch) { return och_gpu_render_ssaa_views_dev(p, cam, 1, s, scratch, pixels); });
 }
-
-OCH_API int och_pool_pack(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, int index_base,
-                          uint32_t *out, uint32_t out_capacity, uint32_t *out_nodes, uint32_t *out_root)
-{
-    if (!nodes || !out_nodes || !out_root) return fail(OCH_E_INVALID, "NULL argument");
-    int st = validate_pool(nodes, n_nodes, root, depth, index_base);
-    if (st != OCH_OK) return st;
-    std::vector<uint32_t> packed;
-    uint32_t proot = 0;
-    if (!pack_pool(nodes, n_nodes, root, depth, index_base, packed, proot))
-        return fail(OCH_E_CAPACITY, "more than 2^24 - 1 (node, level) pairs");
-    *out_nodes = (uint32_t)(packed.size() / 8);
-    *out_root = proot;
-    if (out) {
-        if (out_capacity < *out_nodes) return fail(OCH_E_CAPACITY, "output holds %u nodes, %u needed", out_capacity, *out_nodes);
-        std::memcpy(out, packed.data(), packed.size() * 4);
-    }
-    return OCH_OK;
-}
-
-OCH_API int och_pool_occupied_box(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, int index_base,
-                                  int32_t lo[3], int32_t hi[3])
-{
-    if (!nodes || !lo || !hi) return fail(OCH_E_INVALID, "NULL argument");
-    if (index_base != 0 && index_base != 1) return fail(OCH_E_INVALID, "index_base must be 0 or 1");
-    const int st = validate_pool(nodes, n_nodes, root, depth, index_base);
-    if (st != OCH_OK) return st;
-    if (!och::occupied_box(nodes, n_nodes, root, depth, index_base, lo, hi))
-        for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0;
-    return OCH_OK;
-}
-
-OCH_API uint32_t och_pool_at(const uint32_t *nodes, uint32_t root, int depth, int index_base, int x, int y, int z)
-{
-    // h_octree::at (ORT/och_h_octree.h:239-258) with the child digit of z_encode_16.
-    if (!nodes || (index_base == 1 && root == 0)) return 0;
-    uint32_t cur = root;
-    for (int l = depth - 1; l >= 0; --l) {
-        const int c = ((x >> l) & 1) | (((y >> l) & 1) << 1) | (((z >> l) & 1) << 2);
-        const uint32_t nx = nodes[(size_t)(cur - index_base) * 8 + c];
-        if (l == 0 || !nx) return nx;
-        cur = nx;
-    }
-    return 0;
-}
-
-}  // extern "C"

@@ -376,8 +376,6 @@ int build_dag_gpu(const Terrain &tr, uint32_t cap, const std::vector<uint32_t> &
 
 }  // namespace
 
-extern "C" {
-
 OCH_API void och_host_pool_free(och_host_pool *p)
 {
     if (!p) return;
@@ -554,5 +552,3 @@ OCH_API int och_edit_voxels(const och_edit_params *params, och_host_pool *out)
     }
     return finish_pool(out, nodes, n_out, root, 1, P.depth, vs, t_start);
 }
-
-}  // extern "C"

@@ -170,8 +170,6 @@ void comm_abort(och_comm *c)
 
 }  // namespace och
 
-extern "C" {
-
 OCH_API int och_comm_unique_id(uint8_t *id)
 {
     if (!id) return fail(OCH_E_INVALID, "NULL id buffer");
@@ -252,5 +250,3 @@ OCH_API int och_comm_gather(och_comm *c, const void *send, void *recv, size_t by
     DeviceGuard g(c ? c->device : -1);
     return och::comm_gather(c, send, recv, bytes, root, static_cast<hipStream_t>(stream));
 }
-
-}  // extern "C"

@@ -335,8 +335,6 @@ struct och_editor {
     }
 };
 
-extern "C" {
-
 OCH_API int och_editor_create(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, uint32_t capacity,
                               och_editor **out)
 {
@@ -506,5 +504,3 @@ OCH_API int och_editor_flush(och_editor *e, och_gpu_pool *pool)
     e->root_dirty = false;
     return OCH_OK;
 }
-
-}  // extern "C"

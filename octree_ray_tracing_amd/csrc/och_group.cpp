@@ -260,8 +260,6 @@ int render_steps(och_frame_group *g, const och_camera *cams, int n_views, int n_
 
 }  // namespace
 
-extern "C" {
-
 OCH_API int och_frame_group_create(const int *devices, int n_devices, const uint32_t *nodes, uint32_t n_nodes,
                                    uint32_t root, int depth, int index_base, float miss_t, och_frame_group **out)
 {
@@ -455,5 +453,3 @@ OCH_API int och_frame_group_synchronize(och_frame_group *g)
     if (!g) return fail(OCH_E_INVALID, "NULL group");
     return sync_all(g);
 }
-
-}  // extern "C"

@@ -1,10 +1,7 @@
-// och_host.h -- the host layer's shared plumbing (och_api.cpp, och_group.cpp,
-// och_comm.cpp): the error text, the device guard, the device-memory owner
-// and the internal entry points these files call in each other.  Host only,
-// not part of the public ABI.
-//
-// The Makefile's dependency lists do not name this header: after editing it,
-// run `make clean` or touch the .cpp files.
+// och_host.h -- the host layer's shared plumbing (och_pool.cpp, och_api.cpp,
+// och_rcp.cpp, och_group.cpp, och_comm.cpp): the error text, the device guard,
+// the device-memory owner and the internal entry points these files call in each
+// other.  Host only, not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,7 +15,7 @@ typedef struct ncclComm *ncclComm_t;    // as <rccl/rccl.h> declares it
 namespace och {
 
 // Record the formatted text as och_last_error's (this thread's) and return
-// status (och_api.cpp, beside the text; och::report is its one-string form).
+// status (och_pool.cpp, beside the text; och::report is its one-string form).
 int fail(int status, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 #define OCH_HIP(expr)                                                                             \

@@ -1,5 +1,6 @@
-// och_internal.h -- shared between the C-ABI layer (och_api.cpp) and the
-// gfx950 kernels (och_kernels.hip).  Not part of the public ABI.
+// och_internal.h -- shared between the C-ABI layer (och_pool.cpp the pool,
+// och_api.cpp the launches, och_editor.cpp, och_group.cpp, och_comm.cpp) and
+// the gfx950 kernels (och_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -41,7 +42,7 @@ struct DevPool {
     float cull_lo[3], cull_hi[3];
     // camera_proven_miss (the cull's cheaper test before a camera ray's setup)
     // budgets the RCPPS table's relative error: 1 only when the uploaded
-    // table's maximum error is within kCameraCullRcpError (och_api.cpp).
+    // table's maximum error is within kCameraCullRcpError (och_pool.cpp).
     int32_t cam_cull;
 };
 

@@ -37,7 +37,7 @@
 // hipGetLastError() after it: that call also returns an error left behind by
 // any earlier HIP call of the thread (another library's -- RCCL's communicator
 // init, say), which is not this launch's.  The cleared error is kept for
-// och_discarded_error (clear_pending_error, och_api.cpp).
+// och_discarded_error (clear_pending_error, och_pool.cpp).
 // A traversal launch, timed by the dispatch itself when the schedule carries
 // events (Schedule::ev_start / ev_stop, OCH_OPT_TIMING): hipExtLaunchKernel
 // takes the kernel's own start and end times, with no packets of its own
@@ -77,7 +77,7 @@ __device__ __forceinline__ uint32_t rcpps_model(uint32_t x, uint32_t ent)
 }
 
 // The same for x = -|d| (sign set) from the device table, whose entries carry
-// + 127 << 23 (och_api.cpp upload_lut): while the result exponent ent_e + 127 - e
+// + 127 << 23 (och_pool.cpp upload_lut): while the result exponent ent_e + 127 - e
 // stays in 1..254 -- every x whose exponent bits lie in [xlo, xlo + xspan), a
 // range the host derives from the table (DevPool::rcp_xlo / rcp_xspan) -- the
 // model is one subtraction of x's exponent bits from the entry.  Other x
@@ -724,7 +724,7 @@ __device__ __forceinline__ void camera_rot(const och_camera &C, int col, int row
 // this test's own roundings), ray_cull's exact test is true for the real box
 // and the ray ends as the MISS -- decided here with an approximate
 // reciprocal and no correctly rounded divide or square root.  A pool whose
-// table exceeds the bound (P.cam_cull = 0, och_api.cpp upload_lut) skips
+// table exceeds the bound (P.cam_cull = 0, och_pool.cpp upload_lut) skips
 // this test and leaves every ray to ray_cull.  Same preconditions as
 // ray_cull: origin inside (1, 2)^3, no component below 2^-60 of the largest
 // (so every c_a is a normal float below 2^61).  Rays that fail the test take
@@ -869,7 +869,7 @@ struct TiledArraySource {
 // one 8x8 pixel tile of one view per wave.  Which tile a wave of the launch
 // walks is not computed here: the host lays the launch out as a table of tile
 // descriptors, one per wave in launch order (och::plan::tile_table in
-// och_api.cpp: row-major tiles, supertiles grouped per XCD, a planned order,
+// och_tiles.cpp: row-major tiles, supertiles grouped per XCD, a planned order,
 // all baked in), which depends on the frame's geometry and the launch order
 // but never on the cameras.  The output token is view * slice_pixels + slice
 // pixel.
@@ -1800,7 +1800,7 @@ __global__ __launch_bounds__(256) void k_unshard(const uint32_t *__restrict__ ga
 }
 
 // gathered codes [n_shards][n_views][slice_rows][width] -> RGBA8 frames
-// [n_views][height][width] through the 256-entry code table (och_api.cpp
+// [n_views][height][width] through the 256-entry code table (och_pool.cpp
 // code_table: palette words, the fixed colours, the halved blocked variants).
 __global__ __launch_bounds__(256) void k_shade_unshard(const uint8_t *__restrict__ gathered, uint32_t *__restrict__ frames,
                                                        const uint32_t *__restrict__ table, int width, int height,

@@ -23,6 +23,22 @@ def test_library_exports_every_declared_symbol(ort):
         assert hasattr(lib, name), name
 
 
+def test_library_exports_no_undeclared_c_name(ort):
+    """The converse: a global function of the library under a plain C name (no leading
+    underscore, so neither mangled C++ nor the toolchain's own) is one include/och_gpu.h
+    declares.  A helper that slips into C linkage would be a name an application can collide with."""
+    import shutil
+    import subprocess
+    nm = shutil.which("nm")
+    if nm is None:
+        pytest.skip("no nm")
+    out = subprocess.run([nm, "-D", "--defined-only", ort.load()._name], capture_output=True, text=True, check=True).stdout
+    names = [w[2] for w in (line.split() for line in out.splitlines()) if len(w) == 3 and w[1] == "T" and not w[2].startswith("_")]
+    assert len(names) >= len(declared_symbols(ort))
+    declared = set(declared_symbols(ort))
+    assert [n for n in names if not n.startswith("och_") or n not in declared] == []
+
+
 def test_abi_version(ort):
     assert ort._lib.call("och_abi_version") == 1
 

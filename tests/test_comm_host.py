@@ -6,7 +6,7 @@ a small C++ program linked against liboch_gpu.so, over a fake handle that is
 never dereferenced.
 
 The same driver, compiled with -DOCH_COMM_HOST_STANDALONE together with
-och_comm.cpp (no library; the two och_api.cpp symbols it needs are stubbed
+och_comm.cpp (no library; the two och_pool.cpp symbols it needs are stubbed
 below), is the program to run under -fsanitize=thread.
 """
 import shutil
@@ -35,7 +35,7 @@ typedef struct ncclComm *ncclComm_t;
 namespace och {
 och_comm *comm_adopt(ncclComm_t comm, int n_ranks, int rank, int device);
 ncclComm_t comm_take(och_comm *comm);
-#ifdef OCH_COMM_HOST_STANDALONE             // what och_comm.cpp takes from och_api.cpp
+#ifdef OCH_COMM_HOST_STANDALONE             // what och_comm.cpp takes from och_pool.cpp
 static thread_local std::string t_error;
 int fail(int status, const char *fmt, ...)
 {

@@ -1,9 +1,11 @@
-"""The launch planners of the C-ABI layer (och::plan in csrc/och_api.cpp), called
-without a device from a small C++ program linked against liboch_gpu.so.
+"""The launch planners of the C-ABI layer (och::plan in csrc/och_plan.cpp), called
+without a device from a small C++ program compiled from that file and its header.
 
 Frames do not depend on the launch order, so no GPU parity test can see a wrong
 order; this file is the pin.  Layer 1 asserts properties and hand-checkable
-cases from first principles.  Layer 2 compares the planners word for word with
+cases from first principles, and runs its cases once more through the same
+program built with AddressSanitizer and UBSan as a stand-alone binary: the
+planners index by computed sizes.  Layer 2 compares the planners word for word with
 tests/golden/plan_parent.npz: the outputs of the loop bodies these planners
 were lifted from (och_api.cpp at commit 8ac5967: the stable sort :1599-1601,
 plan_shape :1419-1442, the heavy-tile choice and split packing :1471-1474 and
@@ -17,6 +19,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+CSRC = Path(__file__).resolve().parents[1] / "octree_ray_tracing_amd" / "csrc"
 GOLDEN = Path(__file__).resolve().parent / "golden" / "plan_parent.npz"
 GOLDEN_SEED = 20261019
 IDLE = 0xFFFFFFFF
@@ -30,22 +33,7 @@ DRIVER = r'''
 #include <iostream>
 #include <string>
 #include <vector>
-namespace och {
-namespace plan {
-std::vector<uint32_t> by_cost(const std::vector<uint32_t> &costs);
-void shape(std::vector<uint32_t> &order, int mode);
-std::vector<uint32_t> group_by_xcd(const std::vector<uint32_t> &order, uint32_t tiles_x, uint32_t tiles_y, uint32_t block);
-std::vector<uint32_t> pack_split_tile(const int cnt[64], int S);
-struct Split {
-    std::vector<uint32_t> order, tasks;
-    uint32_t tiles = 0, extra = 0;
-};
-Split split_order(const std::vector<uint16_t> &push, int W, int rows, const std::vector<uint32_t> &by_cost,
-                  const std::vector<uint32_t> &order, const std::vector<uint32_t> &c, int pct, int S);
-std::vector<float> spread_chunk_costs(const std::vector<uint32_t> &c, int n_views, int W, int H, uint32_t per_block,
-                                      int row_chunk);
-}
-}
+#include "och_plan.h"
 using namespace och::plan;
 template <class T>
 static std::vector<T> rd()
@@ -131,18 +119,26 @@ def run_driver(exe, commands):
     return out
 
 
+def compile_driver(tmp, name, cc, flags):
+    src, exe = tmp / "plan_host.cpp", tmp / name
+    src.write_text(DRIVER)
+    run = subprocess.run([*cc, "-std=c++17", "-O1", "-g", "-Wall", *flags, f"-I{CSRC}", str(src),
+                          str(CSRC / "och_plan.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr[-3000:]
+    return exe
+
+
 @pytest.fixture(scope="module")
-def planner(ort, tmp_path_factory):
+def tmp(tmp_path_factory):
+    return tmp_path_factory.mktemp("plan_host")
+
+
+@pytest.fixture(scope="module")
+def planner(tmp):
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     if cxx is None:
         pytest.skip("no C++ compiler")
-    libdir = Path(ort.load()._name).resolve().parent
-    tmp = tmp_path_factory.mktemp("plan_host")
-    src, exe = tmp / "plan_host.cpp", tmp / "plan_host"
-    src.write_text(DRIVER)
-    cc = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", str(src), f"-L{libdir}", "-loch_gpu",
-                         f"-Wl,-rpath,{libdir}", "-o", str(exe)], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
+    exe = compile_driver(tmp, "plain", [cxx], [])
     return lambda commands: run_driver(exe, commands)
 
 
@@ -319,6 +315,51 @@ def test_split_order_cap_and_zero_threshold(planner):
     assert capped[0].size == 18 + (144 - 9)
     assert one[2].tolist() == [1, 1] and one[0].size == 2 + 8     # max(1, 9 / 16) = 1
     assert off[2].tolist() == [0, 0] and off[0].size == 0 and off[1].size == 0   # threshold 0: no split plan
+
+
+def layer1_commands():
+    """The inputs of the layer-1 tests above, from the same seeds."""
+    cmds = [command("by_cost", np.random.default_rng(1).integers(0, 6, 300)), command("by_cost", [])]
+    rng = np.random.default_rng(2)
+    for n in (0, 1, 2, 7, 100):
+        o = rng.permutation(n)
+        cmds += [command(f"shape {mode}", o) for mode in (0, 1, 10, 50, 99, 100)]
+    rng = np.random.default_rng(3)
+    cmds += [command(f"group {tx} {ty} {block}", rng.permutation(-(-tx * ty * views // (block // 64))))
+             for tx, ty, views, block in GROUP_CASES]
+    cmds += [command(f"pack {S}", cnt) for cnt in pack_cases().values() for S in (2, 4, 8, 16)]
+    for H, row_chunk in ((289, 8), (20, 3)):
+        for per_block in (1, 2, 4):
+            c = np.random.default_rng(5).integers(0, 1 << 20, -(-13 * -(-H // 8) // per_block))
+            cmds.append(command(f"spread 1 100 {H} {per_block} {row_chunk}", c))
+    rng = np.random.default_rng(6)
+    costs = rng.integers(50, 200, 16 * 9)
+    costs[37], costs[90] = 1000, 900
+    cmds.append(command("split 128 72 80 4 10", *split_inputs(costs, {37: np.full(64, 50), 90: rng.integers(0, 300, 64)})))
+    flat = split_inputs(np.full(16 * 9, 7), {t: np.full(64, 3) for t in range(16 * 9)})
+    cmds += [command("split 128 72 100 2 10", *flat), command("split 128 72 0 2 10", *flat),
+             command("split 24 24 100 2 10", *split_inputs(np.full(9, 7), {t: np.full(64, 3) for t in range(9)}, 3, 3))]
+    return cmds
+
+
+def test_under_address_and_undefined_sanitizers(planner, tmp):
+    """The same program as a stand-alone sanitized binary over the layer-1 inputs: no report
+    (either sanitizer ends the program with a failure), and the plain build's words."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    if Path(hipcc).exists():
+        cc, flags = [hipcc], ["-x", "c++"] + [f for s in san for f in ("-Xarch_host", s)]
+    else:
+        cxx = shutil.which("g++") or shutil.which("clang++")
+        if cxx is None:
+            pytest.skip("no C++ compiler")
+        cc, flags = [cxx], san
+    exe = compile_driver(tmp, "sanitized", cc, flags)
+    commands = layer1_commands()
+    got, want = run_driver(exe, commands), planner(commands)
+    assert len(got) == len(want) >= len(commands)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert np.array_equal(g, w), f"output {i} differs between the sanitized and the plain build"
 
 
 # ------------------------------------------------------------------ layer 2

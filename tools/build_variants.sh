@@ -22,10 +22,9 @@ for spec in "$@"; do
     name=${spec%%:*}
     [[ "$name" == *@* ]] && rm -f octree_ray_tracing_amd/csrc/och_kernels_${name%%@*}.hip
     name=${name%%@*}
+    # every object of the product's build but its kernels
     $HIPCC -shared -fPIC --offload-arch=gfx950 -o build_variants/liboch_gpu_$name.so build_variants/k_$name.o \
-        octree_ray_tracing_amd/csrc/build/och_api.o octree_ray_tracing_amd/csrc/build/och_builder.o \
-        octree_ray_tracing_amd/csrc/build/och_editor.o octree_ray_tracing_amd/csrc/build/och_group.o \
-        octree_ray_tracing_amd/csrc/build/och_comm.o -pthread -ldl
+        $(ls octree_ray_tracing_amd/csrc/build/*.o | grep -v '/och_kernels\.o$') -pthread -ldl
     rm -f build_variants/k_$name.o
 done
 ls -la build_variants
