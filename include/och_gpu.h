@@ -726,7 +726,8 @@ OCH_API int och_build_voxels(const och_voxel_params *params, och_host_pool *out)
  * node reachable at two heights.  OCH_E_CAPACITY: the caller's capacity is too
  * small.  OCH_E_NOMEM, OCH_E_NODEV, OCH_E_HIP as the builders.
  * Every call uploads, adopts, renumbers and returns the whole pool in host
- * memory; nothing stays on the device between calls.
+ * memory; nothing stays on the device between calls (och_world, below, is
+ * the same editor over a store that does stay).
  * OCH_BUILD_TRACE=1 prints phase times ("edit gpu " / "edit host "). */
 typedef struct och_edit_params {
     const uint32_t *nodes;  /* the pool to edit, host memory: n_nodes x 8, 1-based (h_octree form) */
@@ -758,6 +759,91 @@ OCH_API int och_pool_occupied_box(const uint32_t *nodes, uint32_t n_nodes, uint3
 /* h_octree::at over any pool (ORT/och_h_octree.h:239-258). */
 OCH_API uint32_t och_pool_at(const uint32_t *nodes, uint32_t root, int depth, int index_base,
                              int x, int y, int z);
+
+/* ------------------------------------------------------------ world */
+/* A DAG that stays on one GPU between brush strokes: the node store
+ * och_edit_voxels builds per call (nodes, levels, hash table), kept, with the
+ * current root, a stream and the stroke's work buffers.  och_world_edit applies
+ * a list of records to it as och_edit_voxels would and replaces the root;
+ * och_world_flush publishes the new nodes to a pool made by
+ * och_world_pool_create, which traces and renders like any other pool.
+ * The store is append-only: a stroke only adds nodes, so every earlier root,
+ * and every frame in flight that walks from one, stays valid, and a flush
+ * waits for no kernel.  Ids are handed out in claim order and mean something
+ * only inside one world and generation; och_world_download gives the canonical
+ * pool.  What strokes no longer reach stays in the store until
+ * och_world_compact.
+ * GPU only (OCH_E_NODEV without a device), 1-based pools, depth 1..21, one
+ * thread at a time per world, like the editor.  After a HIP failure inside a
+ * stroke the world is broken: every later call on it but och_world_destroy
+ * returns OCH_E_INVALID; pools keep what their last flush gave them.
+ * OCH_BUILD_TRACE=1 prints phase times ("world ").
+ * Out of scope: worlds replicated across GPUs, frame groups and the sharded
+ * paths; 0-based pools; undo or checkout of older roots; a single-voxel `at`
+ * on the device; a tight box after removals; depth 22. */
+typedef struct och_world och_world;
+
+typedef struct och_world_stats {
+    uint32_t capacity;    /* ids, id 0 included */
+    uint32_t used;        /* ids handed out, id 0 included */
+    uint32_t root;        /* store id (0 = no voxels); means something only inside this world and generation */
+    int32_t depth, device;
+    uint64_t strokes;     /* edits applied since create */
+    uint64_t generation;  /* +1 per och_world_compact: store ids of another generation mean nothing */
+    int32_t box_lo[3], box_hi[3];  /* a superset of the voxels' box, [lo, hi); lo = hi = 0: none */
+} och_world_stats;
+
+/* Adopt a pool: what och_edit_voxels accepts as its pool (host memory,
+ * 1-based, not necessarily canonical; n_nodes = 0 or root = 0: an empty world
+ * to paint into), with its refusals before anything is touched
+ * (OCH_E_INVALID: depth outside 1..21, nodes NULL with n_nodes > 0,
+ * root > n_nodes, a child word past the end, a node at two heights).
+ * capacity = ids to reserve, id 0 included and fixed for the world's life;
+ * 0 = twice the reachable nodes + 64 * depth.  OCH_E_CAPACITY: fewer than the
+ * reachable nodes + 1; OCH_E_INVALID: 2^29 - 1 or more.  device < 0: the
+ * current one.  The box starts as och_pool_occupied_box of the nodes. */
+OCH_API int och_world_create(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, uint32_t capacity,
+                             int device, och_world **out);
+OCH_API int och_world_destroy(och_world *world);
+OCH_API int och_world_info(const och_world *world, och_world_stats *info);
+/* One stroke: n records as OCH_VOXELS_LIST (host memory, or device memory of
+ * the world's device with its writes complete; n < 2^31, n = 0 is a no-op)
+ * with och_edit_voxels' semantics -- in order, last wins, id 0 removes, out of
+ * range ignored, any uint32 id.  Nothing of the pool is uploaded, reached,
+ * adopted, renumbered, counted or downloaded.
+ * OCH_E_CAPACITY, with the world unchanged, when used + the level counts of
+ * the stroke's unique in-range keys > capacity: one id per row of the
+ * records' own tree, ignoring what the rows share with the store, so the
+ * answer depends on the records alone.  Call och_world_compact and retry.
+ * The box grows by the box of the stroke's in-range records with id != 0;
+ * removals never shrink it. */
+OCH_API int och_world_edit(och_world *world, const void *records, uint64_t n, int on_device);
+/* A pool of the current world on the world's device: index_base 1, the
+ * world's depth, miss t = +INF, capacity slots (och_pool_info.n_nodes), its
+ * raw layout the store's rows, its packed layout (capacity <= 2^24; raw only
+ * above) numbered like them.  The caller destroys it, before or after the
+ * world.  It has no host mirror: och_gpu_pool_update and och_editor_flush on
+ * it return OCH_E_INVALID.  Everything else about a pool works unchanged. */
+OCH_API int och_world_pool_create(och_world *world, och_gpu_pool **out);
+/* Publish the strokes since the pool's last flush: the ids handed out since
+ * then are copied and packed on the device, then both roots and the box are
+ * published.  Complete on return.  The ids written are reached by no root
+ * published before, so launches in flight are not waited for -- except after a
+ * compaction, which renumbers: the flush then waits for all work on the device
+ * and rewrites the pool whole (a failure then leaves the pool torn, as a
+ * failed och_editor_flush does, until a later flush succeeds; any other failed
+ * flush leaves the pool showing its last one).  OCH_E_INVALID for a pool not
+ * made from this world. */
+OCH_API int och_world_flush(och_world *world, och_gpu_pool *pool);
+/* The canonical pool of the world's voxels with its statistics, slot for slot
+ * what och_build_voxels / och_edit_voxels give for the same content; freed
+ * with och_host_pool_free.  The world is unchanged: the save path. */
+OCH_API int och_world_download(och_world *world, och_host_pool *out);
+/* Drop what the root no longer reaches: the reachable nodes renumbered on the
+ * device and interned into a fresh store of the same capacity.  Content, box
+ * and capacity are unchanged, `used` becomes the distinct nodes + 1,
+ * generation + 1; every pool is rewritten whole by its next flush. */
+OCH_API int och_world_compact(och_world *world);
 
 /* ------------------------------------------------------------ editor */
 /* Interactive editing (the demo's place/remove, ORT/test_och_h_octree.cpp:

@@ -57,6 +57,8 @@ public:
     {
         check(och_gpu_pool_create(nodes, n_nodes, root, depth, index_base, miss_t, device, &pool_), "och_gpu_pool_create");
     }
+    // A pool the library made (world::make_pool); the tree owns it.
+    explicit tree(och_gpu_pool *adopted) : pool_(adopted) {}
     tree(const tree &) = delete;
     tree &operator=(const tree &) = delete;
     ~tree() { och_gpu_pool_destroy(pool_); }
@@ -248,6 +250,51 @@ inline host_pool edit_voxels(const och_edit_params &params)
     check(och_edit_voxels(&params, p.out()), "och_edit_voxels");
     return p;
 }
+
+// A world that stays on one GPU between brush strokes (och_world_*): edit()
+// applies a record list as edit_voxels would, flush() publishes the stroke's
+// new nodes to a tree made by make_pool(), download() gives the canonical pool.
+class world {
+public:
+    world(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, uint32_t capacity = 0, int device = -1)
+    {
+        check(och_world_create(nodes, n_nodes, root, depth, capacity, device, &w_), "och_world_create");
+    }
+    world(const world &) = delete;
+    world &operator=(const world &) = delete;
+    ~world() { och_world_destroy(w_); }
+
+    // One stroke: n records of (x, y, z, id); OCH_E_CAPACITY leaves the world as it was (compact() and retry).
+    void edit(const uint32_t *records, uint64_t n, bool on_device = false)
+    {
+        check(och_world_edit(w_, records, n, on_device ? 1 : 0), "och_world_edit");
+    }
+    tree make_pool()
+    {
+        och_gpu_pool *p = nullptr;
+        check(och_world_pool_create(w_, &p), "och_world_pool_create");
+        return tree(p);
+    }
+    void flush(tree &t) { check(och_world_flush(w_, t.handle()), "och_world_flush"); }
+    host_pool download()
+    {
+        host_pool p;
+        check(och_world_download(w_, p.out()), "och_world_download");
+        return p;
+    }
+    void compact() { check(och_world_compact(w_), "och_world_compact"); }
+    och_world_stats info() const
+    {
+        och_world_stats st;
+        check(och_world_info(w_, &st), "och_world_info");
+        return st;
+    }
+
+    och_world *handle() const { return w_; }
+
+private:
+    och_world *w_ = nullptr;
+};
 
 // Every GPU of the node from one host thread: a pool replica
 // per device, row chunks dealt round-robin, one RCCL all-gather, shading on

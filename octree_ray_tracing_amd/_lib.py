@@ -60,6 +60,13 @@ class EditorStats(C.Structure):
                 ("root", C.c_uint32), ("depth", C.c_int32), ("dirty_first", C.c_uint32), ("dirty_count", C.c_uint32)]
 
 
+class WorldStats(C.Structure):
+    """och_world_stats: what och_world_info reports."""
+    _fields_ = [("capacity", C.c_uint32), ("used", C.c_uint32), ("root", C.c_uint32), ("depth", C.c_int32),
+                ("device", C.c_int32), ("strokes", C.c_uint64), ("generation", C.c_uint64),
+                ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3)]
+
+
 class TerrainParams(C.Structure):
     _fields_ = [("depth", C.c_int32), ("tunnels", C.c_int32), ("dedup", C.c_int32),
                 ("rand_kind", C.c_int32), ("threads", C.c_int32), ("use_gpu", C.c_int32)]
@@ -159,6 +166,14 @@ PROTOTYPES = {
     "och_build_voxels": (C.c_int, [C.POINTER(VoxelParams), C.POINTER(HostPool)]),
     "och_edit_voxels": (C.c_int, [C.POINTER(EditParams), C.POINTER(HostPool)]),
     "och_host_pool_free": (None, [C.POINTER(HostPool)]),
+    "och_world_create": (C.c_int, [_P, _u32, _u32, C.c_int, _u32, C.c_int, C.POINTER(_P)]),
+    "och_world_destroy": (C.c_int, [_P]),
+    "och_world_info": (C.c_int, [_P, C.POINTER(WorldStats)]),
+    "och_world_edit": (C.c_int, [_P, _P, C.c_uint64, C.c_int]),
+    "och_world_pool_create": (C.c_int, [_P, C.POINTER(_P)]),
+    "och_world_flush": (C.c_int, [_P, _P]),
+    "och_world_download": (C.c_int, [_P, C.POINTER(HostPool)]),
+    "och_world_compact": (C.c_int, [_P]),
     "och_pool_pack": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "och_pool_at": (_u32, [_P, _u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "och_pool_occupied_box": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _P]),

@@ -1,11 +1,12 @@
 // och_builder.cpp -- the builders' C-ABI entries (och_build_terrain,
-// och_build_voxels, och_edit_voxels, och_host_pool_free) and the terrain
+// och_build_voxels, och_edit_voxels, och_host_pool_free, och_world_*) and the terrain
 // builder: the demo terrain's canonical DAG, built bottom-up in parallel.  The
 // DAG stores, their kernels and the renumbering are och_dag.h's; the voxel
 // builder, which builds the same DAG from a caller's voxels, is
 // och_voxel_build.h; the batch editor, which applies a list of edits to an
-// existing pool, is och_voxel_edit.h.  One translation unit: the headers are
-// included here and nowhere else.
+// existing pool, is och_voxel_edit.h; the resident world, which keeps that
+// editor's store on the device between strokes, is och_world.h.  One
+// translation unit: the headers are included here and nowhere else.
 //
 // The reference builds its tree by recursive create_volume + per-voxel
 // h_octree::set edits (ORT/test_och_h_octree.cpp:651-695, :767-787;
@@ -35,6 +36,7 @@
 #include "och_terrain.h"
 #include "och_voxel_build.h"
 #include "och_voxel_edit.h"
+#include "och_world.h"
 
 namespace {
 

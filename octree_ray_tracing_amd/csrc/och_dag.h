@@ -354,9 +354,11 @@ bool gpu_present()
 
 // The device buffers and the one stream of a GPU build on the current device:
 // when the scope ends the stream is synchronised and destroyed and the buffers
-// are freed, whatever the build returned.
+// are freed, whatever the build returned.  A scope that borrows its stream (a
+// world's, och_world.h) synchronises it and leaves it to its owner.
 struct GpuScope {
     hipStream_t st = nullptr;
+    bool own_stream = true;
     std::vector<void *> bufs;
 
     GpuScope() = default;
@@ -366,10 +368,11 @@ struct GpuScope {
     {
         if (st) {
             (void)hipStreamSynchronize(st);
-            (void)hipStreamDestroy(st);
+            if (own_stream) (void)hipStreamDestroy(st);
         }
         for (void *p : bufs) (void)hipFree(p);
     }
+    explicit GpuScope(hipStream_t borrowed) : st(borrowed), own_stream(false) {}
     int open()
     {
         if (!gpu_present()) return OCH_E_NODEV;
@@ -693,7 +696,8 @@ struct DevicePool {
 
 // The store's nodes reachable from root (!= 0), renumbered breadth-first and
 // 1-based on the device (k_bfs_*), with buffers of the build's scope.
-// *out: malloc'd n_out x 8 words, as renumber().
+// *out: malloc'd n_out x 8 words, as renumber(); out = null leaves the pool on
+// the device only (dev).
 int renumber_gpu(const GpuStore &S, uint32_t used, uint32_t root, int depth, GpuScope &G, uint32_t **out, uint32_t *n_out,
                  bool trace, DevicePool *dev = nullptr)
 {
@@ -739,6 +743,8 @@ int renumber_gpu(const GpuStore &S, uint32_t used, uint32_t root, int depth, Gpu
     }
     hipLaunchKernelGGL(k_bfs_output, blocks((size_t)n * 8), dim3(256), 0, st, S.nodes, S.level, d_order, d_newid, n, d_out);
     GPU_TRY(hipGetLastError());
+    *n_out = n;
+    if (!out) return OCH_OK;
     uint32_t *nodes = static_cast<uint32_t *>(std::malloc((size_t)n * 32));
     if (!nodes) return OCH_E_NOMEM;
     if (hipMemcpyAsync(nodes, d_out, (size_t)n * 32, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -747,7 +753,6 @@ int renumber_gpu(const GpuStore &S, uint32_t used, uint32_t root, int depth, Gpu
         return OCH_E_HIP;
     }
     *out = nodes;
-    *n_out = n;
     if (trace)
         std::fprintf(stderr, "[och_build] gpu renumbering %.3f s\n",
                      std::chrono::duration<double>(std::chrono::steady_clock::now() - t_bfs).count());

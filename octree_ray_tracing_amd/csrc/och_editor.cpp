@@ -18,7 +18,7 @@
 //    dead node's children and can share one slot between levels.
 //  * a full pool is reported (OCH_E_CAPACITY) before the edit starts and the
 //    tree is left unchanged; the reference exit(0)s mid-edit (:112-116).
-#include "och_internal.h"
+#include "och_host.h"
 
 #include <algorithm>
 #include <atomic>
@@ -463,6 +463,8 @@ OCH_API int och_editor_flush(och_editor *e, och_gpu_pool *pool)
     if (st != OCH_OK) return st;
     if (pi.index_base != 1 || pi.depth != e->depth || pi.n_nodes != e->capacity + 1)
         return och::report(OCH_E_INVALID, "och_editor_flush: the pool was not made from this editor's slots");
+    // a world's pool of the same size has no host mirror for the writes below
+    if (och::pool_world(pool)) return och::report(OCH_E_INVALID, "och_editor_flush: the pool belongs to an och_world");
     const uint32_t *pk = e->packed_ok ? e->packed.data() : nullptr;
     // Windowed only when this pool holds exactly what this editor's last flush
     // wrote: same pool (by serial -- a new pool can reuse a freed address) and

@@ -1,5 +1,6 @@
 // och_host.h -- the host layer's shared plumbing (och_pool.cpp, och_api.cpp,
-// och_rcp.cpp, och_group.cpp, och_comm.cpp): the error text, the device guard,
+// och_rcp.cpp, och_group.cpp, och_comm.cpp, och_editor.cpp and och_builder.cpp's
+// och_world.h): the error text, the device guard,
 // the device-memory owner and the internal entry points these files call in each
 // other.  Host only, not part of the public ABI.
 #pragma once
@@ -72,6 +73,27 @@ struct DevBuf {
         return e != hipSuccess ? e : hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
     }
 };
+
+// A resident world's pools (och_pool.cpp for och_world.h's och_world_pool_create
+// and och_world_flush; they stand here, not beside the editor's hooks in
+// och_internal.h, because that header is part of the identity of the kernel
+// source that the committed profiles are keyed by).
+// pool_create_for_world: a 1-based pool of `capacity` slots on `device` (current),
+// miss t = +INF, both layouts allocated (the packed one, numbered like the slots,
+// only for capacity <= 2^24), no content, root 0, no host mirror, marked with the
+// world's id.  pool_world: that id, 0 for any other pool -- och_gpu_pool_update
+// and och_editor_flush refuse a marked pool.  pool_world_view: the buffers the
+// flush's copy and pack kernel write and where the pool keeps what the last
+// flush published; OCH_E_INVALID unless the pool was made from `world`.
+struct WorldPoolView {
+    uint32_t *raw, *packed;   // n_nodes x 8 words each; packed = null: raw only
+    uint32_t n_nodes;
+    uint64_t *generation;     // the world generation of the published ids
+    uint32_t *published;      // ids [0, *published) are on the pool
+};
+int pool_create_for_world(int device, int depth, uint32_t capacity, uint64_t world, och_gpu_pool **out);
+uint64_t pool_world(const och_gpu_pool *pool);
+int pool_world_view(och_gpu_pool *pool, uint64_t world, WorldPoolView *view);
 
 // n_views views of one positive width and height (och_api.cpp).
 int check_views(const och_camera *cams, int n_views);

@@ -367,6 +367,34 @@ int upload_lut(och_gpu_pool *p, const uint32_t *lut, int log2_entries)
     return OCH_OK;
 }
 
+// A pool object of n_nodes device nodes, nothing allocated yet.
+och_gpu_pool *pool_new(int device, int depth, int index_base, float miss_t, uint32_t n_nodes)
+{
+    och_gpu_pool *p = new och_gpu_pool;
+    static std::atomic<uint64_t> next_serial{1};
+    p->serial = next_serial.fetch_add(1);
+    p->device = device;
+    p->depth = depth;
+    p->index_base = index_base;
+    p->miss_t = miss_t;
+    p->n_nodes = n_nodes;
+    return p;
+}
+
+// What every pool has besides its nodes: its stream, the timing events and this host's RCPPS table.
+int pool_equip(och_gpu_pool *p)
+{
+    if (hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess ||
+        // timing only: no system-scope release at the timed kernel's end
+        hipEventCreateWithFlags(&p->ev_start, hipEventDisableSystemFence) != hipSuccess ||
+        hipEventCreateWithFlags(&p->ev_stop, hipEventDisableSystemFence) != hipSuccess)
+        return fail(OCH_E_HIP, "stream/event creation failed");
+    // A host whose RCPPS does not fit the model leaves the pool without a table:
+    // tracing then fails with OCH_E_RCP_MODEL until och_gpu_set_rcp_lut is called.
+    const HostRcp &rc = host_rcp();
+    return rc.status == OCH_OK ? upload_lut(p, rc.lut.data(), rc.log2_entries) : OCH_OK;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------ create, destroy, info, update
@@ -386,15 +414,8 @@ OCH_API int och_gpu_pool_create(const uint32_t *nodes, uint32_t n_nodes, uint32_
     DeviceGuard g(device);
     if (!g.ok) return fail(OCH_E_HIP, "hipSetDevice(%d) failed", device);
 
-    och_gpu_pool *p = new och_gpu_pool;
-    static std::atomic<uint64_t> next_serial{1};
-    p->serial = next_serial.fetch_add(1);
-    p->device = device;
-    p->depth = depth;
-    p->index_base = index_base;
-    p->miss_t = miss_t;
+    och_gpu_pool *p = pool_new(device, depth, index_base, miss_t, n_nodes + (uint32_t)index_base);   // padding node 0 for 1-based pools
     p->root = root;
-    p->n_nodes = n_nodes + (uint32_t)index_base;   // padding node 0 for 1-based pools
     auto bail = [&](int s) { och_gpu_pool_destroy(p); return s; };
     if (p->d_nodes.reserve((size_t)p->n_nodes * 8) != hipSuccess)
         return bail(fail(OCH_E_NOMEM, "hipMalloc(%zu) failed", (size_t)p->n_nodes * 32));
@@ -405,21 +426,47 @@ OCH_API int och_gpu_pool_create(const uint32_t *nodes, uint32_t n_nodes, uint32_
     set_box(p, nodes, n_nodes);
     st = upload_packed(p, nodes, n_nodes);
     if (st != OCH_OK) return bail(st);
-    if (hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        // timing only: no system-scope release at the timed kernel's end
-        hipEventCreateWithFlags(&p->ev_start, hipEventDisableSystemFence) != hipSuccess ||
-        hipEventCreateWithFlags(&p->ev_stop, hipEventDisableSystemFence) != hipSuccess)
-        return bail(fail(OCH_E_HIP, "stream/event creation failed"));
-    const HostRcp &rc = host_rcp();
-    if (rc.status == OCH_OK) {
-        st = upload_lut(p, rc.lut.data(), rc.log2_entries);
-        if (st != OCH_OK) return bail(st);
-    }
-    // A host whose RCPPS does not fit the model leaves the pool without a table:
-    // tracing then fails with OCH_E_RCP_MODEL until och_gpu_set_rcp_lut is called.
+    st = pool_equip(p);
+    if (st != OCH_OK) return bail(st);
     *out = p;
     return OCH_OK;
 }
+
+// A world's pool (och_world.h): capacity slots in both layouts, the packed one
+// (capacity <= 2^24) numbered like the slots, nothing in them yet and no host
+// mirror; och_world_flush fills it.  The caller has the device current.
+int och::pool_create_for_world(int device, int depth, uint32_t capacity, uint64_t world, och_gpu_pool **out)
+{
+    och_gpu_pool *p = pool_new(device, depth, 1, INFINITY, capacity);
+    p->world = world;
+    auto bail = [&](int s) { och_gpu_pool_destroy(p); return s; };
+    if (p->d_nodes.reserve((size_t)capacity * 8) != hipSuccess ||
+        (capacity <= kIdLimit && p->d_packed.reserve((size_t)capacity * 8) != hipSuccess))
+        return bail(fail(OCH_E_NOMEM, "hipMalloc(%zu) failed", (size_t)capacity * 32));
+    if (hipMemset(p->d_nodes.d, 0, 32) != hipSuccess || (p->d_packed.d && hipMemset(p->d_packed.d, 0, 32) != hipSuccess))
+        return bail(fail(OCH_E_HIP, "hipMemset failed"));
+    if (p->d_packed.d) {
+        p->packed_nodes = capacity;
+        p->packed_by_slot = true;
+    }
+    const int st = pool_equip(p);
+    if (st != OCH_OK) return bail(st);
+    *out = p;
+    return OCH_OK;
+}
+
+int och::pool_world_view(och_gpu_pool *p, uint64_t world, WorldPoolView *v)
+{
+    if (!p || !v || !world || p->world != world) return fail(OCH_E_INVALID, "the pool was not made from this world");
+    v->raw = p->d_nodes.d;
+    v->packed = p->packed_by_slot ? p->d_packed.d : nullptr;
+    v->n_nodes = p->n_nodes;
+    v->generation = &p->world_generation;
+    v->published = &p->world_published;
+    return OCH_OK;
+}
+
+uint64_t och::pool_world(const och_gpu_pool *p) { return p ? p->world : 0; }
 
 OCH_API int och_gpu_pool_destroy(och_gpu_pool *p)
 {
@@ -455,6 +502,7 @@ OCH_API int och_gpu_pool_update(och_gpu_pool *p, uint32_t first, uint32_t count,
     OCH_ENTRY();
     if (!p || (count && !nodes)) return fail(OCH_E_INVALID, "pool/nodes is NULL");
     if (p->torn) return fail(OCH_E_INVALID, "pool left half written by a failed och_editor_flush: flush the editor again");
+    if (p->world) return fail(OCH_E_INVALID, "a world's pool has no host mirror: it is written by och_world_flush alone");
     const uint32_t n_user = p->n_nodes - (uint32_t)p->index_base;
     const uint32_t lo = p->index_base == 1 ? 1u : 0u;
     if (count && (first < lo || (uint64_t)first - lo + count > n_user))
@@ -511,7 +559,7 @@ int och::pool_drain(och_gpu_pool *p)
 int och::pool_write_slots(och_gpu_pool *p, uint32_t first, uint32_t count, const uint32_t *raw,
                           const uint32_t *packed, bool full)
 {
-    if (!p || p->index_base != 1 || (count && !raw)) return fail(OCH_E_INVALID, "bad editor flush");
+    if (!p || p->index_base != 1 || p->world || (count && !raw)) return fail(OCH_E_INVALID, "bad editor flush");
     if ((uint64_t)first + count > p->n_nodes || (full && (first != 0 || count != p->n_nodes)))
         return fail(OCH_E_INVALID, "editor window [%u, +%u) outside the pool", first, count);
     if (packed && p->n_nodes > kIdLimit) return fail(OCH_E_INVALID, "packed ids exceed 24 bits");
@@ -542,7 +590,7 @@ int och::pool_write_slots(och_gpu_pool *p, uint32_t first, uint32_t count, const
 int och::pool_scatter_slots(och_gpu_pool *p, const uint32_t *ids, uint32_t count, const uint32_t *raw,
                             const uint32_t *packed)
 {
-    if (!p || p->index_base != 1 || (count && (!ids || !raw))) return fail(OCH_E_INVALID, "bad editor flush");
+    if (!p || p->index_base != 1 || p->world || (count && (!ids || !raw))) return fail(OCH_E_INVALID, "bad editor flush");
     if (packed && (!p->d_packed.d || !p->packed_by_slot))
         return fail(OCH_E_INVALID, "packed buffer is not in editor numbering");
     if (count == 0) return OCH_OK;

@@ -87,6 +87,11 @@ struct och_gpu_pool {
     uint64_t serial = 0;            // process-unique, never reused (och::pool_serial)
     uint64_t last_writer = 0;       // editor id of the last och::pool_commit, 0 otherwise
     bool torn = false;              // a failed editor flush left the slots half written (och::pool_mark_torn)
+    // A world's pool (och::pool_create_for_world): the world's id (0: an ordinary pool), and what
+    // och_world_flush last wrote, ids [0, world_published) of generation world_generation.  Such a
+    // pool has no mirror: och_gpu_pool_update and the editor's writes refuse it.
+    uint64_t world = 0, world_generation = 0;
+    uint32_t world_published = 0;
     int opt_layout = 1;
     int opt_tile_order = 0;
     int opt_bounce_compact = 1;

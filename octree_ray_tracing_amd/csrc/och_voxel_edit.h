@@ -3,6 +3,8 @@
 // (edit_voxels_host) or on the GPU (edit_voxels_gpu, the k_edit_* kernels).
 // Included by och_builder.cpp only, after och_voxel_build.h, whose keys, sort,
 // level counts and row-per-parent level loop it uses over och_dag.h's stores.
+// och_world.h, included after this file, runs the GPU path's steps over a store
+// that stays on the device between calls.
 //
 // The voxel builder's rows start from zeros; an edit's rows start from the old
 // tree.  Host and GPU run the same steps:
@@ -269,6 +271,188 @@ int pool_stats_gpu(GpuScope &G, const DevicePool &dev, uint32_t n, int depth, Bu
 }
 
 // ------------------------------------------------------------ GPU path
+//
+// In the steps och_edit_voxels (edit_voxels_gpu) and a resident world
+// (och_world.h) share: upload + reach + adopt bring a caller's pool into a
+// store, records + levels apply one list of records to a store.
+
+// A caller's pool on the device: its nodes, each depth's distinct nodes
+// (d_order[lv_off[l], + lv_cnt[l]), each id placed once: <= n_nodes in all)
+// and, after edit_adopt, d_map[old id] = store id.
+struct EditReach {
+    uint32_t *d_pool = nullptr, *d_placed = nullptr, *d_map = nullptr, *d_order = nullptr, *d_head = nullptr;
+    uint32_t n_nodes = 0, root = 0;
+    uint32_t lv_off[kMaxVoxelDepth + 1] = {0}, lv_cnt[kMaxVoxelDepth + 1] = {0};
+    uint64_t reach = 0;   // the distinct reachable nodes
+
+    uint32_t widest() const { return *std::max_element(lv_cnt, lv_cnt + kMaxVoxelDepth + 1); }
+};
+
+// The work buffers of the records phase (n_cap records) and of a level loop (rows_cap rows).
+struct EditWork {
+    uint64_t *keys[2] = {nullptr, nullptr};
+    uint32_t *words[2] = {nullptr, nullptr}, *flags = nullptr, *pos = nullptr, *ids = nullptr, *bins = nullptr;
+    void *temp = nullptr;
+    size_t temp_bytes = 0;
+    uint32_t n_cap = 0;
+    uint32_t *rows = nullptr, *rep = nullptr, *slot = nullptr;
+    uint32_t rows_cap = 0;
+};
+
+int edit_upload(GpuScope &G, EditReach &R, const uint32_t *nodes, uint32_t n_nodes, uint32_t root)
+{
+    const hipStream_t st = G.st;
+    R.n_nodes = n_nodes;
+    R.root = root;
+    if (!G.alloc(&R.d_pool, (size_t)n_nodes * 32) || !G.alloc(&R.d_placed, ((size_t)n_nodes + 1) * 4) ||
+        !G.alloc(&R.d_map, ((size_t)n_nodes + 1) * 4) || !G.alloc(&R.d_order, (size_t)n_nodes * 4) || !G.alloc(&R.d_head, 8))
+        return OCH_E_NOMEM;
+    if (n_nodes) GPU_TRY(hipMemcpyAsync(R.d_pool, nodes, (size_t)n_nodes * 32, hipMemcpyHostToDevice, st));
+    GPU_TRY(hipMemsetAsync(R.d_placed, 0, ((size_t)n_nodes + 1) * 4, st));
+    GPU_TRY(hipMemsetAsync(R.d_map, 0, 4, st));   // map[0]: the adopted root of a world without voxels
+    GPU_TRY(hipMemsetAsync(R.d_head, 0, 8, st));
+    return OCH_OK;
+}
+
+int edit_reach(hipStream_t st, EditReach &R, int depth)
+{
+    if (!R.root) return OCH_OK;
+    const uint32_t first_tag = 1;
+    GPU_TRY(hipMemcpyAsync(R.d_order, &R.root, 4, hipMemcpyHostToDevice, st));
+    GPU_TRY(hipMemcpyAsync(R.d_placed + R.root, &first_tag, 4, hipMemcpyHostToDevice, st));
+    R.lv_cnt[0] = 1;
+    for (int l = 0; l + 1 < depth && R.lv_cnt[l]; ++l) {
+        uint32_t head[2] = {0, 0};
+        R.lv_off[l + 1] = R.lv_off[l] + R.lv_cnt[l];
+        hipLaunchKernelGGL(k_edit_reach, blocks((size_t)R.lv_cnt[l] * 8), dim3(256), 0, st, R.d_pool, R.n_nodes,
+                           R.d_order + R.lv_off[l], R.lv_cnt[l], (uint32_t)l + 2u, R.d_placed, R.d_order + R.lv_off[l + 1],
+                           R.d_head);
+        GPU_TRY(hipGetLastError());
+        GPU_TRY(hipMemcpyAsync(head, R.d_head, 8, hipMemcpyDeviceToHost, st));
+        GPU_TRY(hipMemsetAsync(R.d_head, 0, 4, st));
+        GPU_TRY(hipStreamSynchronize(st));
+        if (head[1]) return och::report(OCH_E_INVALID, head[1] & 1u ? kBadChild : kTwoHeights);
+        R.lv_cnt[l + 1] = head[0];
+    }
+    for (int l = 0; l < depth; ++l) R.reach += R.lv_cnt[l];
+    return OCH_OK;
+}
+
+// Adopt, leaf level first: map[old id] = store id; W holds rows for the widest depth.
+int edit_adopt(hipStream_t st, const EditReach &R, const GpuStore &S, const EditWork &W, int depth)
+{
+    for (int l = depth - 1; l >= 0; --l) {
+        const uint32_t cnt = R.lv_cnt[l];
+        if (!cnt) continue;
+        const int h = depth - 1 - l;
+        hipLaunchKernelGGL(k_edit_adopt_rows, blocks((size_t)cnt * 8), dim3(256), 0, st, R.d_pool, R.n_nodes,
+                           R.d_order + R.lv_off[l], cnt, h > 0 ? 1 : 0, R.d_map, W.rows);
+        GpuLevel L{W.rows, 0, 0, cnt, h, 1};
+        hipLaunchKernelGGL(k_intern_rows<true>, blocks(cnt), dim3(256), 0, st, S, L, W.rep, W.slot);
+        hipLaunchKernelGGL(k_settle, blocks(cnt), dim3(256), 0, st, S, cnt, W.rep, W.slot, R.d_map, R.d_order + R.lv_off[l]);
+        GPU_TRY(hipGetLastError());
+    }
+    return OCH_OK;
+}
+
+// What the sort and the scans of n records need as temporary storage.
+int edit_temp_bytes(uint32_t n, int depth, hipStream_t st, size_t *bytes)
+{
+    uint64_t *k = nullptr;
+    uint32_t *w = nullptr;
+    size_t sort_bytes = 0, scan_bytes = 0;
+    GPU_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k, k, w, w, (int)n, 0, std::min(64, 3 * depth + 1), st));
+    GPU_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, w, w, (int)n, st));
+    *bytes = std::max(sort_bytes, scan_bytes);
+    return OCH_OK;
+}
+
+int edit_work_records(GpuScope &G, EditWork &W, uint32_t n, int depth)
+{
+    if (const int ts = edit_temp_bytes(n, depth, G.st, &W.temp_bytes)) return ts;
+    if (!G.alloc(&W.flags, (size_t)n * 4) || !G.alloc(&W.pos, (size_t)n * 4) || !G.alloc(&W.ids, (size_t)n * 4) ||
+        !G.alloc(&W.bins, (size_t)kCounters * kBins * 4) || !G.alloc(&W.keys[0], (size_t)n * 8) ||
+        !G.alloc(&W.keys[1], (size_t)n * 8) || !G.alloc(&W.words[0], (size_t)n * 4) || !G.alloc(&W.words[1], (size_t)n * 4) ||
+        !G.alloc(&W.temp, W.temp_bytes))
+        return OCH_E_NOMEM;
+    W.n_cap = n;
+    return OCH_OK;
+}
+
+int edit_work_rows(GpuScope &G, EditWork &W, uint32_t rows)
+{
+    if (!G.alloc(&W.rows, (size_t)rows * 32) || !G.alloc(&W.rep, (size_t)rows * 4) || !G.alloc(&W.slot, (size_t)rows * 4))
+        return OCH_E_NOMEM;
+    W.rows_cap = rows;
+    return OCH_OK;
+}
+
+// records: the unique in-range keys of recs[n] (device memory, 0 < n <= W.n_cap),
+// zeros kept, packed into W.keys[0] / W.words[0]; m = how many, counts[h] = the
+// rows of level h (all 0 when m is), rows_total their sum.
+int edit_records(hipStream_t st, const EditWork &W, const uint32_t *recs, uint32_t n, int depth, PhaseTimer &phase,
+                 uint32_t &m, uint64_t *counts, uint64_t &rows_total)
+{
+    const size_t bins_bytes = (size_t)kCounters * kBins * 4;
+    const int key_bits = std::min(64, 3 * depth + 1);
+    GPU_TRY(hipMemsetAsync(W.bins, 0, bins_bytes, st));
+    hipLaunchKernelGGL(k_vox_keys, blocks(n), dim3(256), 0, st, recs, n, depth, W.keys[0], W.words[0]);
+    GPU_TRY(hipGetLastError());
+    size_t tb = W.temp_bytes;
+    GPU_TRY(hipcub::DeviceRadixSort::SortPairs(W.temp, tb, W.keys[0], W.keys[1], W.words[0], W.words[1], (int)n, 0, key_bits,
+                                               st));
+    if (!phase("sort")) return OCH_E_HIP;
+    hipLaunchKernelGGL(k_edit_last, blocks(n), dim3(256), 0, st, W.keys[1], W.words[1], recs, n, depth, W.flags, W.ids);
+    GPU_TRY(hipGetLastError());
+    tb = W.temp_bytes;
+    GPU_TRY(hipcub::DeviceScan::InclusiveSum(W.temp, tb, W.flags, W.pos, (int)n, st));
+    GPU_TRY(hipMemcpyAsync(&m, W.pos + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    GPU_TRY(hipStreamSynchronize(st));
+    if (m) {
+        hipLaunchKernelGGL(k_vox_compact, blocks(n), dim3(256), 0, st, W.keys[1], W.flags, W.pos, W.ids, n, W.keys[0],
+                           W.words[0]);
+        hipLaunchKernelGGL(k_vox_levels, blocks(m), dim3(256), 0, st, W.keys[0], m, depth, W.bins);
+        GPU_TRY(hipGetLastError());
+        std::vector<uint32_t> h_bins((size_t)kCounters * kBins);
+        GPU_TRY(hipMemcpyAsync(h_bins.data(), W.bins, bins_bytes, hipMemcpyDeviceToHost, st));
+        GPU_TRY(hipStreamSynchronize(st));
+        uint64_t bins[kBins] = {0};
+        for (int r = 0; r < kCounters; ++r)
+            for (int t = 0; t < kBins; ++t) bins[t] += h_bins[(size_t)r * kBins + t];
+        rows_total = level_counts(bins, depth, counts);
+        if (counts[0] > m || counts[depth - 1] != 1)
+            return och::report(OCH_E_HIP, "GPU voxel editor: inconsistent level counts");
+    }
+    if (!phase("last wins")) return OCH_E_HIP;
+    return OCH_OK;
+}
+
+// levels: the m keys edit_records left in W, level by level over the store S
+// from *d_old_root (device memory); *d_root names the device word that holds
+// the new root (d_old_root itself when m is 0).  W.rows_cap >= counts[0].
+int edit_levels(hipStream_t st, const EditWork &W, const GpuStore &S, const uint32_t *d_old_root, uint32_t m,
+                const uint64_t *counts, int depth, const uint32_t **d_root)
+{
+    int cur = 0;
+    uint32_t n_in = m;
+    for (int h = 0; h < depth && m; ++h) {
+        const uint32_t n_rows = (uint32_t)counts[h];
+        hipLaunchKernelGGL(k_vox_heads, blocks(n_in), dim3(256), 0, st, W.keys[cur], n_in, W.flags);
+        GPU_TRY(hipGetLastError());
+        size_t tb = W.temp_bytes;
+        GPU_TRY(hipcub::DeviceScan::InclusiveSum(W.temp, tb, W.flags, W.pos, (int)n_in, st));
+        hipLaunchKernelGGL(k_edit_rows, blocks(n_in), dim3(256), 0, st, S, d_old_root, W.keys[cur], W.words[cur], n_in, W.flags,
+                           W.pos, n_rows, depth, h, W.rows, W.keys[cur ^ 1]);
+        GpuLevel L{W.rows, 0, 0, n_rows, h, 1};
+        hipLaunchKernelGGL(k_intern_rows<true>, blocks(n_rows), dim3(256), 0, st, S, L, W.rep, W.slot);
+        hipLaunchKernelGGL(k_settle, blocks(n_rows), dim3(256), 0, st, S, n_rows, W.rep, W.slot, W.words[cur ^ 1], nullptr);
+        GPU_TRY(hipGetLastError());
+        cur ^= 1;
+        n_in = n_rows;
+    }
+    *d_root = m ? W.words[cur] : d_old_root;
+    return OCH_OK;
+}
 
 int edit_voxels_gpu(const och_edit_params &P, uint32_t **out, uint32_t *n_out, uint32_t &root, BuildStats &vs)
 {
@@ -276,16 +460,10 @@ int edit_voxels_gpu(const och_edit_params &P, uint32_t **out, uint32_t *n_out, u
     if (const int os = G.open()) return os;
     const hipStream_t st = G.st;
     const int depth = P.depth;
-    const uint32_t n = (uint32_t)P.n, n_nodes = P.n_nodes;
+    const uint32_t n = (uint32_t)P.n;
     PhaseTimer phase{"edit gpu ", 4, st};
-    uint32_t *d_pool, *d_placed, *d_map, *d_order, *d_head;
-    if (!G.alloc(&d_pool, (size_t)n_nodes * 32) || !G.alloc(&d_placed, ((size_t)n_nodes + 1) * 4) ||
-        !G.alloc(&d_map, ((size_t)n_nodes + 1) * 4) || !G.alloc(&d_order, (size_t)n_nodes * 4) || !G.alloc(&d_head, 8))
-        return OCH_E_NOMEM;
-    if (n_nodes) GPU_TRY(hipMemcpyAsync(d_pool, P.nodes, (size_t)n_nodes * 32, hipMemcpyHostToDevice, st));
-    GPU_TRY(hipMemsetAsync(d_placed, 0, ((size_t)n_nodes + 1) * 4, st));
-    GPU_TRY(hipMemsetAsync(d_map, 0, 4, st));   // map[0]: the adopted root of a world without voxels
-    GPU_TRY(hipMemsetAsync(d_head, 0, 8, st));
+    EditReach R;
+    if (const int us = edit_upload(G, R, P.nodes, P.n_nodes, P.root)) return us;
     const void *d_in = P.records;
     if (n && !P.on_device) {
         void *up;
@@ -294,126 +472,28 @@ int edit_voxels_gpu(const och_edit_params &P, uint32_t **out, uint32_t *n_out, u
         d_in = up;
     }
     if (!phase("upload")) return OCH_E_HIP;
-
-    // reach: d_order[lv_off[l], + lv_cnt[l]) = the distinct nodes at depth l (each id is placed once: <= n_nodes in all)
-    uint32_t lv_off[kMaxVoxelDepth + 1] = {0}, lv_cnt[kMaxVoxelDepth + 1] = {0};
-    uint64_t reach = 0;
-    if (P.root) {
-        const uint32_t first_tag = 1;
-        GPU_TRY(hipMemcpyAsync(d_order, &P.root, 4, hipMemcpyHostToDevice, st));
-        GPU_TRY(hipMemcpyAsync(d_placed + P.root, &first_tag, 4, hipMemcpyHostToDevice, st));
-        lv_cnt[0] = 1;
-        for (int l = 0; l + 1 < depth && lv_cnt[l]; ++l) {
-            uint32_t head[2] = {0, 0};
-            lv_off[l + 1] = lv_off[l] + lv_cnt[l];
-            hipLaunchKernelGGL(k_edit_reach, blocks((size_t)lv_cnt[l] * 8), dim3(256), 0, st, d_pool, n_nodes,
-                               d_order + lv_off[l], lv_cnt[l], (uint32_t)l + 2u, d_placed, d_order + lv_off[l + 1], d_head);
-            GPU_TRY(hipGetLastError());
-            GPU_TRY(hipMemcpyAsync(head, d_head, 8, hipMemcpyDeviceToHost, st));
-            GPU_TRY(hipMemsetAsync(d_head, 0, 4, st));
-            GPU_TRY(hipStreamSynchronize(st));
-            if (head[1]) return och::report(OCH_E_INVALID, head[1] & 1u ? kBadChild : kTwoHeights);
-            lv_cnt[l + 1] = head[0];
-        }
-        for (int l = 0; l < depth; ++l) reach += lv_cnt[l];
-    }
+    if (const int rs = edit_reach(st, R, depth)) return rs;
     if (!phase("reach")) return OCH_E_HIP;
 
-    // records: the unique in-range keys, zeros kept, packed into d_keys[0] / d_words[0]
-    uint64_t *d_keys[2] = {nullptr, nullptr};
-    uint32_t *d_words[2] = {nullptr, nullptr}, *d_flags = nullptr, *d_pos = nullptr, *d_ids, *d_bins;
-    void *d_temp = nullptr;
-    size_t temp_bytes = 0;
+    EditWork W;
     uint32_t m = 0;
     uint64_t counts[kMaxVoxelDepth] = {0}, rows_total = 0;
     if (n) {
-        const size_t bins_bytes = (size_t)kCounters * kBins * 4;
-        if (!G.alloc(&d_flags, (size_t)n * 4) || !G.alloc(&d_pos, (size_t)n * 4) || !G.alloc(&d_ids, (size_t)n * 4) ||
-            !G.alloc(&d_bins, bins_bytes) || !G.alloc(&d_keys[0], (size_t)n * 8) || !G.alloc(&d_keys[1], (size_t)n * 8) ||
-            !G.alloc(&d_words[0], (size_t)n * 4) || !G.alloc(&d_words[1], (size_t)n * 4))
-            return OCH_E_NOMEM;
-        const int key_bits = std::min(64, 3 * depth + 1);
-        size_t sort_bytes = 0, scan_bytes = 0;
-        GPU_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_keys[0], d_keys[1], d_words[0], d_words[1], (int)n,
-                                                   0, key_bits, st));
-        GPU_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, d_flags, d_pos, (int)n, st));
-        temp_bytes = std::max(sort_bytes, scan_bytes);
-        if (!G.alloc(&d_temp, temp_bytes)) return OCH_E_NOMEM;
-        GPU_TRY(hipMemsetAsync(d_bins, 0, bins_bytes, st));
-        const uint32_t *recs = static_cast<const uint32_t *>(d_in);
-        hipLaunchKernelGGL(k_vox_keys, blocks(n), dim3(256), 0, st, recs, n, depth, d_keys[0], d_words[0]);
-        GPU_TRY(hipGetLastError());
-        size_t tb = temp_bytes;
-        GPU_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp, tb, d_keys[0], d_keys[1], d_words[0], d_words[1], (int)n, 0,
-                                                   key_bits, st));
-        if (!phase("sort")) return OCH_E_HIP;
-        hipLaunchKernelGGL(k_edit_last, blocks(n), dim3(256), 0, st, d_keys[1], d_words[1], recs, n, depth, d_flags, d_ids);
-        GPU_TRY(hipGetLastError());
-        tb = temp_bytes;
-        GPU_TRY(hipcub::DeviceScan::InclusiveSum(d_temp, tb, d_flags, d_pos, (int)n, st));
-        GPU_TRY(hipMemcpyAsync(&m, d_pos + (n - 1), 4, hipMemcpyDeviceToHost, st));
-        GPU_TRY(hipStreamSynchronize(st));
-        if (m) {
-            hipLaunchKernelGGL(k_vox_compact, blocks(n), dim3(256), 0, st, d_keys[1], d_flags, d_pos, d_ids, n, d_keys[0],
-                               d_words[0]);
-            hipLaunchKernelGGL(k_vox_levels, blocks(m), dim3(256), 0, st, d_keys[0], m, depth, d_bins);
-            GPU_TRY(hipGetLastError());
-            std::vector<uint32_t> h_bins((size_t)kCounters * kBins);
-            GPU_TRY(hipMemcpyAsync(h_bins.data(), d_bins, bins_bytes, hipMemcpyDeviceToHost, st));
-            GPU_TRY(hipStreamSynchronize(st));
-            uint64_t bins[kBins] = {0};
-            for (int r = 0; r < kCounters; ++r)
-                for (int t = 0; t < kBins; ++t) bins[t] += h_bins[(size_t)r * kBins + t];
-            rows_total = level_counts(bins, depth, counts);
-            if (counts[0] > m || counts[depth - 1] != 1)
-                return och::report(OCH_E_HIP, "GPU voxel editor: inconsistent level counts");
-        }
-        if (!phase("last wins")) return OCH_E_HIP;
+        if (const int ws = edit_work_records(G, W, n, depth)) return ws;
+        if (const int es = edit_records(st, W, static_cast<const uint32_t *>(d_in), n, depth, phase, m, counts, rows_total))
+            return es;
     }
-
-    uint32_t rows_max = (uint32_t)counts[0];   // counts only shrink towards the root
-    for (int l = 0; l < depth; ++l) rows_max = std::max(rows_max, lv_cnt[l]);
-    uint32_t *d_rows, *d_rep, *d_slot;
-    if (!G.alloc(&d_rows, (size_t)rows_max * 32) || !G.alloc(&d_rep, (size_t)rows_max * 4) ||
-        !G.alloc(&d_slot, (size_t)rows_max * 4))
-        return OCH_E_NOMEM;
+    // counts only shrink towards the root
+    if (const int ws = edit_work_rows(G, W, std::max((uint32_t)counts[0], R.widest()))) return ws;
     GpuStore S;
-    if (const int cs = gpu_store_create(G, voxel_capacity(P.capacity, reach + rows_total), false, S)) return cs;
-
-    // adopt, leaf level first: map[old id] = store id
-    for (int l = depth - 1; l >= 0; --l) {
-        const uint32_t cnt = lv_cnt[l];
-        if (!cnt) continue;
-        const int h = depth - 1 - l;
-        hipLaunchKernelGGL(k_edit_adopt_rows, blocks((size_t)cnt * 8), dim3(256), 0, st, d_pool, n_nodes, d_order + lv_off[l],
-                           cnt, h > 0 ? 1 : 0, d_map, d_rows);
-        GpuLevel L{d_rows, 0, 0, cnt, h, 1};
-        hipLaunchKernelGGL(k_intern_rows<true>, blocks(cnt), dim3(256), 0, st, S, L, d_rep, d_slot);
-        hipLaunchKernelGGL(k_settle, blocks(cnt), dim3(256), 0, st, S, cnt, d_rep, d_slot, d_map, d_order + lv_off[l]);
-        GPU_TRY(hipGetLastError());
-    }
-    const uint32_t *d_old_root = d_map + P.root;
+    if (const int cs = gpu_store_create(G, voxel_capacity(P.capacity, R.reach + rows_total), false, S)) return cs;
+    if (const int as = edit_adopt(st, R, S, W, depth)) return as;
     if (!phase("adopt")) return OCH_E_HIP;
 
-    int cur = 0;
-    uint32_t n_in = m;
-    for (int h = 0; h < depth && m; ++h) {
-        const uint32_t n_rows = (uint32_t)counts[h];
-        hipLaunchKernelGGL(k_vox_heads, blocks(n_in), dim3(256), 0, st, d_keys[cur], n_in, d_flags);
-        GPU_TRY(hipGetLastError());
-        size_t tb = temp_bytes;
-        GPU_TRY(hipcub::DeviceScan::InclusiveSum(d_temp, tb, d_flags, d_pos, (int)n_in, st));
-        hipLaunchKernelGGL(k_edit_rows, blocks(n_in), dim3(256), 0, st, S, d_old_root, d_keys[cur], d_words[cur], n_in, d_flags,
-                           d_pos, n_rows, depth, h, d_rows, d_keys[cur ^ 1]);
-        GpuLevel L{d_rows, 0, 0, n_rows, h, 1};
-        hipLaunchKernelGGL(k_intern_rows<true>, blocks(n_rows), dim3(256), 0, st, S, L, d_rep, d_slot);
-        hipLaunchKernelGGL(k_settle, blocks(n_rows), dim3(256), 0, st, S, n_rows, d_rep, d_slot, d_words[cur ^ 1], nullptr);
-        GPU_TRY(hipGetLastError());
-        cur ^= 1;
-        n_in = n_rows;
-    }
+    const uint32_t *d_root = nullptr;
+    if (const int ls = edit_levels(st, W, S, R.d_map + P.root, m, counts, depth, &d_root)) return ls;
     uint32_t used = 0;
-    GPU_TRY(hipMemcpyAsync(&root, m ? d_words[cur] : d_old_root, 4, hipMemcpyDeviceToHost, st));
+    GPU_TRY(hipMemcpyAsync(&root, d_root, 4, hipMemcpyDeviceToHost, st));
     const int us = gpu_store_used(S, st, &used);
     if (!phase("levels")) return OCH_E_HIP;
     if (us != OCH_OK) return us;
@@ -429,7 +509,7 @@ int edit_voxels_gpu(const och_edit_params &P, uint32_t **out, uint32_t *n_out, u
     if (!phase("statistics")) return OCH_E_HIP;
     if (phase.on)
         std::fprintf(stderr, "[och_build] edit gpu: %llu old nodes, %u records, %u keys, %u ids of %u\n",
-                     (unsigned long long)reach, n, m, used - 1, S.cap - 1);
+                     (unsigned long long)R.reach, n, m, used - 1, S.cap - 1);
     return OCH_OK;
 }
 

@@ -1,0 +1,506 @@
+// och_world.h -- the resident world (och_world_*): a DAG that stays on one GPU
+// between brush strokes.  Included by och_builder.cpp only, after
+// och_voxel_edit.h, whose steps it runs over a store that outlives the call:
+//   create   -- upload, reach and adopt (edit_upload, edit_reach, edit_adopt),
+//               once; the store, its table and the root stay on the device.
+//   edit     -- records and levels (edit_records, edit_levels) against that
+//               store, then the root is replaced.  Nothing of the pool is
+//               uploaded, reached, adopted, renumbered, counted or downloaded.
+//   flush    -- the ids handed out since a pool's last flush, copied (raw
+//               layout) and packed (k_world_pack) on the device, then the
+//               roots and the box through och::pool_commit.
+//   download -- renumber_gpu + pool_stats_gpu from the current root.
+//   compact  -- renumber_gpu, then the renumbered pool adopted into a fresh
+//               store (its levels are contiguous id ranges: no reach).
+//
+// Append-only.  alloc_node writes only ids nobody has seen yet and k_settle
+// only finishes table slots claimed in the same level, so a stroke changes no
+// row that any earlier root reaches: a frame in flight that walks a pool from
+// an earlier root reads only ids below that flush's `used`, a later flush
+// writes only ids at or above it, and no device-wide wait is needed before
+// publishing.  Store and pool meet only across dispatch boundaries (the flush
+// ends in a synchronise of the world's stream; a launch takes its root by
+// value, after that), which is all the per-XCD L2s ask for (k_intern's rule,
+// och_dag.h).
+//
+// Capacity is checked before anything is interned: a stroke that ran out of
+// ids half way would leave table slots that went back to 0 behind probes that
+// already passed them; a later equal row would be interned twice and the
+// downloaded pool would no longer be canonical.  The bound, used + the level
+// counts of the stroke's unique keys, allows one id per row of the records'
+// own tree: a row allocates at most one id (its claimant's), so no intern of
+// an admitted stroke can fail, and the answer depends on the records alone.
+//
+// Out of scope: worlds replicated across GPUs, frame groups and the sharded
+// paths; 0-based pools; undo or checkout of older roots (the store would allow
+// it); a single-voxel `at` on the device; a tight box after removals; depth 22.
+#pragma once
+#include <memory>
+
+#include "och_host.h"
+#include "och_voxel_edit.h"
+
+namespace {
+
+// Words of a store's head (GpuStore.next; [0] the id counter, [1] overflow,
+// the tree-node counters from word 64) that a world uses: the current root
+// and its child mask, and the stroke's box (min x y z, max x y z, inclusive).
+constexpr int kHeadRoot = 8, kHeadBox = 16, kHeadWords = 22;
+
+// The stroke's result into the head, for one read-back with the id counter.
+__global__ __launch_bounds__(64) void k_world_root(GpuStore S, const uint32_t *__restrict__ new_root, uint32_t *__restrict__ head)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    const uint32_t r = *new_root;
+    uint32_t mask = 0;
+    if (r && r < S.cap)
+        for (uint32_t k = 0; k < 8; ++k) mask |= (uint32_t)(S.nodes[(size_t)r * 8 + k] != 0) << k;
+    head[kHeadRoot] = r;
+    head[kHeadRoot + 1] = mask;
+}
+
+// The box of the stroke's voxels, from its m unique keys and their ids (id 0
+// is a removal: no voxel): a wavefront's minima and maxima in registers, then
+// six atomics per wavefront that holds a voxel.  box: 0xFFFFFFFF x 3, 0 x 3 before.
+__global__ __launch_bounds__(256) void k_world_box(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ words,
+                                                   uint32_t m, uint32_t *__restrict__ box)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0, 0, 0};
+    if (i < m && words[i]) {
+        const uint64_t key = keys[i];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) lo[a] = hi[a] = compact3(key >> a);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int o = 32; o; o >>= 1) {
+            lo[a] = min(lo[a], (uint32_t)__shfl_xor(lo[a], o));
+            hi[a] = max(hi[a], (uint32_t)__shfl_xor(hi[a], o));
+        }
+    if ((threadIdx.x & 63u) == 0 && lo[0] != 0xFFFFFFFFu) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            atomicMin(box + a, lo[a]);
+            atomicMax(box + 3 + a, hi[a]);
+        }
+    }
+}
+
+// The packed layout numbered like the store, ids [lo, hi): thread q is child
+// word q & 7 of id lo + q / 8.  An interior word becomes child | mask(child) << 24
+// (the child's row is an earlier dispatch's), a leaf-level word stays as it is.
+__global__ __launch_bounds__(256) void k_world_pack(GpuStore S, uint32_t lo, uint32_t hi, uint32_t *__restrict__ packed)
+{
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (size_t)(hi - lo) * 8) return;
+    const uint32_t id = lo + (uint32_t)(q >> 3);
+    const size_t at = (size_t)id * 8 + (q & 7u);
+    uint32_t w = S.nodes[at];
+    if (w && w < S.cap && S.level[id] != 0) {
+        const uint4 *rec = reinterpret_cast<const uint4 *>(S.nodes + (size_t)w * 8);
+        const uint4 a = rec[0], b = rec[1];
+        const uint32_t mask = (uint32_t)(a.x != 0) | (uint32_t)(a.y != 0) << 1 | (uint32_t)(a.z != 0) << 2 |
+                              (uint32_t)(a.w != 0) << 3 | (uint32_t)(b.x != 0) << 4 | (uint32_t)(b.y != 0) << 5 |
+                              (uint32_t)(b.z != 0) << 6 | (uint32_t)(b.w != 0) << 7;
+        w |= mask << 24;
+    }
+    packed[at] = w;
+}
+
+// list[i] = first + i
+__global__ __launch_bounds__(256) void k_world_iota(uint32_t *__restrict__ list, uint32_t n, uint32_t first)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) list[i] = first + i;
+}
+
+constexpr uint32_t kWorldIdLimit = 1u << 24;           // packed ids are 24 bits
+constexpr uint32_t kWorldCapLimit = (1u << 29) - 1;    // a pool's n_nodes + 1 stays below 2^29 (och_gpu_pool_create)
+
+}  // namespace
+
+struct och_world {
+    int device = 0, depth = 0;
+    uint64_t id = 0;                  // process-unique, never reused: the mark on this world's pools
+    bool broken = false;
+    hipStream_t st = nullptr;
+    std::unique_ptr<GpuScope> store_scope, work_scope;   // both on st, which the world owns
+    GpuStore S{};
+    EditWork W;                       // for W.n_cap records and as many rows, grown on demand and kept
+    void *d_upload = nullptr;         // W.n_cap host records' way to the device
+    uint32_t used = 1, root = 0, root_mask = 0;
+    uint64_t strokes = 0, generation = 0;
+    bool box_any = false;
+    int32_t box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
+
+    uint32_t *head() const { return S.next; }
+    ~och_world()
+    {
+        work_scope.reset();           // each synchronises st before it frees
+        store_scope.reset();
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+
+namespace {
+
+// The head's words after the stroke's (or the adoption's) last dispatch: used,
+// root and mask into the world; synchronises st.
+int world_read_head(och_world &w, const GpuStore &S, uint32_t *used, uint32_t *root, uint32_t *mask, uint32_t *box)
+{
+    uint32_t h[kHeadWords] = {0};
+    GPU_TRY(hipMemcpyAsync(h, S.next, sizeof h, hipMemcpyDeviceToHost, w.st));
+    GPU_TRY(hipStreamSynchronize(w.st));
+    if (h[1] & 4u) return och::report(OCH_E_HIP, "och_world: a row outside its level");
+    if (h[1]) return och::report(OCH_E_HIP, "och_world: the store overflowed after its capacity check");
+    *used = std::min(h[0], S.cap);
+    *root = h[kHeadRoot];
+    *mask = h[kHeadRoot + 1];
+    if (box) std::memcpy(box, h + kHeadBox, 24);
+    return OCH_OK;
+}
+
+// Work buffers for n records: kept while they suffice, else replaced by larger ones.
+int world_reserve(och_world &w, uint32_t n)
+{
+    size_t need = 0;
+    if (const int ts = edit_temp_bytes(n, w.depth, w.st, &need)) return ts;
+    if (n <= w.W.n_cap && need <= w.W.temp_bytes) return OCH_OK;
+    uint32_t cap = 4096;
+    while (cap < n) cap <<= 1;
+    w.work_scope.reset();
+    w.W = EditWork{};
+    w.d_upload = nullptr;
+    w.work_scope.reset(new GpuScope(w.st));
+    GpuScope &G = *w.work_scope;
+    int st = edit_work_records(G, w.W, cap, w.depth);
+    if (st == OCH_OK) st = edit_work_rows(G, w.W, cap);   // a level's rows never outnumber the keys
+    if (st == OCH_OK && !G.alloc(&w.d_upload, (size_t)cap * 16)) st = OCH_E_NOMEM;
+    if (st == OCH_OK && w.W.temp_bytes < need) st = OCH_E_NOMEM;
+    if (st != OCH_OK) {
+        w.work_scope.reset();
+        w.W = EditWork{};
+        w.d_upload = nullptr;
+    }
+    return st;
+}
+
+int world_edit(och_world &w, const void *records, uint32_t n, bool on_device)
+{
+    const hipStream_t st = w.st;
+    PhaseTimer phase{"world ", 4, st};
+    if (const int rs = world_reserve(w, n)) return rs;
+    const void *d_in = records;
+    if (!on_device) {
+        GPU_TRY(hipMemcpyAsync(w.d_upload, records, (size_t)n * 16, hipMemcpyHostToDevice, st));
+        d_in = w.d_upload;
+    }
+    if (!phase("upload")) return OCH_E_HIP;
+    uint32_t m = 0;
+    uint64_t counts[kMaxVoxelDepth] = {0}, rows_total = 0;
+    if (const int es = edit_records(st, w.W, static_cast<const uint32_t *>(d_in), n, w.depth, phase, m, counts, rows_total))
+        return es;
+    if (!m) {   // every record outside the tree
+        ++w.strokes;
+        return OCH_OK;
+    }
+    // before anything is interned: see the head of this file
+    if ((uint64_t)w.used + rows_total > w.S.cap) return OCH_E_CAPACITY;
+    static const uint32_t no_box[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0};
+    uint32_t *head = w.head();
+    GPU_TRY(hipMemcpyAsync(head + kHeadBox, no_box, sizeof no_box, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_world_box, blocks(m), dim3(256), 0, st, w.W.keys[0], w.W.words[0], m, head + kHeadBox);
+    GPU_TRY(hipGetLastError());
+    const uint32_t *d_new = nullptr;
+    if (const int ls = edit_levels(st, w.W, w.S, head + kHeadRoot, m, counts, w.depth, &d_new)) return ls;
+    hipLaunchKernelGGL(k_world_root, dim3(1), dim3(64), 0, st, w.S, d_new, head);
+    GPU_TRY(hipGetLastError());
+    uint32_t used = 0, root = 0, mask = 0, box[6];
+    if (const int hs = world_read_head(w, w.S, &used, &root, &mask, box)) return hs;
+    if (!phase("levels")) return OCH_E_HIP;
+    if (phase.on)
+        std::fprintf(stderr, "[och_build] world: %u records, %u keys, %u new ids, %u of %u used\n", n, m, used - w.used, used,
+                     w.S.cap);
+    w.used = used;
+    w.root = root;
+    w.root_mask = mask;
+    if (box[0] != 0xFFFFFFFFu)
+        for (int a = 0; a < 3; ++a) {
+            w.box_lo[a] = w.box_any ? std::min(w.box_lo[a], (int32_t)box[a]) : (int32_t)box[a];
+            w.box_hi[a] = w.box_any ? std::max(w.box_hi[a], (int32_t)box[3 + a] + 1) : (int32_t)box[3 + a] + 1;
+        }
+    w.box_any = w.box_any || box[0] != 0xFFFFFFFFu;
+    ++w.strokes;
+    return OCH_OK;
+}
+
+// A fresh store of `cap` ids holding the 1-based pool R names (reached, on the
+// device), in a scope of its own on the world's stream; T takes the adoption's
+// rows.  used / root / mask: the store's after the adoption.
+int world_adopt(och_world &w, GpuScope &T, const EditReach &R, uint32_t cap, std::unique_ptr<GpuScope> &scope, GpuStore &S,
+                uint32_t *used, uint32_t *root, uint32_t *mask)
+{
+    scope.reset(new GpuScope(w.st));
+    if (const int cs = gpu_store_create(*scope, cap, false, S)) return cs;
+    EditWork TW;
+    if (const int ws = edit_work_rows(T, TW, R.widest())) return ws;
+    if (const int as = edit_adopt(w.st, R, S, TW, w.depth)) return as;
+    hipLaunchKernelGGL(k_world_root, dim3(1), dim3(64), 0, w.st, S, R.d_map + R.root, S.next);
+    GPU_TRY(hipGetLastError());
+    return world_read_head(w, S, used, root, mask, nullptr);
+}
+
+int world_create(och_world &w, const uint32_t *nodes, uint32_t n_nodes, uint32_t root, uint32_t capacity)
+{
+    GPU_TRY(hipStreamCreateWithFlags(&w.st, hipStreamNonBlocking));
+    PhaseTimer phase{"world ", 4, w.st};
+    GpuScope T(w.st);
+    EditReach R;
+    if (const int us = edit_upload(T, R, nodes, n_nodes, root)) return us;
+    if (const int rs = edit_reach(w.st, R, w.depth)) return rs;
+    if (!phase("reach")) return OCH_E_HIP;
+    const uint64_t cap = capacity ? capacity : 2 * R.reach + 64ull * (uint64_t)w.depth;
+    if (cap < R.reach + 1) return OCH_E_CAPACITY;
+    if (cap >= kWorldCapLimit) return och::report(OCH_E_INVALID, "och_world_create: a capacity of 2^29 - 1 ids or more");
+    if (const int as = world_adopt(w, T, R, (uint32_t)cap, w.store_scope, w.S, &w.used, &w.root, &w.root_mask)) return as;
+    if (!phase("adopt")) return OCH_E_HIP;
+    w.box_any = och::occupied_box(nodes, n_nodes, root, w.depth, 1, w.box_lo, w.box_hi);
+    phase("box");
+    return OCH_OK;
+}
+
+int world_compact(och_world &w)
+{
+    PhaseTimer phase{"world ", 4, w.st};
+    GpuScope T(w.st);
+    EditReach R;
+    if (w.root) {
+        DevicePool dev;
+        uint32_t n = 0;
+        if (const int rs = renumber_gpu(w.S, w.used, w.root, w.depth, T, nullptr, &n, false, &dev)) return rs;
+        // the renumbered pool's depths are id ranges: lv_cnt as the reach would give them, the ids as a list
+        R.d_pool = const_cast<uint32_t *>(dev.nodes);
+        R.n_nodes = n;
+        R.root = 1;
+        if (!T.alloc(&R.d_map, ((size_t)n + 1) * 4) || !T.alloc(&R.d_order, (size_t)n * 4)) return OCH_E_NOMEM;
+        GPU_TRY(hipMemsetAsync(R.d_map, 0, 4, w.st));
+        hipLaunchKernelGGL(k_world_iota, blocks(n), dim3(256), 0, w.st, R.d_order, n, 1u);
+        GPU_TRY(hipGetLastError());
+        uint32_t off = 0;
+        for (size_t l = 0; l < dev.level_counts.size() && l < (size_t)w.depth && off < n; ++l) {
+            R.lv_off[l] = off;
+            R.lv_cnt[l] = std::min(dev.level_counts[l], n - off);
+            off += R.lv_cnt[l];
+        }
+        R.reach = n;
+        if (!phase("renumber")) return OCH_E_HIP;
+    } else {
+        if (!T.alloc(&R.d_map, 4)) return OCH_E_NOMEM;
+        GPU_TRY(hipMemsetAsync(R.d_map, 0, 4, w.st));
+    }
+    std::unique_ptr<GpuScope> scope;
+    GpuStore S;
+    uint32_t used = 0, root = 0, mask = 0;
+    if (const int as = world_adopt(w, T, R, w.S.cap, scope, S, &used, &root, &mask)) return as;
+    if (!phase("adopt")) return OCH_E_HIP;
+    if (phase.on) std::fprintf(stderr, "[och_build] world: compacted %u ids to %u\n", w.used, used);
+    w.store_scope.swap(scope);   // the old store goes with `scope`, after a synchronise of the stream
+    w.S = S;
+    w.used = used;
+    w.root = root;
+    w.root_mask = mask;
+    ++w.generation;
+    return OCH_OK;
+}
+
+int world_flush(och_world &w, och_gpu_pool *pool)
+{
+    och::WorldPoolView v;
+    if (const int vs = och::pool_world_view(pool, w.id, &v)) return vs;
+    if (v.n_nodes != w.S.cap) return och::report(OCH_E_INVALID, "och_world_flush: the pool was not made from this world");
+    const bool whole = *v.generation != w.generation;
+    // ids of another generation: launches in flight may walk the slots about to change
+    if (whole && *v.published)
+        if (const int ds = och::pool_drain(pool)) return ds;
+    const uint32_t lo = whole ? 0u : *v.published, hi = w.used;
+    PhaseTimer phase{"world ", 4, w.st};
+    int st = OCH_OK;
+    if (hi > lo) {
+        if (hipMemcpyAsync(v.raw + (size_t)lo * 8, w.S.nodes + (size_t)lo * 8, (size_t)(hi - lo) * 32, hipMemcpyDeviceToDevice,
+                           w.st) != hipSuccess)
+            st = OCH_E_HIP;
+        if (st == OCH_OK && v.packed) {
+            hipLaunchKernelGGL(k_world_pack, blocks((size_t)(hi - lo) * 8), dim3(256), 0, w.st, w.S, lo, hi, v.packed);
+            if (hipGetLastError() != hipSuccess) st = OCH_E_HIP;
+        }
+    }
+    // complete on return: the launch that takes the new root starts after its nodes are there
+    if (st == OCH_OK && hipStreamSynchronize(w.st) != hipSuccess) st = OCH_E_HIP;
+    if (st == OCH_OK)
+        st = och::pool_commit(pool, w.root, w.root ? w.root | w.root_mask << 24 : 0u, v.packed != nullptr, 0,
+                              w.box_any ? w.box_lo : nullptr, w.box_any ? w.box_hi : nullptr);
+    if (st != OCH_OK) {
+        // below `published` nothing was written, so the pool still shows its last flush -- unless it was being rewritten
+        if (whole && *v.published) (void)och::pool_mark_torn(pool);
+        return st;
+    }
+    *v.published = hi;
+    *v.generation = w.generation;
+    phase("flush");
+    return OCH_OK;
+}
+
+int world_usable(const och_world *w, const char *who)
+{
+    if (!w) return och::report(OCH_E_INVALID, (std::string(who) + ": world is NULL").c_str());
+    if (w->broken)
+        return och::report(OCH_E_INVALID, (std::string(who) + ": the world is broken (an earlier call failed in HIP)").c_str());
+    return OCH_OK;
+}
+
+// A world call's status: reported, and a HIP failure breaks the world.
+int world_status(och_world *w, int st)
+{
+    if (st == OCH_E_HIP) w->broken = true;
+    if (st == OCH_OK || st == OCH_E_INVALID) return st;   // INVALID is reported where it is found
+    return report_build(st, "och_world", "allocation failed");
+}
+
+}  // namespace
+
+OCH_API int och_world_create(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, uint32_t capacity, int device,
+                             och_world **out)
+{
+    if (!out) return och::report(OCH_E_INVALID, "och_world_create: out is NULL");
+    *out = nullptr;
+    if (depth < 1 || depth > kMaxVoxelDepth)
+        return och::report(OCH_E_INVALID, "och_world_create: depth must be 1..21 (a Morton key of 3 * depth bits and the "
+                                          "out-of-range bit fill 64 bits)");
+    if (!nodes && n_nodes) return och::report(OCH_E_INVALID, "och_world_create: nodes is null");
+    if (root > n_nodes) return och::report(OCH_E_INVALID, "och_world_create: root lies past the pool's end");
+    int ndev = 0;
+    if (!gpu_present() || hipGetDeviceCount(&ndev) != hipSuccess) return report_build(OCH_E_NODEV, "och_world", "");
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return report_build(OCH_E_HIP, "och_world", "");
+    if (device >= ndev) return report_build(OCH_E_NODEV, "och_world", "");
+    och::DeviceGuard g(device);
+    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
+    static std::atomic<uint64_t> next_id{1};
+    och_world *w = new och_world;
+    w->id = next_id.fetch_add(1);
+    w->device = device;
+    w->depth = depth;
+    const int st = world_create(*w, nodes, n_nodes, root, capacity);
+    if (st != OCH_OK) {
+        delete w;
+        return st == OCH_E_INVALID ? st : report_build(st, "och_world", "allocation failed");
+    }
+    *out = w;
+    return OCH_OK;
+}
+
+OCH_API int och_world_destroy(och_world *w)
+{
+    if (!w) return OCH_OK;
+    och::DeviceGuard g(w->device);
+    delete w;
+    return OCH_OK;
+}
+
+OCH_API int och_world_info(const och_world *w, och_world_stats *info)
+{
+    if (!info) return och::report(OCH_E_INVALID, "och_world_info: info is NULL");
+    if (const int us = world_usable(w, "och_world_info")) return us;
+    info->capacity = w->S.cap;
+    info->used = w->used;
+    info->root = w->root;
+    info->depth = w->depth;
+    info->device = w->device;
+    info->strokes = w->strokes;
+    info->generation = w->generation;
+    for (int a = 0; a < 3; ++a) {
+        info->box_lo[a] = w->box_any ? w->box_lo[a] : 0;
+        info->box_hi[a] = w->box_any ? w->box_hi[a] : 0;
+    }
+    return OCH_OK;
+}
+
+OCH_API int och_world_edit(och_world *w, const void *records, uint64_t n, int on_device)
+{
+    if (n >= (1ull << 31)) return och::report(OCH_E_INVALID, "och_world_edit: a list holds fewer than 2^31 records");
+    if (!records && n) return och::report(OCH_E_INVALID, "och_world_edit: records is null");
+    if (const int us = world_usable(w, "och_world_edit")) return us;
+    if (!n) return OCH_OK;
+    och::DeviceGuard g(w->device);
+    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
+    return world_status(w, world_edit(*w, records, (uint32_t)n, on_device != 0));
+}
+
+OCH_API int och_world_pool_create(och_world *w, och_gpu_pool **out)
+{
+    if (!out) return och::report(OCH_E_INVALID, "och_world_pool_create: out is NULL");
+    *out = nullptr;
+    if (const int us = world_usable(w, "och_world_pool_create")) return us;
+    och::DeviceGuard g(w->device);
+    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
+    och_gpu_pool *pool = nullptr;
+    if (const int cs = och::pool_create_for_world(w->device, w->depth, w->S.cap, w->id, &pool)) return cs;
+    och::WorldPoolView v;
+    int st = och::pool_world_view(pool, w->id, &v);
+    if (st == OCH_OK) {
+        *v.generation = w->generation;   // nothing published: the first flush writes ids [0, used)
+        st = world_flush(*w, pool);
+    }
+    if (st != OCH_OK) {
+        (void)och_gpu_pool_destroy(pool);
+        return st == OCH_E_HIP ? report_build(st, "och_world", "") : st;
+    }
+    *out = pool;
+    return OCH_OK;
+}
+
+OCH_API int och_world_flush(och_world *w, och_gpu_pool *pool)
+{
+    if (const int us = world_usable(w, "och_world_flush")) return us;
+    if (!pool) return och::report(OCH_E_INVALID, "och_world_flush: pool is NULL");
+    och::DeviceGuard g(w->device);
+    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
+    const int st = world_flush(*w, pool);
+    return st == OCH_E_HIP ? report_build(st, "och_world", "") : st;
+}
+
+OCH_API int och_world_download(och_world *w, och_host_pool *out)
+{
+    if (!out) return och::report(OCH_E_INVALID, "och_world_download: out is NULL");
+    if (const int us = world_usable(w, "och_world_download")) return us;
+    och::DeviceGuard g(w->device);
+    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
+    const auto t_start = std::chrono::steady_clock::now();
+    PhaseTimer phase{"world ", 4, w->st};
+    BuildStats vs;
+    uint32_t root = w->root, n_out = 0;
+    uint32_t *nodes = nullptr;
+    int st = OCH_OK;
+    if (!root) {
+        st = empty_pool(&nodes, &n_out, root);
+    } else {
+        GpuScope T(w->st);
+        DevicePool dev;
+        st = renumber_gpu(w->S, w->used, root, w->depth, T, &nodes, &n_out, phase.on, &dev);
+        if (st == OCH_OK && (st = pool_stats_gpu(T, dev, n_out, w->depth, vs)) != OCH_OK) std::free(nodes);
+    }
+    if (st != OCH_OK) return report_build(st, "och_world", "allocation failed");   // reads only: the world stays usable
+    phase("download");
+    return finish_pool(out, nodes, n_out, root, 1, w->depth, vs, t_start);
+}
+
+OCH_API int och_world_compact(och_world *w)
+{
+    if (const int us = world_usable(w, "och_world_compact")) return us;
+    och::DeviceGuard g(w->device);
+    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
+    // the old store is replaced only once the new one is whole: a failure leaves the world as it was
+    const int st = world_compact(*w);
+    return st == OCH_OK || st == OCH_E_INVALID ? st : report_build(st, "och_world", "allocation failed");
+}

@@ -133,6 +133,15 @@ class GpuPool:
              int(index_base), float(miss_t), int(device), C.byref(self._h))
         self._palette_n = 0
 
+    @classmethod
+    def _adopt(cls, handle, depth: int, index_base: int = 1, miss_t: float = math.inf):
+        """The Python side of a pool the library made itself (World.make_pool); it owns the handle."""
+        pool = cls.__new__(cls)
+        pool.depth, pool.index_base, pool.miss_t = int(depth), int(index_base), float(miss_t)
+        pool._h = handle
+        pool._palette_n = 0
+        return pool
+
     # -- lifetime
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

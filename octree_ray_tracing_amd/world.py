@@ -1,0 +1,128 @@
+"""A world that stays on the GPU between brush strokes (och_world_* in include/och_gpu.h).
+
+The demo's brush keys (ORT/test_och_h_octree.cpp:397-433) call ``tree.set`` 64 000 times and redraw;
+here a stroke is ``world.edit(box_records(...))`` followed by ``world.flush(pool)`` before the next
+frame.  Only the stroke's new nodes are made and published: the store is append-only, so frames in
+flight stay valid and nothing of the pool travels to the host and back.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import HostPool, OchError, call
+from .builder import NodePool, _capacity, _host_records
+from .tracer import HOctree
+
+
+class World:
+    """A 1-based DAG resident on one GPU: edit() applies a record list as edit_voxels would, make_pool()
+    and flush() show it, download() gives the canonical pool, compact() drops what strokes left behind."""
+
+    def __init__(self, tree, capacity: int | None = None, device: int = -1):
+        """tree is a NodePool with index_base 1 or a (nodes, root, depth) tuple in that form, as edit_voxels
+        takes it (no nodes or root 0: an empty world to paint into).  capacity = node ids to reserve for the
+        world's life, id 0 included; None = twice the reachable nodes + 64 * depth."""
+        self._h = C.c_void_p()
+        if isinstance(tree, NodePool):
+            if tree.index_base != 1:
+                raise OchError(-1, "och_world_create", "a pool with index_base 1 (h_octree form), not an och::octree pool")
+            tree = (tree.nodes, tree.root, tree.depth)
+        nodes, root, depth = tree
+        nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 8)
+        if not 0 <= int(root) <= 0xFFFFFFFF:
+            raise ValueError(f"World: root {root} outside uint32")
+        self.depth = int(depth)
+        call("och_world_create", nodes.ctypes.data if nodes.size else None, nodes.shape[0], int(root), self.depth,
+             _capacity(capacity or 0, "World"), int(device), C.byref(self._h))
+        self.device = self.info()["device"]
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            call("och_world_destroy", self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def closed(self) -> bool:
+        return not (getattr(self, "_h", None) and self._h.value)
+
+    def _open(self, who: str):
+        if self.closed:
+            raise ValueError(f"World.{who}: the world is closed")
+        return self._h
+
+    def info(self) -> dict:
+        """och_world_stats: capacity, used, root, depth, device, strokes, generation, box_lo, box_hi."""
+        st = _lib.WorldStats()
+        call("och_world_info", self._open("info"), C.byref(st))
+        out = {f: getattr(st, f) for f, _ in _lib.WorldStats._fields_}
+        out["box_lo"], out["box_hi"] = tuple(st.box_lo), tuple(st.box_hi)
+        return out
+
+    def edit(self, records) -> None:
+        """One stroke: an (n, 4) record list as edit_voxels takes it, a numpy array or a CUDA tensor
+        (int32 / uint32) on the world's device.  OchError CAPACITY leaves the world unchanged:
+        compact() and retry."""
+        if hasattr(records, "is_cuda") and not records.is_cuda:
+            records = records.numpy()
+        if hasattr(records, "is_cuda"):
+            h = self._open("edit")
+            import torch
+
+            if records.dim() != 2 or records.shape[1] != 4 or records.dtype not in (torch.int32, torch.uint32):
+                raise ValueError(f"World.edit: a device list is an (n, 4) int32 / uint32 tensor, not "
+                                 f"{tuple(records.shape)} {records.dtype}")
+            if records.device.index != self.device:
+                raise ValueError(f"World.edit: the tensor is on {records.device}, the world on device {self.device}")
+            records = records.contiguous()
+            torch.cuda.current_stream(records.device).synchronize()      # the stroke reads on the world's stream
+            call("och_world_edit", h, records.data_ptr(), records.shape[0], 1)
+            return
+        records = np.asarray(records)
+        if records.ndim != 2 or records.shape[1] != 4:
+            raise ValueError(f"World.edit: an (n, 4) record list, not shape {records.shape}")
+        records = _host_records(records, "World.edit")
+        call("och_world_edit", self._open("edit"), records.ctypes.data, records.shape[0], 0)
+
+    def make_pool(self) -> HOctree:
+        """A device pool of the current world on the world's device (och_world_pool_create); the caller
+        closes it.  It has no host mirror: update() and Editor.flush() on it raise OchError INVALID."""
+        h = C.c_void_p()
+        call("och_world_pool_create", self._open("make_pool"), C.byref(h))
+        return HOctree._adopt(h, self.depth)
+
+    def flush(self, pool) -> None:
+        """Publish the strokes since this pool's last flush; complete on return."""
+        call("och_world_flush", self._open("flush"), pool._h)
+
+    def download(self) -> NodePool:
+        """The canonical pool of the world's voxels with its statistics, as build_voxels / edit_voxels
+        return it for the same content.  The world is unchanged."""
+        hp = HostPool()
+        call("och_world_download", self._open("download"), C.byref(hp))
+        try:
+            n = hp.n_nodes
+            arr = np.ctypeslib.as_array(hp.nodes, shape=(n * 8,)).reshape(n, 8).copy()
+        finally:
+            call("och_host_pool_free", C.byref(hp))
+        return NodePool(arr, hp.root, hp.depth, hp.index_base, hp.solid_voxels, list(hp.voxel_hist), hp.tree_nodes,
+                        hp.build_seconds)
+
+    def compact(self) -> None:
+        """Drop what the root no longer reaches (och_world_compact): generation + 1, every pool is
+        rewritten whole by its next flush."""
+        call("och_world_compact", self._open("compact"))
