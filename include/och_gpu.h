@@ -759,6 +759,24 @@ OCH_API int och_pool_occupied_box(const uint32_t *nodes, uint32_t n_nodes, uint3
 /* h_octree::at over any pool (ORT/och_h_octree.h:239-258). */
 OCH_API uint32_t och_pool_at(const uint32_t *nodes, uint32_t root, int depth, int index_base,
                              int x, int y, int z);
+/* A box of voxels as a dense grid, on the host, from any pool: the cell of
+ * (x, y, z), lo <= (x, y, z) < hi per axis, is grid[((z - lo[2]) * ny +
+ * (y - lo[1])) * nx + (x - lo[0])] with (nx, ny, nz) = hi - lo -- x fastest,
+ * then y, then z, the layout och_build_voxels takes, so a whole tree read and
+ * fed back as a grid rebuilds the same pool.  kind is OCH_VOXELS_GRID_U8 or
+ * OCH_VOXELS_GRID_U32.  A cell inside [0, dim) holds och_pool_at of its
+ * coordinate, a cell outside holds 0: the box may reach past the tree on any
+ * side and lo may be negative (extents and the volume are 64-bit).  A box with
+ * hi == lo on some axis writes nothing and returns OCH_OK.
+ * Refused before anything is written -- OCH_E_INVALID: a NULL pointer, another
+ * kind, index_base outside 0 and 1, a pool och_pool_occupied_box refuses,
+ * hi[a] < lo[a], a volume times the cell size above capacity_bytes.
+ * With OCH_VOXELS_GRID_U8 an id above 255 inside the box gives OCH_E_INVALID,
+ * the text naming the id, and the grid's contents are then unspecified (this
+ * cannot be known before reading); no value is ever truncated.
+ * och_world_read_box, below, gives the same bytes from a resident world. */
+OCH_API int och_pool_read_box(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, int index_base,
+                              const int32_t lo[3], const int32_t hi[3], int kind, void *grid, size_t capacity_bytes);
 
 /* ------------------------------------------------------------ world */
 /* A DAG that stays on one GPU between brush strokes: the node store
@@ -779,8 +797,7 @@ OCH_API uint32_t och_pool_at(const uint32_t *nodes, uint32_t root, int depth, in
  * returns OCH_E_INVALID; pools keep what their last flush gave them.
  * OCH_BUILD_TRACE=1 prints phase times ("world ").
  * Out of scope: worlds replicated across GPUs, frame groups and the sharded
- * paths; 0-based pools; undo or checkout of older roots; a single-voxel `at`
- * on the device; a tight box after removals; depth 22. */
+ * paths; 0-based pools; undo or checkout of older roots; depth 22. */
 typedef struct och_world och_world;
 
 typedef struct och_world_stats {
@@ -790,7 +807,8 @@ typedef struct och_world_stats {
     int32_t depth, device;
     uint64_t strokes;     /* edits applied since create */
     uint64_t generation;  /* +1 per och_world_compact: store ids of another generation mean nothing */
-    int32_t box_lo[3], box_hi[3];  /* a superset of the voxels' box, [lo, hi); lo = hi = 0: none */
+    int32_t box_lo[3], box_hi[3];  /* a superset of the voxels' box, [lo, hi); lo = hi = 0: none.
+                                      Exact right after och_world_tighten */
 } och_world_stats;
 
 /* Adopt a pool: what och_edit_voxels accepts as its pool (host memory,
@@ -816,7 +834,7 @@ OCH_API int och_world_info(const och_world *world, och_world_stats *info);
  * records' own tree, ignoring what the rows share with the store, so the
  * answer depends on the records alone.  Call och_world_compact and retry.
  * The box grows by the box of the stroke's in-range records with id != 0;
- * removals never shrink it. */
+ * removals never shrink it (och_world_tighten does). */
 OCH_API int och_world_edit(och_world *world, const void *records, uint64_t n, int on_device);
 /* A pool of the current world on the world's device: index_base 1, the
  * world's depth, miss t = +INF, capacity slots (och_pool_info.n_nodes), its
@@ -844,6 +862,51 @@ OCH_API int och_world_download(och_world *world, och_host_pool *out);
  * and capacity are unchanged, `used` becomes the distinct nodes + 1,
  * generation + 1; every pool is rewritten whole by its next flush. */
 OCH_API int och_world_compact(och_world *world);
+
+/* ------------------------------------------------------------ world: reading back */
+/* Asking a resident world what it holds, on its GPU, under its current root:
+ * every stroke applied so far counts, flushed to a pool or not.  The store is
+ * append-only, so a query waits for nothing but its own kernel.  All three
+ * calls are synchronous: the world's stream is synchronised and the results
+ * are complete on return.  och_world_at and och_world_read_box only read: a
+ * HIP failure in them is reported (OCH_E_HIP) and leaves the world usable, as
+ * in och_world_download.  OCH_BUILD_TRACE=1 prints their phase times too.
+ * Out of scope: queries on an och_gpu_pool instead of the world; asynchronous
+ * queries on a caller's stream; reading older roots; run-length or sparse
+ * output; shrinking the box inside a stroke. */
+
+/* h_octree::at for n coordinates: coords is n x 3 int32 (x, y, z), AoS, and
+ * ids[i] becomes the voxel at coordinate i.  A coordinate outside [0, dim)
+ * gives 0 -- unlike och_pool_at, which does not range-check.  on_device != 0:
+ * both buffers are memory of the world's device, their writes complete (the
+ * kernel runs on the world's stream); otherwise both are host memory.
+ * n = 0 is a no-op.  OCH_E_INVALID, whatever the world: n >= 2^31, a NULL
+ * buffer with n > 0; then a NULL or broken world. */
+OCH_API int och_world_at(och_world *world, const int32_t *coords, uint64_t n, uint32_t *ids, int on_device);
+/* och_pool_read_box of the world's current content, byte for byte: the
+ * layout, the overhang (cells outside [0, dim) read 0), the empty box, the
+ * refusals before anything is written (a NULL lo, hi or grid, another kind,
+ * hi[a] < lo[a], a volume times the cell size above capacity_bytes; then a
+ * NULL or broken world) and OCH_E_INVALID naming an id above 255 met under
+ * OCH_VOXELS_GRID_U8, the grid's contents then unspecified.  on_device
+ * applies to grid only (memory of the world's device; lo and hi are host
+ * memory); a host grid goes through a device buffer the world allocates on
+ * demand and keeps.  A box that meets the tree in 2^32 aligned 4x4x4 bricks
+ * or more is refused (OCH_E_INVALID). */
+OCH_API int och_world_read_box(och_world *world, const int32_t lo[3], const int32_t hi[3], int kind, void *grid,
+                               size_t capacity_bytes, int on_device);
+/* Make the world's box exact: och_pool_occupied_box of what
+ * och_world_download would return; a world without voxels reports
+ * lo = hi = 0.  The next och_world_flush of each pool publishes it.  Later
+ * strokes grow it by their own boxes again, so it is exact right after this
+ * call and a superset afterwards.  No traced record depends on which superset
+ * of the voxels' box a pool holds, so frames are unchanged.
+ * The first call allocates 16 bytes per id of the world's capacity (256 MiB at
+ * capacity 2^24), kept for the world's life, and fills it for every id in use;
+ * later calls only visit the ids handed out since, a call after
+ * och_world_compact starts over.  OCH_E_NOMEM leaves the box and the world as
+ * they were; a HIP failure breaks the world, as in a stroke. */
+OCH_API int och_world_tighten(och_world *world);
 
 /* ------------------------------------------------------------ editor */
 /* Interactive editing (the demo's place/remove, ORT/test_och_h_octree.cpp:

@@ -251,9 +251,20 @@ inline host_pool edit_voxels(const och_edit_params &params)
     return p;
 }
 
+// A box of a host pool's voxels as a dense grid, x fastest, then y, then z
+// (och_pool_read_box): the grid och_voxel_params takes back.
+inline void read_box(const och_host_pool &pool, const int32_t lo[3], const int32_t hi[3], int kind, void *grid,
+                     size_t capacity_bytes)
+{
+    check(och_pool_read_box(pool.nodes, pool.n_nodes, pool.root, pool.depth, pool.index_base, lo, hi, kind, grid,
+                            capacity_bytes),
+          "och_pool_read_box");
+}
+
 // A world that stays on one GPU between brush strokes (och_world_*): edit()
 // applies a record list as edit_voxels would, flush() publishes the stroke's
-// new nodes to a tree made by make_pool(), download() gives the canonical pool.
+// new nodes to a tree made by make_pool(), download() gives the canonical pool;
+// at() and read_box() ask it what it holds, tighten() makes its box exact.
 class world {
 public:
     world(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, uint32_t capacity = 0, int device = -1)
@@ -283,6 +294,22 @@ public:
         return p;
     }
     void compact() { check(och_world_compact(w_), "och_world_compact"); }
+    // The voxels at n coordinates of (x, y, z) under the current root, 0 outside the tree; complete on return.
+    void at(const int32_t *coords, uint64_t n, uint32_t *ids, bool on_device = false)
+    {
+        check(och_world_at(w_, coords, n, ids, on_device ? 1 : 0), "och_world_at");
+    }
+    // The box [lo, hi) as a grid, x fastest (och_pool_read_box's bytes); kind is OCH_VOXELS_GRID_U8 or _U32.
+    void read_box(const int32_t lo[3], const int32_t hi[3], int kind, void *grid, size_t capacity_bytes, bool on_device = false)
+    {
+        check(och_world_read_box(w_, lo, hi, kind, grid, capacity_bytes, on_device ? 1 : 0), "och_world_read_box");
+    }
+    // The box made exact; the stats carry it (box_lo, box_hi; hi exclusive).
+    och_world_stats tighten()
+    {
+        check(och_world_tighten(w_), "och_world_tighten");
+        return info();
+    }
     och_world_stats info() const
     {
         och_world_stats st;

@@ -174,9 +174,13 @@ PROTOTYPES = {
     "och_world_flush": (C.c_int, [_P, _P]),
     "och_world_download": (C.c_int, [_P, C.POINTER(HostPool)]),
     "och_world_compact": (C.c_int, [_P]),
+    "och_world_at": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_int]),
+    "och_world_read_box": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, C.c_int]),
+    "och_world_tighten": (C.c_int, [_P]),
     "och_pool_pack": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "och_pool_at": (_u32, [_P, _u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "och_pool_occupied_box": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _P]),
+    "och_pool_read_box": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_size_t]),
     "och_editor_create": (C.c_int, [_P, _u32, _u32, C.c_int, _u32, C.POINTER(_P)]),
     "och_editor_destroy": (C.c_int, [_P]),
     "och_editor_set": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _u32]),

@@ -37,6 +37,20 @@ class NodePool:
         """h_octree::at (ORT/och_h_octree.h:239-258)."""
         return call("och_pool_at", self.nodes.ctypes.data, self.root, self.depth, self.index_base, x, y, z)
 
+    def read_box(self, lo, hi, dtype=np.uint8) -> np.ndarray:
+        """The voxels of the box lo <= (x, y, z) < hi as a dense (nz, ny, nx) array indexed [z, y, x]
+        (och_pool_read_box), the form build_voxels takes a grid in.  The box may reach outside the tree:
+        cells there read 0.  dtype is np.uint8 or np.uint32; OchError INVALID names an id that uint8
+        cannot hold."""
+        lo, hi, shape, kind = _read_box_args(lo, hi, dtype, "NodePool.read_box")
+        nodes = np.ascontiguousarray(self.nodes, np.uint32).reshape(-1, 8)
+        grid = np.zeros(shape, dtype)
+        # an empty grid still names a buffer: the call refuses NULL before it looks at the box
+        target = grid if grid.size else np.zeros(1, dtype)
+        call("och_pool_read_box", nodes.ctypes.data, nodes.shape[0], int(self.root), int(self.depth), int(self.index_base),
+             lo, hi, kind, target.ctypes.data, grid.nbytes)
+        return grid
+
     # -- linearised node-pool file (SURVEY §8f row 1): a 64-byte header, then the
     # n x 8 little-endian uint32 slots exactly as och_gpu_pool_create takes them.
     # The reference rebuilds its world on every start (ORT/test_och_h_octree.cpp:822);
@@ -92,6 +106,26 @@ class NodePool:
         if verify and cls._crc(ver, depth, base, root, n, memoryview(np.ascontiguousarray(nodes)).cast("B")) != crc:
             raise ValueError(f"{path}: checksum mismatch")
         return cls(np.asarray(nodes, dtype=np.uint32), root, depth, base)
+
+
+def _read_box_args(lo, hi, dtype, who: str):
+    """(lo, hi as int32[3], the (nz, ny, nx) shape, the grid kind) of a read_box call."""
+    if np.dtype(dtype) not in (np.dtype(np.uint8), np.dtype(np.uint32)):
+        raise ValueError(f"{who}: dtype is np.uint8 or np.uint32, not {np.dtype(dtype)}")
+    corners = []
+    for name, v in (("lo", lo), ("hi", hi)):
+        v = np.asarray(v)
+        if v.shape != (3,) or v.dtype.kind not in "iu":
+            raise ValueError(f"{who}: {name} is three integers (x, y, z), not {v.dtype} of shape {v.shape}")
+        v = v.astype(np.int64)
+        if v.min() < -(1 << 31) or v.max() >= 1 << 31:
+            raise ValueError(f"{who}: {name} outside int32")
+        corners.append(v)
+    if (corners[1] < corners[0]).any():
+        raise ValueError(f"{who}: hi {tuple(corners[1].tolist())} lies below lo {tuple(corners[0].tolist())}")
+    nx, ny, nz = (int(n) for n in corners[1] - corners[0])
+    kind = VOXELS_GRID_U8 if np.dtype(dtype) == np.dtype(np.uint8) else VOXELS_GRID_U32
+    return ((C.c_int32 * 3)(*corners[0].tolist()), (C.c_int32 * 3)(*corners[1].tolist()), (nz, ny, nx), kind)
 
 
 def build_terrain(depth: int, tunnels: bool = True, dedup: bool = True, rand_kind: str = "glibc",

@@ -5,8 +5,10 @@
 // builder, which builds the same DAG from a caller's voxels, is
 // och_voxel_build.h; the batch editor, which applies a list of edits to an
 // existing pool, is och_voxel_edit.h; the resident world, which keeps that
-// editor's store on the device between strokes, is och_world.h.  One
-// translation unit: the headers are included here and nowhere else.
+// editor's store on the device between strokes, is och_world.h, and what
+// reads that world back on the device (at, a box to a grid, the exact box) is
+// och_world_read.h.  One translation unit: the headers are included here and
+// nowhere else.
 //
 // The reference builds its tree by recursive create_volume + per-voxel
 // h_octree::set edits (ORT/test_och_h_octree.cpp:651-695, :767-787;
@@ -37,6 +39,7 @@
 #include "och_voxel_build.h"
 #include "och_voxel_edit.h"
 #include "och_world.h"
+#include "och_world_read.h"
 
 namespace {
 

@@ -95,6 +95,13 @@ int pool_create_for_world(int device, int depth, uint32_t capacity, uint64_t wor
 uint64_t pool_world(const och_gpu_pool *pool);
 int pool_world_view(och_gpu_pool *pool, uint64_t world, WorldPoolView *view);
 
+// What och_pool_read_box and och_world_read_box (och_world_read.h) refuse
+// alike before anything is written (och_pool.cpp): a NULL lo, hi or grid,
+// another kind than the two grids, hi[a] < lo[a], a volume times the cell size
+// above capacity_bytes.  *cells: the box's volume, 0 for an empty box.
+int read_box_cells(const char *who, const int32_t lo[3], const int32_t hi[3], int kind, const void *grid,
+                   size_t capacity_bytes, uint64_t *cells);
+
 // n_views views of one positive width and height (och_api.cpp).
 int check_views(const och_camera *cams, int n_views);
 

@@ -850,3 +850,97 @@ OCH_API uint32_t och_pool_at(const uint32_t *nodes, uint32_t root, int depth, in
     }
     return 0;
 }
+
+int och::read_box_cells(const char *who, const int32_t lo[3], const int32_t hi[3], int kind, const void *grid,
+                        size_t capacity_bytes, uint64_t *cells)
+{
+    *cells = 0;
+    if (!lo || !hi || !grid) return fail(OCH_E_INVALID, "%s: NULL argument", who);
+    if (kind != OCH_VOXELS_GRID_U8 && kind != OCH_VOXELS_GRID_U32)
+        return fail(OCH_E_INVALID, "%s: kind must be OCH_VOXELS_GRID_U8 or OCH_VOXELS_GRID_U32", who);
+    uint64_t n[3];
+    for (int a = 0; a < 3; ++a) {
+        if (hi[a] < lo[a]) return fail(OCH_E_INVALID, "%s: hi[%d] = %d lies below lo[%d] = %d", who, a, hi[a], a, lo[a]);
+        n[a] = (uint64_t)((int64_t)hi[a] - (int64_t)lo[a]);
+    }
+    if (!n[0] || !n[1] || !n[2]) return OCH_OK;
+    // n[0] * n[1] * n[2] <= room without forming a product that could pass 64 bits
+    const uint64_t room = (uint64_t)capacity_bytes / (kind == OCH_VOXELS_GRID_U8 ? 1u : 4u);
+    if (n[0] > room || n[1] > room / n[0] || n[2] > room / n[0] / n[1])
+        return fail(OCH_E_INVALID, "%s: a box of %llu x %llu x %llu cells does not fit %zu bytes", who,
+                    (unsigned long long)n[0], (unsigned long long)n[1], (unsigned long long)n[2], capacity_bytes);
+    *cells = n[0] * n[1] * n[2];
+    return OCH_OK;
+}
+
+namespace {
+
+// och_pool_read_box's walk: only the nodes that meet the box (clipped to the
+// tree) are visited, so empty space costs nothing beyond the zeroed grid.
+struct BoxReader {
+    const uint32_t *nodes;
+    int base;
+    int64_t clo[3], chi[3], lo[3];
+    uint64_t nx, ny;
+    bool u8;
+    void *grid;
+    uint32_t over = 0;   // the first id met that a u8 cell cannot hold
+
+    // node v at height h with its corner at o: its children have side 1 << h
+    void walk(uint32_t v, int h, const int64_t o[3])
+    {
+        const uint32_t *c = nodes + (size_t)(v - (uint32_t)base) * 8;
+        const int64_t s = (int64_t)1 << h;
+        for (int k = 0; k < 8 && !over; ++k) {
+            if (!c[k]) continue;
+            const int64_t p[3] = {o[0] + (k & 1) * s, o[1] + ((k >> 1) & 1) * s, o[2] + ((k >> 2) & 1) * s};
+            if (p[0] >= chi[0] || p[0] + s <= clo[0] || p[1] >= chi[1] || p[1] + s <= clo[1] || p[2] >= chi[2] ||
+                p[2] + s <= clo[2])
+                continue;
+            if (h) {
+                walk(c[k], h - 1, p);
+                continue;
+            }
+            const size_t at = ((size_t)(p[2] - lo[2]) * ny + (size_t)(p[1] - lo[1])) * nx + (size_t)(p[0] - lo[0]);
+            if (!u8)
+                static_cast<uint32_t *>(grid)[at] = c[k];
+            else if (c[k] <= 255u)
+                static_cast<uint8_t *>(grid)[at] = (uint8_t)c[k];
+            else
+                over = c[k];
+        }
+    }
+};
+
+}  // namespace
+
+OCH_API int och_pool_read_box(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, int index_base,
+                              const int32_t lo[3], const int32_t hi[3], int kind, void *grid, size_t capacity_bytes)
+{
+    if (!nodes) return fail(OCH_E_INVALID, "och_pool_read_box: NULL argument");
+    if (index_base != 0 && index_base != 1) return fail(OCH_E_INVALID, "och_pool_read_box: index_base must be 0 or 1");
+    uint64_t cells = 0;
+    if (const int cs = och::read_box_cells("och_pool_read_box", lo, hi, kind, grid, capacity_bytes, &cells)) return cs;
+    if (const int vs = validate_pool(nodes, n_nodes, root, depth, index_base)) return vs;
+    if (!cells) return OCH_OK;
+    BoxReader r{};
+    r.nodes = nodes;
+    r.base = index_base;
+    r.u8 = kind == OCH_VOXELS_GRID_U8;
+    r.grid = grid;
+    std::memset(grid, 0, (size_t)cells * (r.u8 ? 1 : 4));
+    const int64_t dim = (int64_t)1 << depth;
+    bool meets = !(index_base == 1 && root == 0);
+    for (int a = 0; a < 3; ++a) {
+        r.lo[a] = lo[a];
+        r.clo[a] = std::max<int64_t>(lo[a], 0);
+        r.chi[a] = std::min<int64_t>(hi[a], dim);
+        meets = meets && r.clo[a] < r.chi[a];
+    }
+    r.nx = (uint64_t)((int64_t)hi[0] - lo[0]);
+    r.ny = (uint64_t)((int64_t)hi[1] - lo[1]);
+    const int64_t origin[3] = {0, 0, 0};
+    if (meets) r.walk(root, depth - 1, origin);
+    if (r.over) return fail(OCH_E_INVALID, "och_pool_read_box: voxel id %u does not fit a u8 grid", r.over);
+    return OCH_OK;
+}

@@ -33,7 +33,8 @@
 //
 // Out of scope: worlds replicated across GPUs, frame groups and the sharded
 // paths; 0-based pools; undo or checkout of older roots (the store would allow
-// it); a single-voxel `at` on the device; a tight box after removals; depth 22.
+// it); depth 22.  Reading the world back (at, a box to a grid, the exact box
+// after removals) is och_world_read.h, with what stays out of scope there.
 #pragma once
 #include <memory>
 
@@ -134,6 +135,11 @@ struct och_world {
     uint64_t strokes = 0, generation = 0;
     bool box_any = false;
     int32_t box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
+    // och_world_read.h: freed after the destructor's body, the stream gone by then (hipFree waits for the device)
+    och::DevBuf<uint8_t> d_read;      // a host grid's, or host coordinates' and ids', way through the device
+    och::DevBuf<ulonglong2> d_lbox;   // the local boxes of ids [1, boxed) of generation lbox_generation
+    uint32_t boxed = 1;
+    uint64_t lbox_generation = 0;
 
     uint32_t *head() const { return S.next; }
     ~och_world()

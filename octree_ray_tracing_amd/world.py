@@ -13,13 +13,14 @@ import numpy as np
 
 from . import _lib
 from ._lib import HostPool, OchError, call
-from .builder import NodePool, _capacity, _host_records
+from .builder import VOXELS_GRID_U8, NodePool, _capacity, _host_records, _read_box_args
 from .tracer import HOctree
 
 
 class World:
     """A 1-based DAG resident on one GPU: edit() applies a record list as edit_voxels would, make_pool()
-    and flush() show it, download() gives the canonical pool, compact() drops what strokes left behind."""
+    and flush() show it, download() gives the canonical pool, compact() drops what strokes left behind;
+    at() and read_box() ask it what it holds without a download, tighten() makes its box exact."""
 
     def __init__(self, tree, capacity: int | None = None, device: int = -1):
         """tree is a NodePool with index_base 1 or a (nodes, root, depth) tuple in that form, as edit_voxels
@@ -121,6 +122,71 @@ class World:
             call("och_host_pool_free", C.byref(hp))
         return NodePool(arr, hp.root, hp.depth, hp.index_base, hp.solid_voxels, list(hp.voxel_hist), hp.tree_nodes,
                         hp.build_seconds)
+
+    def at(self, coords):
+        """The voxels at (n, 3) coordinates (x, y, z) under the current root, unflushed strokes included
+        (och_world_at); a coordinate outside the tree gives 0.  An integer array gives np.uint32 of shape
+        (n,); an int32 CUDA tensor on the world's device is read where it lies and gives an int32 CUDA
+        tensor holding the ids' bits.  Complete on return."""
+        if hasattr(coords, "is_cuda") and not coords.is_cuda:
+            coords = coords.numpy()
+        if hasattr(coords, "is_cuda"):
+            import torch
+
+            if coords.dim() != 2 or coords.shape[1] != 3 or coords.dtype != torch.int32:
+                raise ValueError(f"World.at: device coordinates are an (n, 3) int32 tensor, not "
+                                 f"{tuple(coords.shape)} {coords.dtype}")
+            h = self._open("at")
+            if coords.device.index != self.device:
+                raise ValueError(f"World.at: the tensor is on {coords.device}, the world on device {self.device}")
+            coords = coords.contiguous()
+            ids = torch.empty(coords.shape[0], dtype=torch.int32, device=coords.device)
+            torch.cuda.current_stream(coords.device).synchronize()       # the query reads on the world's stream
+            call("och_world_at", h, coords.data_ptr(), coords.shape[0], ids.data_ptr(), 1)
+            return ids
+        coords = np.asarray(coords)
+        if coords.ndim != 2 or coords.shape[1] != 3:
+            raise ValueError(f"World.at: an (n, 3) coordinate list, not shape {coords.shape}")
+        if coords.dtype.kind not in "iu":
+            raise ValueError(f"World.at: coordinates are integers, not {coords.dtype}")
+        if coords.dtype != np.int32:
+            wide = coords.astype(np.int64) if coords.dtype != np.uint64 else coords
+            if wide.size and (int(wide.min()) < -(1 << 31) or int(wide.max()) >= 1 << 31):
+                raise ValueError("World.at: a coordinate outside int32")
+            coords = wide.astype(np.int32)
+        coords = np.ascontiguousarray(coords)
+        ids = np.zeros(coords.shape[0], np.uint32)
+        call("och_world_at", self._open("at"), coords.ctypes.data if coords.size else None, coords.shape[0],
+             ids.ctypes.data if ids.size else None, 0)
+        return ids
+
+    def read_box(self, lo, hi, dtype=np.uint8, device: bool = False):
+        """The voxels of the box lo <= (x, y, z) < hi under the current root as a dense (nz, ny, nx)
+        array indexed [z, y, x] (och_world_read_box): NodePool.read_box of the download, byte for byte,
+        without the download.  dtype is np.uint8 or np.uint32.  device=True leaves the grid on the
+        world's device as a CUDA tensor (uint8, or int32 holding the ids' bits).  Complete on return."""
+        lo, hi, shape, kind = _read_box_args(lo, hi, dtype, "World.read_box")
+        h = self._open("read_box")
+        if device:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            grid = torch.empty(shape, dtype=torch.uint8 if kind == VOXELS_GRID_U8 else torch.int32, device=dev)
+            target = grid if grid.numel() else torch.empty(1, dtype=grid.dtype, device=dev)
+            torch.cuda.current_stream(dev).synchronize()                  # the allocation's stream before the world's
+            call("och_world_read_box", h, lo, hi, kind, target.data_ptr(), grid.numel() * grid.element_size(), 1)
+            return grid
+        grid = np.zeros(shape, dtype)
+        target = grid if grid.size else np.zeros(1, dtype)
+        call("och_world_read_box", h, lo, hi, kind, target.ctypes.data, grid.nbytes, 0)
+        return grid
+
+    def tighten(self):
+        """Make the world's box exact (och_world_tighten): (box_lo, box_hi), hi exclusive, both (0, 0, 0)
+        for a world without voxels.  The next flush of each pool publishes it; later strokes grow it again."""
+        call("och_world_tighten", self._open("tighten"))
+        info = self.info()
+        return info["box_lo"], info["box_hi"]
 
     def compact(self) -> None:
         """Drop what the root no longer reaches (och_world_compact): generation + 1, every pool is
