@@ -7,16 +7,18 @@
  * product path is the HIP library (octree_ray_tracing_amd/csrc) and fails
  * loudly when that library is missing.
  *
- * Parity status: the reference tracer (ORT/och_h_octree.h, ORT/och_octree.cpp)
- * cannot be compiled in this image without stand-ins (MSVC-only <intrin.h> and
- * the MSVC-only __m128::m128_f32 / m128_u32 members), so this restatement is
- * pinned by (a) the reference's own och_noise.h compiled as it lies
- * (oracle/_ref/ref_harness, see oracle/Makefile), (b) the known-answer values
- * SURVEY.md records from the reference run in this container (§4, §6, §7,
- * §8c: depth-3 zero-direction KAT, depth-8/10 node and voxel counts, mean
- * PUSH/STEP/POP per ray, hit fractions) and (c) the host's own RCPPS
- * instruction.  Per-ray hit records beyond those are "parity unpinned"
- * against a reference binary; see DESIGN.md §3.
+ * Parity status: pinned against the reference's own tracers and tree code
+ * (ORT/och_h_octree.h, ORT/och_octree.cpp), compiled where they lie into
+ * oracle/_ref/ref_trace (oracle/ref_trace.cpp, oracle/Makefile): per-ray
+ * records, bit for bit and with no ray excluded, on the trees and rays of
+ * tests/ref_cases.py, live and from tests/golden/ref_trace_*.npz
+ * (tests/test_oracle_pins.py).  Further pins: (a) the reference's own
+ * och_noise.h compiled as it lies (oracle/_ref/ref_harness), (b) the
+ * known-answer values SURVEY.md records from the reference run in this
+ * container (§4, §6, §7, §8c: depth-3 zero-direction KAT, depth-8/10 node and
+ * voxel counts, mean PUSH/STEP/POP per ray, hit fractions) and (c) the host's
+ * own RCPPS instruction.  PUSH counts are pinned by (b)'s statistics only: the
+ * reference exposes no counter.  See DESIGN.md §3.
  *
  * ORT/ = /root/reference/Octree_Ray_Tracing/.  Compile with
  * -ffp-contract=off (the reference pins fused ops with explicit intrinsics and

@@ -3,8 +3,9 @@
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py, always as the checker, never as the thing being
 measured or shipped.  See oracle/och_oracle.c for what each entry restates
-(reference file:line) and for the parity status ("parity unpinned" per-ray
-against a reference binary; pinned by the reference's own noise source and the
+(reference file:line) and for the parity status (per-ray records pinned
+against the reference's own tracers, compiled into oracle/_ref/ref_trace and
+run by ref_trace() below; also by the reference's own noise source and the
 SURVEY known-answer values).
 """
 from __future__ import annotations
@@ -19,6 +20,7 @@ import numpy as np
 HERE = Path(__file__).resolve().parent
 LIB_PATH = HERE / "build" / "liboch_oracle.so"
 REF_HARNESS = HERE / "_ref" / "ref_harness"
+REF_TRACE = HERE / "_ref" / "ref_trace"
 
 INF = float("inf")
 
@@ -290,6 +292,46 @@ def ref_run(mode: str, records: np.ndarray, freq: float = 1.0) -> bytes:
     out = subprocess.run([str(REF_HARNESS), mode, repr(float(freq))], input=records.tobytes(),
                          capture_output=True, check=True)
     return out.stdout
+
+
+def ref_trace_available() -> bool:
+    return REF_TRACE.exists() and os.access(REF_TRACE, os.X_OK)
+
+
+def ref_trace(kind: str, depth: int, ops, origins: np.ndarray, dirs: np.ndarray,
+              capacity: int | None = None, timeout: float = 120.0) -> dict:
+    """Run the reference's own tracer (oracle/_ref/ref_trace, ORT/och_h_octree.h
+    or ORT/och_octree.cpp compiled where they lie) in a child process.
+
+    kind "h": h_octree<19, depth>; ops are set(x, y, z, v) records.
+    kind "o": octree(depth, capacity); ops with v == 0 are unset(x, y, z).
+    Returns dir / voxel / t per ray and "tail": get_root() ("h") or
+    get_node_cnt() ("o").  Raises when the child is killed at the timeout,
+    exits non-zero or answers with anything but n records."""
+    if kind not in ("h", "o"):
+        raise ValueError("kind is 'h' (h_octree) or 'o' (octree)")
+    ops = np.ascontiguousarray(ops, dtype=np.uint32).reshape(-1, 4)
+    dirs = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    n = dirs.shape[0]
+    origins = np.ascontiguousarray(origins, dtype=np.float32)
+    origins = np.tile(origins.reshape(1, 3), (n, 1)) if origins.size == 3 else origins.reshape(n, 3)
+    rays = np.ascontiguousarray(np.concatenate([origins, dirs], axis=1), dtype=np.float32)
+    if not np.all(np.isfinite(rays)):
+        raise ValueError("the reference tracer need not terminate on NaN or inf rays")
+    argv = [str(REF_TRACE), kind, str(int(depth))]
+    if kind == "o":
+        if capacity is None:
+            raise ValueError("octree needs a table capacity")
+        argv.append(str(int(capacity)))
+    head = np.array([ops.shape[0], n], np.uint32)
+    # subprocess.run kills the child when the timeout expires and raises TimeoutExpired
+    out = subprocess.run(argv, input=head.tobytes() + ops.tobytes() + rays.tobytes(),
+                         capture_output=True, check=True, timeout=timeout).stdout
+    if len(out) != 12 * n + 4:
+        raise RuntimeError(f"ref_trace answered {len(out)} bytes for {n} rays (table full?): {out[-80:]!r}")
+    rec = np.frombuffer(out, dtype=np.dtype([("dir", "<i4"), ("voxel", "<u4"), ("t", "<f4")]), count=n)
+    return {"dir": rec["dir"].copy(), "voxel": rec["voxel"].copy(), "t": rec["t"].copy(),
+            "tail": int(np.frombuffer(out, np.uint32, count=1, offset=12 * n)[0])}
 
 
 class HRef:

@@ -1,6 +1,7 @@
 """Regenerate tests/golden/ (run in the build container, where /root/reference exists).
 
-    python tests/make_golden.py
+    python tests/make_golden.py              every fixture
+    python tests/make_golden.py ref_trace    only ref_trace_*.npz
 
 Fixtures (all small, data only):
   rcp_lut_intel.bin   RCPPS of this container's Intel CPU for inputs -(1 + k/2048), k < 2048,
@@ -12,7 +13,18 @@ Fixtures (all small, data only):
   trace_d6.npz        a depth-6 terrain pool, ray sets (camera, random, edge cases) and the
                       oracle's hit records under the Intel table (regression vectors; the
                       oracle itself is pinned by known_answers.json).
-  known_answers.json  values SURVEY.md reports from the reference run in this container.
+  ref_trace_<k><D>.npz  the REFERENCE's own tracers on the trees and rays of tests/ref_cases.py:
+                      och::h_octree<19, D>::sse_trace (k = h; D = 2, 3, 6, 8, 12, 16) and
+                      och::octree::sse_trace (k = o; D = 2, 3, 6, 8), compiled where they lie
+                      by oracle/Makefile (oracle/_ref/ref_trace) and run on this host.  Each
+                      holds the tree's ops, the rays, the binary's records (direction, voxel,
+                      t bits, every ray), get_root() / get_node_cnt(), and the RCPPS table
+                      och_host_rcp_lut returned on this host.  The expectation is the
+                      reference's, not the oracle's: tests/test_oracle_pins.py replays them
+                      through the oracle, tests/test_gpu_reference.py through the kernels.
+  known_answers.json  values SURVEY.md reports from the reference run in this container;
+                      its zero_direction_quirk cases are re-derived live from
+                      oracle/_ref/ref_trace by tests/test_oracle_pins.py.
 """
 from __future__ import annotations
 
@@ -47,6 +59,21 @@ def edge_rays():
     return np.array(o, np.float32), np.array(d, np.float32)
 
 
+def record_ref_traces(O, lut):
+    """The reference binary's records on every case of tests/ref_cases.py."""
+    import ref_cases as RC
+    if not O.ref_trace_available():
+        raise SystemExit("oracle/_ref/ref_trace missing: run make -C oracle with /root/reference present")
+    for kind, depth in RC.CASES:
+        c = RC.case(kind, depth)
+        r = O.ref_trace(kind, depth, c["ops"], c["o"], c["d"], c["capacity"])
+        path = GOLD / RC.fixture_name(kind, depth)
+        np.savez_compressed(path, ops=c["ops"], o=c["o"], d=c["d"], aimed=c["aimed"],
+                            dir=r["dir"].astype(np.int8), vox=r["voxel"], t=r["t"].view(np.uint32),
+                            tail=np.uint32(r["tail"]), capacity=np.uint32(c["capacity"] or 0), lut=lut)
+        print(f"{path.name}: {len(c['o'])} rays, {path.stat().st_size} bytes")
+
+
 def main():
     import octree_ray_tracing_amd as ort
     from oracle import oracle as O
@@ -57,6 +84,9 @@ def main():
     sha = hashlib.sha256(lut.tobytes()).hexdigest()
     if sha != SURVEY_LUT_SHA256:
         raise SystemExit(f"this host's RCPPS table {sha} is not the survey's Intel table")
+    if sys.argv[1:] == ["ref_trace"]:
+        record_ref_traces(O, lut)
+        return
     (GOLD / "rcp_lut_intel.bin").write_bytes(lut.tobytes())
 
     if not O.ref_harness_available():
@@ -97,6 +127,7 @@ def main():
         out[f"{name}_dir"], out[f"{name}_vox"] = r["dir"], r["voxel"]
         out[f"{name}_t"], out[f"{name}_push"] = r["t"].view(np.uint32), r["push"]
     np.savez_compressed(GOLD / "trace_d6.npz", **out)
+    record_ref_traces(O, lut)
     print("golden fixtures written to", GOLD)
 
 

@@ -1,5 +1,7 @@
 """The CPU oracle against everything that pins it:
-the reference's own noise / z-order code (golden vectors made by
+the reference's own tracers and tree edits (oracle/_ref/ref_trace from
+ORT/och_h_octree.h and ORT/och_octree.cpp, live and as golden records), the
+reference's own noise / z-order code (golden vectors made by
 oracle/_ref/ref_harness from ORT/och_noise.h and ORT/och_z_order.cpp), the
 known-answer values SURVEY.md records from the reference run in this
 container, and the host's RCPPS instruction."""
@@ -9,6 +11,7 @@ import math
 import numpy as np
 import pytest
 
+import ref_cases as RC
 from conftest import GOLD
 
 
@@ -185,3 +188,107 @@ def test_sparse_dag_matches_reference_set(O):
     final = {(x, y, z): v for x, y, z, v in vox}      # a later set() of a voxel wins
     for (x, y, z), v in list(final.items())[::7]:
         assert T.at(x, y, z) == v
+
+
+# --- the oracle against the reference's own tracers -------------------------
+# oracle/_ref/ref_trace is ORT/och_h_octree.h and ORT/och_octree.cpp compiled
+# where they lie (oracle/Makefile).  Live tests run it here; the golden tests
+# replay what it answered on the recording host (tests/golden/ref_trace_*.npz,
+# made by tests/make_golden.py), so the expectation is the reference's, never
+# the oracle's own output.  No ray is excluded from any comparison.
+
+REF_CASES = [pytest.param(k, d, id=RC.case_name(k, d)) for k, d in RC.CASES]
+_oracle_trees = {}
+
+
+def _fixture(kind, depth):
+    g = np.load(GOLD / RC.fixture_name(kind, depth))
+    return {"kind": kind, "depth": depth, "ops": g["ops"], "o": g["o"], "d": g["d"], "aimed": g["aimed"],
+            "capacity": int(g["capacity"]) or None, "lut": g["lut"], "tail": int(g["tail"]),
+            "ref": {"dir": g["dir"].astype(np.int32), "voxel": g["vox"], "t": g["t"].view(np.float32)}}
+
+
+def _oracle_tree(O, c):
+    """The oracle's tree for a case, built once and left unchanged."""
+    key = (c["kind"], c["depth"])
+    if key not in _oracle_trees:
+        _oracle_trees[key] = RC.oracle_tree(O, c["kind"], c["depth"], c["ops"], c["capacity"])
+    return _oracle_trees[key]
+
+
+def _assert_records(c, ref, got):
+    bad = RC.records_differ(ref, got)
+    assert bad.size == 0, (f"{bad.size} of {len(c['o'])} records differ; " +
+                           "; ".join(RC.describe(c, i, reference=ref, oracle=got) for i in bad[:3]))
+
+
+@pytest.mark.parametrize("kind,depth", REF_CASES)
+def test_fixture_holds_the_generators_case(kind, depth):
+    """The committed trees and rays are tests/ref_cases.py's, ray for ray: what
+    was shown about that ray set (it tells five single mutations of the tracer
+    from the reference) holds for the fixtures."""
+    c, g = _fixture(kind, depth), RC.case(kind, depth)
+    assert np.array_equal(c["ops"], g["ops"]) and c["capacity"] == g["capacity"]
+    for k in ("o", "d"):
+        assert np.array_equal(c[k].view(np.uint32), g[k].view(np.uint32)), k
+    assert np.array_equal(c["aimed"], g["aimed"])
+    assert np.all(np.isfinite(c["o"])) and np.all(np.isfinite(c["d"]))
+
+
+@pytest.mark.parametrize("kind,depth", REF_CASES)
+def test_reference_golden_records(O, kind, depth):
+    """The oracle under the recording host's RCPPS table reproduces the
+    reference binary's records, and its tree the reference's root / node count."""
+    c = _fixture(kind, depth)
+    ref = c["ref"]
+    T, tail = _oracle_tree(O, c)
+    assert tail == c["tail"]
+    _assert_records(c, ref, O.trace_batch(T.pool(), O.Rcp(c["lut"]), c["o"], c["d"]))
+    miss = ref["dir"] == 6
+    assert miss.any() and np.all(ref["voxel"][miss] == 0)
+    want_miss = np.float32(np.inf if kind == "h" else 0.0).view(np.uint32)
+    assert np.all(ref["t"][miss].view(np.uint32) == want_miss)
+    hit = ref["dir"] < 6
+    # deep trees are reached: more than a tenth of the aimed rays hit
+    assert hit[c["aimed"]].sum() > c["aimed"].sum() // 10
+    assert set(np.unique(ref["dir"][hit])) == set(range(6))
+
+
+@pytest.mark.parametrize("kind,depth", REF_CASES)
+def test_reference_live_records(O, kind, depth):
+    """The same trees and rays through the binary on this host, against the
+    oracle with this host's own RCPPS instruction."""
+    if not O.ref_trace_available():
+        pytest.skip("oracle/_ref/ref_trace not built (no reference tree)")
+    c = _fixture(kind, depth)
+    ref = O.ref_trace(kind, depth, c["ops"], c["o"], c["d"], c["capacity"])
+    T, tail = _oracle_tree(O, c)
+    assert tail == ref["tail"]                      # HRef.root == get_root(), ORef.node_cnt == get_node_cnt()
+    _assert_records(c, ref, O.trace_batch(T.pool(), O.Rcp(None), c["o"], c["d"]))
+
+
+def test_zero_direction_quirk_live(O, ort, known, intel_lut):
+    """known_answers.json's zero_direction_quirk cases, re-derived from the
+    reference binary.  The committed values are those of the Intel table's
+    host, so the comparison is made where this host's RCPPS is that table."""
+    if not O.ref_trace_available():
+        pytest.skip("oracle/_ref/ref_trace not built (no reference tree)")
+    if not np.array_equal(ort.host_rcp_lut(), intel_lut):
+        pytest.skip("this host's RCPPS is not the Intel table the known answers were recorded under")
+    k = known["zero_direction_quirk"]
+    dirs = np.array([case["dir"] for case in k["cases"]], np.float32)
+    r = O.ref_trace("h", k["depth"], k["voxels"], np.array(k["origin"], np.float32), dirs)
+    for i, case in enumerate(k["cases"]):
+        assert (int(r["dir"][i]), int(r["voxel"][i])) == (case["direction"], case["voxel"])
+        assert float(r["t"][i]) == float.fromhex(case["t_hex"])
+
+
+def test_ref_trace_reports_failure(O):
+    """A depth the binary does not instantiate exits non-zero: the call raises."""
+    if not O.ref_trace_available():
+        pytest.skip("oracle/_ref/ref_trace not built (no reference tree)")
+    import subprocess
+    with pytest.raises(subprocess.CalledProcessError):
+        O.ref_trace("h", 5, [[0, 0, 0, 1]], [1.5, 1.5, 1.5], [[0.0, 0.0, -1.0]])
+    with pytest.raises(ValueError):
+        O.ref_trace("h", 3, [[0, 0, 0, 1]], [1.5, 1.5, 1.5], [[np.nan, 0.0, -1.0]])
