@@ -778,6 +778,32 @@ OCH_API uint32_t och_pool_at(const uint32_t *nodes, uint32_t root, int depth, in
 OCH_API int och_pool_read_box(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, int index_base,
                               const int32_t lo[3], const int32_t hi[3], int kind, void *grid, size_t capacity_bytes);
 
+/* What a diff reports (och_pool_diff here, och_world_diff below). */
+typedef struct och_diff_stats {
+    uint64_t n;                    /* voxels whose id differs between the two roots */
+    uint64_t pairs;                /* node positions expanded, the root's included */
+    int32_t box_lo[3], box_hi[3];  /* box of those voxels, [lo, hi); lo = hi = 0 when n = 0 */
+} och_diff_stats;                  /* 40 bytes */
+/* The voxels that differ between two host pools of one depth and index_base:
+ * for every coordinate where the voxel under (nodes_a, root_a) differs from the
+ * one under (nodes_b, root_b), one record (x, y, z, id under b), 4 x uint32 in
+ * the OCH_VOXELS_LIST layout, id 0 = the voxel was removed; in ascending Morton
+ * order (key = x bit 0, y bit 1, z bit 2 per level).  Applied as edits to a's
+ * content the records give b's.  The pools need not be canonical; an all-zero
+ * node counts as no node.  capacity counts records; records = NULL is the
+ * summary form: only *stats.  och_world_diff gives the same records, n and box
+ * for the same two contents; `pairs` here is the positions this walk visited,
+ * which prunes only where both arguments are the same array and the ids are
+ * equal, so it is not comparable with the world's.
+ * Refused before anything is written -- OCH_E_INVALID: NULL stats or nodes,
+ * index_base outside 0 and 1, depth outside 1..21, a pool
+ * och_pool_occupied_box refuses, 2^31 differing voxels or more.
+ * OCH_E_CAPACITY: records != NULL and n > capacity; *stats is complete and
+ * nothing has been written to records. */
+OCH_API int och_pool_diff(const uint32_t *nodes_a, uint32_t n_a, uint32_t root_a,
+                          const uint32_t *nodes_b, uint32_t n_b, uint32_t root_b, int depth, int index_base,
+                          void *records, uint64_t capacity, och_diff_stats *stats);
+
 /* ------------------------------------------------------------ world */
 /* A DAG that stays on one GPU between brush strokes: the node store
  * och_edit_voxels builds per call (nodes, levels, hash table), kept, with the
@@ -797,7 +823,8 @@ OCH_API int och_pool_read_box(const uint32_t *nodes, uint32_t n_nodes, uint32_t 
  * returns OCH_E_INVALID; pools keep what their last flush gave them.
  * OCH_BUILD_TRACE=1 prints phase times ("world ").
  * Out of scope: worlds replicated across GPUs, frame groups and the sharded
- * paths; 0-based pools; undo or checkout of older roots; depth 22. */
+ * paths; 0-based pools; depth 22.  Earlier roots (undo, checkout, the diff of
+ * two roots) are the history section below. */
 typedef struct och_world och_world;
 
 typedef struct och_world_stats {
@@ -857,10 +884,12 @@ OCH_API int och_world_flush(och_world *world, och_gpu_pool *pool);
  * what och_build_voxels / och_edit_voxels give for the same content; freed
  * with och_host_pool_free.  The world is unchanged: the save path. */
 OCH_API int och_world_download(och_world *world, och_host_pool *out);
-/* Drop what the root no longer reaches: the reachable nodes renumbered on the
- * device and interned into a fresh store of the same capacity.  Content, box
- * and capacity are unchanged, `used` becomes the distinct nodes + 1,
- * generation + 1; every pool is rewritten whole by its next flush. */
+/* Drop what neither the root nor a live snapshot (below) reaches: the
+ * reachable nodes interned into a fresh store of the same capacity.  Content
+ * (the current root's and every snapshot's), box and capacity are unchanged
+ * and every handle stays valid; `used` becomes the distinct nodes reachable
+ * from all of them + 1, generation + 1; every pool is rewritten whole by its
+ * next flush.  A failure leaves the old store and every handle in place. */
 OCH_API int och_world_compact(och_world *world);
 
 /* ------------------------------------------------------------ world: reading back */
@@ -872,8 +901,9 @@ OCH_API int och_world_compact(och_world *world);
  * HIP failure in them is reported (OCH_E_HIP) and leaves the world usable, as
  * in och_world_download.  OCH_BUILD_TRACE=1 prints their phase times too.
  * Out of scope: queries on an och_gpu_pool instead of the world; asynchronous
- * queries on a caller's stream; reading older roots; run-length or sparse
- * output; shrinking the box inside a stroke. */
+ * queries on a caller's stream; run-length or sparse output; shrinking the box
+ * inside a stroke.  An older root is read by checking its snapshot out first
+ * (och_world_checkout, below: O(1)). */
 
 /* h_octree::at for n coordinates: coords is n x 3 int32 (x, y, z), AoS, and
  * ids[i] becomes the voxel at coordinate i.  A coordinate outside [0, dim)
@@ -907,6 +937,61 @@ OCH_API int och_world_read_box(och_world *world, const int32_t lo[3], const int3
  * och_world_compact starts over.  OCH_E_NOMEM leaves the box and the world as
  * they were; a HIP failure breaks the world, as in a stroke. */
 OCH_API int och_world_tighten(och_world *world);
+
+/* ------------------------------------------------------------ world: history */
+/* The store is append-only, so every earlier state of a world is still intact
+ * on the GPU: a snapshot remembers one, a checkout makes it current again
+ * (undo; strokes after it branch off, and the state left behind stays
+ * reachable through its own snapshot: redo), and och_world_diff answers what
+ * changed between two of them at a cost that follows the change, not the world.
+ * A snapshot is a handle: handles start at 1 per world, are never reused and
+ * mean something only for that world; two snapshots of one state are two
+ * handles.  It keeps the root, its child mask and the world's box as they are
+ * at the call, and lives until och_world_release or och_world_destroy;
+ * och_world_compact keeps what live snapshots reach.
+ * Out of scope: snapshots across och_world_destroy, or their serialisation; a
+ * diff between two worlds or between generations; och_world_at /
+ * och_world_read_box of a snapshot (check it out first); asynchronous diffs;
+ * replicated worlds themselves (diff(A, B) applied as one och_world_edit turns
+ * a replica holding A into B: this is their primitive); frame groups and the
+ * sharded paths. */
+#define OCH_WORLD_CURRENT 0ull            /* as `from` / `to` / `snapshot`: the world's current root */
+#define OCH_WORLD_MAX_SNAPSHOTS 65536
+/* Remember the current root.  OCH_E_INVALID: a NULL snapshot, a NULL or broken
+ * world; OCH_E_CAPACITY: OCH_WORLD_MAX_SNAPSHOTS are live already. */
+OCH_API int och_world_snapshot(och_world *world, uint64_t *snapshot);
+/* Make the snapshot's root, mask and box the world's again: O(1), nothing is
+ * launched; used, strokes, generation and the store do not change.  The box is
+ * the one the world had at the snapshot, a superset of that content
+ * (och_world_tighten makes it exact); the next och_world_flush of each pool
+ * publishes the root.  OCH_WORLD_CURRENT is a no-op.  OCH_E_INVALID, the text
+ * naming the handle: an unknown or released one. */
+OCH_API int och_world_checkout(och_world *world, uint64_t snapshot);
+/* Forget a snapshot; what only it reached goes with the next och_world_compact.
+ * OCH_E_INVALID: an unknown or released handle, OCH_WORLD_CURRENT. */
+OCH_API int och_world_release(och_world *world, uint64_t snapshot);
+/* The live handles in ascending order: up to `capacity` of them into ids
+ * (NULL with capacity 0: count only), the total in *count. */
+OCH_API int och_world_snapshots(const och_world *world, uint64_t *ids, uint32_t capacity, uint32_t *count);
+/* och_pool_diff of the contents under two roots of this world, on its GPU:
+ * the same records in the same (ascending Morton) order, the same n and box.
+ * from / to are snapshot handles or OCH_WORLD_CURRENT.  capacity counts
+ * records; on_device != 0: records is memory of the world's device, otherwise
+ * host memory, reached through a device buffer the world keeps; records = NULL
+ * is the summary form: only *stats.  Two ids at one height are equal exactly
+ * when their subtrees hold the same voxels, so the walk expands only positions
+ * whose subtrees differ: `pairs`, the frontier sizes summed over the levels,
+ * is the sum over h = 1..depth of the distinct values of key >> 3h over the
+ * differing voxels' Morton keys, and roots with equal ids give n = 0, pairs = 0
+ * and no launch.  Synchronous on the world's stream (one 8-byte read-back per
+ * level); the buffers are kept, grown on demand.  It only reads: a HIP failure
+ * is OCH_E_HIP and leaves the world usable.
+ * Refused, nothing written -- OCH_E_INVALID: NULL stats, a NULL or broken
+ * world, an unknown handle, a level's frontier or an n of 2^31 or more.
+ * OCH_E_CAPACITY: records != NULL and n > capacity; *stats is complete and
+ * nothing has been written to records. */
+OCH_API int och_world_diff(och_world *world, uint64_t from, uint64_t to, void *records, uint64_t capacity,
+                           int on_device, och_diff_stats *stats);
 
 /* ------------------------------------------------------------ editor */
 /* Interactive editing (the demo's place/remove, ORT/test_och_h_octree.cpp:

@@ -261,10 +261,22 @@ inline void read_box(const och_host_pool &pool, const int32_t lo[3], const int32
           "och_pool_read_box");
 }
 
+// The voxels that differ between two host pools of one depth and index_base
+// (och_pool_diff): records of (x, y, z, id under b) in ascending Morton order;
+// records = nullptr gives the stats alone.
+inline och_diff_stats pool_diff(const och_host_pool &a, const och_host_pool &b, void *records = nullptr, uint64_t capacity = 0)
+{
+    och_diff_stats st;
+    check(och_pool_diff(a.nodes, a.n_nodes, a.root, b.nodes, b.n_nodes, b.root, a.depth, a.index_base, records, capacity, &st),
+          "och_pool_diff");
+    return st;
+}
+
 // A world that stays on one GPU between brush strokes (och_world_*): edit()
 // applies a record list as edit_voxels would, flush() publishes the stroke's
 // new nodes to a tree made by make_pool(), download() gives the canonical pool;
-// at() and read_box() ask it what it holds, tighten() makes its box exact.
+// at() and read_box() ask it what it holds, tighten() makes its box exact;
+// snapshot(), checkout() and release() keep earlier states, diff() compares two.
 class world {
 public:
     world(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, uint32_t capacity = 0, int device = -1)
@@ -314,6 +326,25 @@ public:
     {
         och_world_stats st;
         check(och_world_info(w_, &st), "och_world_info");
+        return st;
+    }
+    // Remember the current root: a handle for checkout() and diff(), live until release().
+    uint64_t snapshot()
+    {
+        uint64_t s = 0;
+        check(och_world_snapshot(w_, &s), "och_world_snapshot");
+        return s;
+    }
+    // Make a snapshot the current state again (undo / redo): O(1), nothing is launched.
+    void checkout(uint64_t s) { check(och_world_checkout(w_, s), "och_world_checkout"); }
+    void release(uint64_t s) { check(och_world_release(w_, s), "och_world_release"); }
+    // What differs between two snapshots (OCH_WORLD_CURRENT: the current state): records of (x, y, z, id
+    // under to) in ascending Morton order, what edit() takes; records = nullptr gives the stats alone.
+    och_diff_stats diff(uint64_t from, uint64_t to = OCH_WORLD_CURRENT, void *records = nullptr, uint64_t capacity = 0,
+                        bool on_device = false)
+    {
+        och_diff_stats st;
+        check(och_world_diff(w_, from, to, records, capacity, on_device ? 1 : 0, &st), "och_world_diff");
         return st;
     }
 

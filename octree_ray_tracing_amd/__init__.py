@@ -13,8 +13,8 @@ from .frame import FrameGroup, RcclComm, ShardedFrame, ShardedSteps, box_downsam
 from .tracer import (Direction, GpuPool, HOctree, Octree, camera, deal_chunks, display_weight, device_count, device_list, host_rcp_lut,
                      light_check, rcp_from_lut, rcp_lut_error, shard_rows, split_defaults)
 from .voxels import VoxelData, VoxelDataError
-from .world import World
+from .world import UndoStack, World
 
 __all__ = ["LIGHT_AO", "LIGHT_SUN", "Light", "light_check", "shade_lit", "shade_lit_codes", "code_table", "OchError", "library_path", "load", "NodePool", "build_terrain", "build_voxels", "edit_voxels", "box_records", "occupied_box", "pack_pool", "Editor", "FrameGroup", "RcclComm", "ShardedFrame", "ShardedSteps", "box_downsample", "Direction", "GpuPool",
            "HOctree", "Octree", "camera", "deal_chunks", "display_weight", "device_count", "device_list", "host_rcp_lut", "rcp_from_lut", "rcp_lut_error", "shard_rows", "split_defaults",
-           "VoxelData", "VoxelDataError", "World"]
+           "VoxelData", "VoxelDataError", "World", "UndoStack"]

@@ -67,6 +67,11 @@ class WorldStats(C.Structure):
                 ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3)]
 
 
+class DiffStats(C.Structure):
+    """och_diff_stats: what och_pool_diff and och_world_diff report."""
+    _fields_ = [("n", C.c_uint64), ("pairs", C.c_uint64), ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3)]
+
+
 class TerrainParams(C.Structure):
     _fields_ = [("depth", C.c_int32), ("tunnels", C.c_int32), ("dedup", C.c_int32),
                 ("rand_kind", C.c_int32), ("threads", C.c_int32), ("use_gpu", C.c_int32)]
@@ -177,10 +182,16 @@ PROTOTYPES = {
     "och_world_at": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_int]),
     "och_world_read_box": (C.c_int, [_P, _P, _P, C.c_int, _P, C.c_size_t, C.c_int]),
     "och_world_tighten": (C.c_int, [_P]),
+    "och_world_snapshot": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "och_world_checkout": (C.c_int, [_P, C.c_uint64]),
+    "och_world_release": (C.c_int, [_P, C.c_uint64]),
+    "och_world_snapshots": (C.c_int, [_P, _P, _u32, C.POINTER(_u32)]),
+    "och_world_diff": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, C.c_uint64, C.c_int, C.POINTER(DiffStats)]),
     "och_pool_pack": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "och_pool_at": (_u32, [_P, _u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "och_pool_occupied_box": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _P]),
     "och_pool_read_box": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_size_t]),
+    "och_pool_diff": (C.c_int, [_P, _u32, _u32, _P, _u32, _u32, C.c_int, C.c_int, _P, C.c_uint64, C.POINTER(DiffStats)]),
     "och_editor_create": (C.c_int, [_P, _u32, _u32, C.c_int, _u32, C.POINTER(_P)]),
     "och_editor_destroy": (C.c_int, [_P]),
     "och_editor_set": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _u32]),
@@ -211,6 +222,9 @@ PROTOTYPES = {
     "och_gpu_render_sharded_steps_dev": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P,
                                                    C.c_int, C.c_int, C.c_int]),
 }
+
+# och_world_checkout / och_world_diff: the world's current root (include/och_gpu.h OCH_WORLD_*)
+WORLD_CURRENT, WORLD_MAX_SNAPSHOTS = 0, 65536
 
 # och_light.flags (include/och_gpu.h OCH_LIGHT_*)
 LIGHT_SUN, LIGHT_AO = 1, 2

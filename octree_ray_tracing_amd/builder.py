@@ -15,7 +15,12 @@ from pathlib import Path
 
 import numpy as np
 
-from ._lib import EditParams, HostPool, OchError, TerrainParams, VoxelParams, call
+from ._lib import DiffStats, EditParams, HostPool, OchError, TerrainParams, VoxelParams, call
+
+
+def diff_stats_dict(st: DiffStats) -> dict:
+    """och_diff_stats as NodePool.diff and World.diff return it."""
+    return {"n": int(st.n), "pairs": int(st.pairs), "box_lo": tuple(st.box_lo), "box_hi": tuple(st.box_hi)}
 
 
 @dataclass
@@ -50,6 +55,30 @@ class NodePool:
         call("och_pool_read_box", nodes.ctypes.data, nodes.shape[0], int(self.root), int(self.depth), int(self.index_base),
              lo, hi, kind, target.ctypes.data, grid.nbytes)
         return grid
+
+    def diff(self, other: "NodePool", records: bool = True):
+        """The voxels that differ between this pool and `other` (same depth and index_base), as
+        (records, stats) (och_pool_diff): an (n, 4) np.uint32 array of (x, y, z, id under other) in
+        ascending Morton order, id 0 where the voxel is gone, and {"n", "pairs", "box_lo", "box_hi"}.
+        Applied to this pool's content with edit_voxels the records give other's.  records=False gives
+        None and the stats."""
+        if not isinstance(other, NodePool):
+            raise ValueError(f"NodePool.diff: a NodePool, not {type(other).__name__}")
+        if (other.depth, other.index_base) != (self.depth, self.index_base):
+            raise ValueError(f"NodePool.diff: depth {other.depth} / index_base {other.index_base} against depth "
+                             f"{self.depth} / index_base {self.index_base}")
+        a = np.ascontiguousarray(self.nodes, np.uint32).reshape(-1, 8)
+        b = a if other.nodes is self.nodes else np.ascontiguousarray(other.nodes, np.uint32).reshape(-1, 8)
+        st = DiffStats()
+        args = (a.ctypes.data, a.shape[0], int(self.root), b.ctypes.data, b.shape[0], int(other.root), int(self.depth),
+                int(self.index_base))
+        call("och_pool_diff", *args, None, 0, C.byref(st))
+        out = None
+        if records:
+            out = np.zeros((st.n, 4), np.uint32)
+            if st.n:
+                call("och_pool_diff", *args, out.ctypes.data, st.n, C.byref(st))
+        return out, diff_stats_dict(st)
 
     # -- linearised node-pool file (SURVEY §8f row 1): a 64-byte header, then the
     # n x 8 little-endian uint32 slots exactly as och_gpu_pool_create takes them.

@@ -7,7 +7,8 @@
 // existing pool, is och_voxel_edit.h; the resident world, which keeps that
 // editor's store on the device between strokes, is och_world.h, and what
 // reads that world back on the device (at, a box to a grid, the exact box) is
-// och_world_read.h.  One translation unit: the headers are included here and
+// och_world_read.h; snapshots of that world, checkout and the diff of two
+// roots are och_world_history.h.  One translation unit: the headers are included here and
 // nowhere else.
 //
 // The reference builds its tree by recursive create_volume + per-voxel
@@ -40,6 +41,7 @@
 #include "och_voxel_edit.h"
 #include "och_world.h"
 #include "och_world_read.h"
+#include "och_world_history.h"
 
 namespace {
 

@@ -944,3 +944,81 @@ OCH_API int och_pool_read_box(const uint32_t *nodes, uint32_t n_nodes, uint32_t 
     if (r.over) return fail(OCH_E_INVALID, "och_pool_read_box: voxel id %u does not fit a u8 grid", r.over);
     return OCH_OK;
 }
+
+namespace {
+
+// och_pool_diff's walk: both trees at once, child digits ascending, so the
+// differing voxels come out in ascending Morton order.  An absent side reads
+// zeros all the way down; an all-zero node on one side is no node either.
+struct PoolDiffer {
+    const uint32_t *na, *nb;
+    int base;
+    bool same_array;     // both arguments are one array: equal ids are equal subtrees
+    uint32_t *out;       // null: count only
+    uint64_t n = 0, pairs = 0;
+    uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0, 0, 0};
+
+    // the position at height h with its corner at o; has_a / has_b: a node is there
+    void walk(bool has_a, uint32_t a, bool has_b, uint32_t b, int h, const uint32_t o[3])
+    {
+        static const uint32_t zeros[8] = {0};
+        const uint32_t *ca = has_a ? na + (size_t)(a - (uint32_t)base) * 8 : zeros;
+        const uint32_t *cb = has_b ? nb + (size_t)(b - (uint32_t)base) * 8 : zeros;
+        const uint32_t s = 1u << h;
+        ++pairs;
+        for (uint32_t k = 0; k < 8; ++k) {
+            const uint32_t wa = ca[k], wb = cb[k];
+            const uint32_t p[3] = {o[0] + (k & 1u) * s, o[1] + ((k >> 1) & 1u) * s, o[2] + ((k >> 2) & 1u) * s};
+            if (h) {
+                if ((!wa && !wb) || (same_array && wa == wb)) continue;
+                walk(wa != 0, wa, wb != 0, wb, h - 1, p);
+            } else if (wa != wb) {
+                if (out) {
+                    uint32_t *r = out + n * 4;
+                    r[0] = p[0], r[1] = p[1], r[2] = p[2], r[3] = wb;
+                }
+                for (int ax = 0; ax < 3; ++ax) {
+                    lo[ax] = std::min(lo[ax], p[ax]);
+                    hi[ax] = std::max(hi[ax], p[ax]);
+                }
+                ++n;
+            }
+        }
+    }
+};
+
+}  // namespace
+
+OCH_API int och_pool_diff(const uint32_t *nodes_a, uint32_t n_a, uint32_t root_a, const uint32_t *nodes_b, uint32_t n_b,
+                          uint32_t root_b, int depth, int index_base, void *records, uint64_t capacity, och_diff_stats *stats)
+{
+    if (!stats) return fail(OCH_E_INVALID, "och_pool_diff: stats is NULL");
+    if (!nodes_a || !nodes_b) return fail(OCH_E_INVALID, "och_pool_diff: NULL argument");
+    if (index_base != 0 && index_base != 1) return fail(OCH_E_INVALID, "och_pool_diff: index_base must be 0 or 1");
+    if (depth < 1 || depth > 21)
+        return fail(OCH_E_INVALID, "och_pool_diff: depth must be 1..21 (a record's Morton key has 3 * depth bits)");
+    if (const int vs = validate_pool(nodes_a, n_a, root_a, depth, index_base)) return vs;
+    if (const int vs = validate_pool(nodes_b, n_b, root_b, depth, index_base)) return vs;
+    const bool has_a = !(index_base == 1 && root_a == 0), has_b = !(index_base == 1 && root_b == 0);
+    const uint32_t origin[3] = {0, 0, 0};
+    PoolDiffer count{nodes_a, nodes_b, index_base, nodes_a == nodes_b, nullptr};
+    const bool equal_roots = count.same_array && has_a == has_b && (!has_a || root_a == root_b);
+    if ((has_a || has_b) && !equal_roots) count.walk(has_a, root_a, has_b, root_b, depth - 1, origin);
+    if (count.n >= (1ull << 31)) return fail(OCH_E_INVALID, "och_pool_diff: the differing voxels number 2^31 or more");
+    och_diff_stats ds;
+    std::memset(&ds, 0, sizeof ds);
+    ds.n = count.n;
+    ds.pairs = count.pairs;
+    for (int a = 0; a < 3 && count.n; ++a) {
+        ds.box_lo[a] = (int32_t)count.lo[a];
+        ds.box_hi[a] = (int32_t)count.hi[a] + 1;
+    }
+    *stats = ds;
+    if (!records || !count.n) return OCH_OK;
+    if (count.n > capacity)
+        return fail(OCH_E_CAPACITY, "och_pool_diff: %llu records, the buffer holds %llu", (unsigned long long)count.n,
+                    (unsigned long long)capacity);
+    PoolDiffer write{nodes_a, nodes_b, index_base, nodes_a == nodes_b, static_cast<uint32_t *>(records)};
+    write.walk(has_a, root_a, has_b, root_b, depth - 1, origin);
+    return OCH_OK;
+}

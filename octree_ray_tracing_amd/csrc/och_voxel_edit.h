@@ -314,13 +314,9 @@ int edit_upload(GpuScope &G, EditReach &R, const uint32_t *nodes, uint32_t n_nod
     return OCH_OK;
 }
 
-int edit_reach(hipStream_t st, EditReach &R, int depth)
+// The reach below depth 0, whose R.lv_cnt[0] distinct nodes stand in d_order with placed[] = 1.
+int edit_reach_levels(hipStream_t st, EditReach &R, int depth)
 {
-    if (!R.root) return OCH_OK;
-    const uint32_t first_tag = 1;
-    GPU_TRY(hipMemcpyAsync(R.d_order, &R.root, 4, hipMemcpyHostToDevice, st));
-    GPU_TRY(hipMemcpyAsync(R.d_placed + R.root, &first_tag, 4, hipMemcpyHostToDevice, st));
-    R.lv_cnt[0] = 1;
     for (int l = 0; l + 1 < depth && R.lv_cnt[l]; ++l) {
         uint32_t head[2] = {0, 0};
         R.lv_off[l + 1] = R.lv_off[l] + R.lv_cnt[l];
@@ -336,6 +332,16 @@ int edit_reach(hipStream_t st, EditReach &R, int depth)
     }
     for (int l = 0; l < depth; ++l) R.reach += R.lv_cnt[l];
     return OCH_OK;
+}
+
+int edit_reach(hipStream_t st, EditReach &R, int depth)
+{
+    if (!R.root) return OCH_OK;
+    const uint32_t first_tag = 1;
+    GPU_TRY(hipMemcpyAsync(R.d_order, &R.root, 4, hipMemcpyHostToDevice, st));
+    GPU_TRY(hipMemcpyAsync(R.d_placed + R.root, &first_tag, 4, hipMemcpyHostToDevice, st));
+    R.lv_cnt[0] = 1;
+    return edit_reach_levels(st, R, depth);
 }
 
 // Adopt, leaf level first: map[old id] = store id; W holds rows for the widest depth.

@@ -32,10 +32,12 @@
 // an admitted stroke can fail, and the answer depends on the records alone.
 //
 // Out of scope: worlds replicated across GPUs, frame groups and the sharded
-// paths; 0-based pools; undo or checkout of older roots (the store would allow
-// it); depth 22.  Reading the world back (at, a box to a grid, the exact box
-// after removals) is och_world_read.h, with what stays out of scope there.
+// paths; 0-based pools; depth 22.  Reading the world back (at, a box to a grid,
+// the exact box after removals) is och_world_read.h, with what stays out of
+// scope there; remembering earlier roots (snapshot, checkout, the diff of two
+// roots) is och_world_history.h.
 #pragma once
+#include <map>
 #include <memory>
 
 #include "och_host.h"
@@ -122,6 +124,14 @@ constexpr uint32_t kWorldCapLimit = (1u << 29) - 1;    // a pool's n_nodes + 1 s
 
 }  // namespace
 
+// What a snapshot keeps (och_world_history.h): a root of the append-only store
+// with its child mask and the world's box as they were at the call.
+struct WorldSnapshot {
+    uint32_t root = 0, root_mask = 0;
+    bool box_any = false;
+    int32_t box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
+};
+
 struct och_world {
     int device = 0, depth = 0;
     uint64_t id = 0;                  // process-unique, never reused: the mark on this world's pools
@@ -140,6 +150,17 @@ struct och_world {
     och::DevBuf<ulonglong2> d_lbox;   // the local boxes of ids [1, boxed) of generation lbox_generation
     uint32_t boxed = 1;
     uint64_t lbox_generation = 0;
+    // och_world_history.h: the live snapshots by handle (ascending; handles start at 1 and are never
+    // reused) and the diff's frontier, count and scan buffers for diff_cap pairs a level, kept
+    std::map<uint64_t, WorldSnapshot> snapshots;
+    uint64_t next_snapshot = 1;
+    // a checkout changed root and root_mask on the host only: the next stroke, which starts from the
+    // head's root word, uploads them first (from head_up, which outlives the copy)
+    bool head_stale = false;
+    uint32_t head_up[2] = {0, 0};
+    och::DevBuf<uint8_t> d_diff;
+    uint32_t diff_cap = 0;
+    size_t diff_temp_bytes = 0;
 
     uint32_t *head() const { return S.next; }
     ~och_world()
@@ -216,6 +237,12 @@ int world_edit(och_world &w, const void *records, uint32_t n, bool on_device)
     if ((uint64_t)w.used + rows_total > w.S.cap) return OCH_E_CAPACITY;
     static const uint32_t no_box[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0};
     uint32_t *head = w.head();
+    if (w.head_stale) {
+        w.head_up[0] = w.root;
+        w.head_up[1] = w.root_mask;
+        GPU_TRY(hipMemcpyAsync(head + kHeadRoot, w.head_up, sizeof w.head_up, hipMemcpyHostToDevice, st));
+        w.head_stale = false;
+    }
     GPU_TRY(hipMemcpyAsync(head + kHeadBox, no_box, sizeof no_box, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_world_box, blocks(m), dim3(256), 0, st, w.W.keys[0], w.W.words[0], m, head + kHeadBox);
     GPU_TRY(hipGetLastError());
@@ -357,6 +384,9 @@ int world_flush(och_world &w, och_gpu_pool *pool)
     phase("flush");
     return OCH_OK;
 }
+
+// och_world_history.h: the compaction of a world with live snapshots (what any of them reaches stays).
+int world_compact_history(och_world &w);
 
 int world_usable(const och_world *w, const char *who)
 {
@@ -507,6 +537,6 @@ OCH_API int och_world_compact(och_world *w)
     och::DeviceGuard g(w->device);
     if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
     // the old store is replaced only once the new one is whole: a failure leaves the world as it was
-    const int st = world_compact(*w);
+    const int st = w->snapshots.empty() ? world_compact(*w) : world_compact_history(*w);
     return st == OCH_OK || st == OCH_E_INVALID ? st : report_build(st, "och_world", "allocation failed");
 }

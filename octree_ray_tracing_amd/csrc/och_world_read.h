@@ -25,8 +25,8 @@
 // the array then belongs to another generation and the next tighten starts over.
 //
 // Out of scope: queries on an och_gpu_pool; asynchronous queries on a caller's
-// stream; reading older roots; run-length or sparse output; shrinking the box
-// inside a stroke.
+// stream; run-length or sparse output; shrinking the box inside a stroke.  An
+// older root is read by checking its snapshot out first (och_world_history.h).
 #pragma once
 #include "och_world.h"
 

@@ -13,14 +13,16 @@ import numpy as np
 
 from . import _lib
 from ._lib import HostPool, OchError, call
-from .builder import VOXELS_GRID_U8, NodePool, _capacity, _host_records, _read_box_args
+from .builder import VOXELS_GRID_U8, NodePool, _capacity, _host_records, _read_box_args, diff_stats_dict
 from .tracer import HOctree
 
 
 class World:
     """A 1-based DAG resident on one GPU: edit() applies a record list as edit_voxels would, make_pool()
     and flush() show it, download() gives the canonical pool, compact() drops what strokes left behind;
-    at() and read_box() ask it what it holds without a download, tighten() makes its box exact."""
+    at() and read_box() ask it what it holds without a download, tighten() makes its box exact;
+    snapshot(), checkout() and release() remember and restore earlier states (UndoStack, below), diff()
+    gives what changed between two of them."""
 
     def __init__(self, tree, capacity: int | None = None, device: int = -1):
         """tree is a NodePool with index_base 1 or a (nodes, root, depth) tuple in that form, as edit_voxels
@@ -192,3 +194,117 @@ class World:
         """Drop what the root no longer reaches (och_world_compact): generation + 1, every pool is
         rewritten whole by its next flush."""
         call("och_world_compact", self._open("compact"))
+
+    # -- history (och_world_snapshot / _checkout / _release / _snapshots / _diff)
+
+    @staticmethod
+    def _handle(s, who: str) -> int:
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)):
+            raise ValueError(f"World.{who}: a snapshot is an integer handle, not {type(s).__name__}")
+        if not 0 <= int(s) < 1 << 64:
+            raise ValueError(f"World.{who}: handle {s} outside uint64")
+        return int(s)
+
+    def snapshot(self) -> int:
+        """Remember the current root: a handle (1, 2, ... per world, never reused) that checkout() and
+        diff() take, live until release() or close().  O(1); compact() keeps what live snapshots reach."""
+        s = C.c_uint64()
+        call("och_world_snapshot", self._open("snapshot"), C.byref(s))
+        return s.value
+
+    def checkout(self, s: int) -> None:
+        """Make snapshot s the current state again (undo / redo): root, mask and the box the world had
+        then.  O(1), nothing is launched; flush() publishes it.  Strokes afterwards branch off."""
+        h = self._open("checkout")
+        call("och_world_checkout", h, self._handle(s, "checkout"))
+
+    def release(self, s: int) -> None:
+        """Forget snapshot s; what only it reached goes with the next compact()."""
+        h = self._open("release")
+        call("och_world_release", h, self._handle(s, "release"))
+
+    def snapshots(self) -> list:
+        """The live handles in ascending order."""
+        h = self._open("snapshots")
+        n = _lib._u32()
+        call("och_world_snapshots", h, None, 0, C.byref(n))
+        ids = (C.c_uint64 * max(n.value, 1))()
+        call("och_world_snapshots", h, ids, n.value, C.byref(n))
+        return [int(v) for v in ids[:n.value]]
+
+    def diff(self, a: int, b: int = 0, device: bool = False, records: bool = True):
+        """The voxels that differ between snapshots a and b (0: the current state), as (records, stats)
+        (och_world_diff): NodePool.diff of the two downloads without a download, at a cost that follows
+        the change.  records is an (n, 4) np.uint32 array of (x, y, z, id under b) in ascending Morton
+        order, id 0 where the voxel is gone -- what edit() takes to turn a's content into b's; with
+        device=True an int32 CUDA tensor on the world's device holding the same bits; with records=False
+        None.  stats is {"n", "pairs", "box_lo", "box_hi"}.  Complete on return."""
+        h = self._open("diff")
+        a, b = self._handle(a, "diff"), self._handle(b, "diff")
+        st = _lib.DiffStats()
+        call("och_world_diff", h, a, b, None, 0, 0, C.byref(st))      # the summary sizes the output
+        if not records:
+            return None, diff_stats_dict(st)
+        n = int(st.n)
+        if device:
+            import torch
+
+            dev = torch.device("cuda", self.device)
+            out = torch.empty((n, 4), dtype=torch.int32, device=dev)
+            if n:
+                torch.cuda.current_stream(dev).synchronize()              # the allocation's stream before the world's
+                call("och_world_diff", h, a, b, out.data_ptr(), n, 1, C.byref(st))
+            return out, diff_stats_dict(st)
+        out = np.zeros((n, 4), np.uint32)
+        if n:
+            call("och_world_diff", h, a, b, out.ctypes.data, n, 0, C.byref(st))
+        return out, diff_stats_dict(st)
+
+
+class UndoStack:
+    """Undo and redo over a World's snapshots.  The stack snapshots the world as it is when made;
+    push() after every stroke.  undo() and redo() are checkouts (O(1); flush() shows them) and return
+    whether they moved.  A push after an undo releases the abandoned branch; beyond `limit` entries
+    the oldest is released."""
+
+    def __init__(self, world: World, limit: int = 64):
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 2:
+            raise ValueError(f"UndoStack: limit is an integer of at least 2 (a state to go back to), not {limit!r}")
+        self.world, self.limit = world, int(limit)
+        self._entries = [world.snapshot()]
+        self._at = 0
+
+    @property
+    def entries(self) -> list:
+        """The stack's handles, oldest first."""
+        return list(self._entries)
+
+    @property
+    def current(self) -> int:
+        return self._entries[self._at]
+
+    def push(self) -> int:
+        """Remember the world as it is now, after a stroke; the new handle."""
+        s = self.world.snapshot()
+        for dead in self._entries[self._at + 1:]:
+            self.world.release(dead)
+        del self._entries[self._at + 1:]
+        self._entries.append(s)
+        while len(self._entries) > self.limit:
+            self.world.release(self._entries.pop(0))
+        self._at = len(self._entries) - 1
+        return s
+
+    def undo(self) -> bool:
+        if self._at == 0:
+            return False
+        self.world.checkout(self._entries[self._at - 1])
+        self._at -= 1
+        return True
+
+    def redo(self) -> bool:
+        if self._at + 1 >= len(self._entries):
+            return False
+        self.world.checkout(self._entries[self._at + 1])
+        self._at += 1
+        return True
