@@ -5,11 +5,12 @@
 // builder, which builds the same DAG from a caller's voxels, is
 // och_voxel_build.h; the batch editor, which applies a list of edits to an
 // existing pool, is och_voxel_edit.h; the resident world, which keeps that
-// editor's store on the device between strokes, is och_world.h, and what
-// reads that world back on the device (at, a box to a grid, the exact box) is
-// och_world_read.h; snapshots of that world, checkout and the diff of two
-// roots are och_world_history.h.  One translation unit: the headers are included here and
-// nowhere else.
+// editor's store on the device between strokes, is och_world.h, with what all
+// three world headers share (the state record, the box convention, the entry
+// wrapper, the staging and read-back steps); what reads that world back on the
+// device (at, a box to a grid, the exact box) is och_world_read.h; snapshots
+// of that world, checkout and the diff of two roots are och_world_history.h.
+// One translation unit: the headers are included here and nowhere else.
 //
 // The reference builds its tree by recursive create_volume + per-voxel
 // h_octree::set edits (ORT/test_och_h_octree.cpp:651-695, :767-787;

@@ -299,19 +299,30 @@ struct EditWork {
     uint32_t rows_cap = 0;
 };
 
-int edit_upload(GpuScope &G, EditReach &R, const uint32_t *nodes, uint32_t n_nodes, uint32_t root)
+// The reach's and the adoption's arrays for a pool of n_nodes, nothing placed
+// yet.  `upload`: the caller's host pool, which gets its device copy here;
+// nullptr: R.d_pool is set already (a world's store).  The pool's allocation
+// comes first and its copy between the allocations and the clears: the order
+// och_edit_voxels always had (every hipMalloc ahead of the large pageable copy).
+int edit_reach_arrays(GpuScope &G, EditReach &R, uint32_t n_nodes, uint32_t root, const uint32_t *upload)
 {
     const hipStream_t st = G.st;
     R.n_nodes = n_nodes;
     R.root = root;
-    if (!G.alloc(&R.d_pool, (size_t)n_nodes * 32) || !G.alloc(&R.d_placed, ((size_t)n_nodes + 1) * 4) ||
+    if ((upload && !G.alloc(&R.d_pool, (size_t)n_nodes * 32)) || !G.alloc(&R.d_placed, ((size_t)n_nodes + 1) * 4) ||
         !G.alloc(&R.d_map, ((size_t)n_nodes + 1) * 4) || !G.alloc(&R.d_order, (size_t)n_nodes * 4) || !G.alloc(&R.d_head, 8))
         return OCH_E_NOMEM;
-    if (n_nodes) GPU_TRY(hipMemcpyAsync(R.d_pool, nodes, (size_t)n_nodes * 32, hipMemcpyHostToDevice, st));
+    if (upload && n_nodes) GPU_TRY(hipMemcpyAsync(R.d_pool, upload, (size_t)n_nodes * 32, hipMemcpyHostToDevice, st));
     GPU_TRY(hipMemsetAsync(R.d_placed, 0, ((size_t)n_nodes + 1) * 4, st));
     GPU_TRY(hipMemsetAsync(R.d_map, 0, 4, st));   // map[0]: the adopted root of a world without voxels
     GPU_TRY(hipMemsetAsync(R.d_head, 0, 8, st));
     return OCH_OK;
+}
+
+int edit_upload(GpuScope &G, EditReach &R, const uint32_t *nodes, uint32_t n_nodes, uint32_t root)
+{
+    static const uint32_t none[8] = {0};   // a pool of no nodes still names one to upload from
+    return edit_reach_arrays(G, R, n_nodes, root, nodes ? nodes : none);
 }
 
 // The reach below depth 0, whose R.lv_cnt[0] distinct nodes stand in d_order with placed[] = 1.

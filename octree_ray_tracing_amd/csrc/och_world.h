@@ -31,6 +31,19 @@
 // own tree: a row allocates at most one id (its claimant's), so no intern of
 // an admitted stroke can fail, and the answer depends on the records alone.
 //
+// Said once, here, for this file, och_world_read.h and och_world_history.h:
+//   the state        -- WorldSnapshot (root, child mask, box): och_world::now,
+//                       copied by a snapshot, assigned by a checkout.
+//   the box          -- six words on the device (kNoBox, box_reduce), lo / hi
+//                       exclusive on the host (WorldBox, box_decode, box_union).
+//   an entry         -- world_call: the usable check, the world's device, the
+//                       body, its status to the caller (who reports what, and
+//                       when a HIP failure breaks the world).
+//   a host array     -- world_stage (its place on the device) and
+//                       world_read_back (queue, synchronise, then look).
+//   the rest         -- row_mask, WorldHead / world_read_head, world_install
+//                       (a compaction's end), world_phase (the trace's timer).
+//
 // Out of scope: worlds replicated across GPUs, frame groups and the sharded
 // paths; 0-based pools; depth 22.  Reading the world back (at, a box to a grid,
 // the exact box after removals) is och_world_read.h, with what stays out of
@@ -50,30 +63,39 @@ namespace {
 // and its child mask, and the stroke's box (min x y z, max x y z, inclusive).
 constexpr int kHeadRoot = 8, kHeadBox = 16, kHeadWords = 22;
 
+// The child mask of a row: bit k set where child word k is not 0.
+__device__ inline uint32_t row_mask(const uint32_t *__restrict__ row)
+{
+    const uint4 *rec = reinterpret_cast<const uint4 *>(row);
+    const uint4 a = rec[0], b = rec[1];
+    return (uint32_t)(a.x != 0) | (uint32_t)(a.y != 0) << 1 | (uint32_t)(a.z != 0) << 2 | (uint32_t)(a.w != 0) << 3 |
+           (uint32_t)(b.x != 0) << 4 | (uint32_t)(b.y != 0) << 5 | (uint32_t)(b.z != 0) << 6 | (uint32_t)(b.w != 0) << 7;
+}
+
 // The stroke's result into the head, for one read-back with the id counter.
 __global__ __launch_bounds__(64) void k_world_root(GpuStore S, const uint32_t *__restrict__ new_root, uint32_t *__restrict__ head)
 {
     if (blockIdx.x || threadIdx.x) return;
     const uint32_t r = *new_root;
-    uint32_t mask = 0;
-    if (r && r < S.cap)
-        for (uint32_t k = 0; k < 8; ++k) mask |= (uint32_t)(S.nodes[(size_t)r * 8 + k] != 0) << k;
     head[kHeadRoot] = r;
-    head[kHeadRoot + 1] = mask;
+    head[kHeadRoot + 1] = r && r < S.cap ? row_mask(S.nodes + (size_t)r * 8) : 0u;
 }
 
-// The box of the stroke's voxels, from its m unique keys and their ids (id 0
-// is a removal: no voxel): a wavefront's minima and maxima in registers, then
-// six atomics per wavefront that holds a voxel.  box: 0xFFFFFFFF x 3, 0 x 3 before.
-__global__ __launch_bounds__(256) void k_world_box(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ words,
-                                                   uint32_t m, uint32_t *__restrict__ box)
+// A box on the device: six words, min x y z then max x y z, inclusive; kNoBox
+// while it holds no voxel.  box_decode (below) is the host's reading of it.
+constexpr uint32_t kNoBox[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0};
+
+// A wavefront's voxels into `box`, this lane's at Morton key `key()` if it
+// `has` one: the minima and maxima in registers, then six atomics by the first
+// lane of a wavefront that holds a voxel (`some`: the caller knows that it does).
+template <class Key>
+__device__ inline void box_reduce(bool has, Key key, bool some, uint32_t *__restrict__ box)
 {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0, 0, 0};
-    if (i < m && words[i]) {
-        const uint64_t key = keys[i];
+    uint32_t lo[3] = {kNoBox[0], kNoBox[1], kNoBox[2]}, hi[3] = {kNoBox[3], kNoBox[4], kNoBox[5]};
+    if (has) {
+        const uint64_t k = key();
 #pragma unroll
-        for (int a = 0; a < 3; ++a) lo[a] = hi[a] = compact3(key >> a);
+        for (int a = 0; a < 3; ++a) lo[a] = hi[a] = compact3(k >> a);
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a)
@@ -82,13 +104,24 @@ __global__ __launch_bounds__(256) void k_world_box(const uint64_t *__restrict__ 
             lo[a] = min(lo[a], (uint32_t)__shfl_xor(lo[a], o));
             hi[a] = max(hi[a], (uint32_t)__shfl_xor(hi[a], o));
         }
-    if ((threadIdx.x & 63u) == 0 && lo[0] != 0xFFFFFFFFu) {
+    if ((threadIdx.x & 63u) == 0 && (some || lo[0] != kNoBox[0])) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             atomicMin(box + a, lo[a]);
             atomicMax(box + 3 + a, hi[a]);
         }
     }
+}
+
+// The box of the stroke's voxels, from its m unique keys and their ids (id 0
+// is a removal: no voxel).  box: kNoBox before.
+__global__ __launch_bounds__(256) void k_world_box(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ words,
+                                                   uint32_t m, uint32_t *__restrict__ box)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool has = i < m && words[i];
+    const uint64_t key = has ? keys[i] : 0ull;   // loaded here, not in the helper: the instructions the kernel always had
+    box_reduce(has, [&] { return key; }, false, box);
 }
 
 // The packed layout numbered like the store, ids [lo, hi): thread q is child
@@ -101,14 +134,7 @@ __global__ __launch_bounds__(256) void k_world_pack(GpuStore S, uint32_t lo, uin
     const uint32_t id = lo + (uint32_t)(q >> 3);
     const size_t at = (size_t)id * 8 + (q & 7u);
     uint32_t w = S.nodes[at];
-    if (w && w < S.cap && S.level[id] != 0) {
-        const uint4 *rec = reinterpret_cast<const uint4 *>(S.nodes + (size_t)w * 8);
-        const uint4 a = rec[0], b = rec[1];
-        const uint32_t mask = (uint32_t)(a.x != 0) | (uint32_t)(a.y != 0) << 1 | (uint32_t)(a.z != 0) << 2 |
-                              (uint32_t)(a.w != 0) << 3 | (uint32_t)(b.x != 0) << 4 | (uint32_t)(b.y != 0) << 5 |
-                              (uint32_t)(b.z != 0) << 6 | (uint32_t)(b.w != 0) << 7;
-        w |= mask << 24;
-    }
+    if (w && w < S.cap && S.level[id] != 0) w |= row_mask(S.nodes + (size_t)w * 8) << 24;
     packed[at] = w;
 }
 
@@ -124,12 +150,18 @@ constexpr uint32_t kWorldCapLimit = (1u << 29) - 1;    // a pool's n_nodes + 1 s
 
 }  // namespace
 
-// What a snapshot keeps (och_world_history.h): a root of the append-only store
-// with its child mask and the world's box as they were at the call.
+// A box as the host keeps it: lo inclusive, hi exclusive; all 0 without a voxel.
+struct WorldBox {
+    bool any = false;
+    int32_t lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+};
+
+// A state of the world: a root of the append-only store with its child mask
+// and the box of its voxels.  The world's current one (och_world::now), and
+// what a snapshot keeps of it (och_world_history.h): a copy.
 struct WorldSnapshot {
     uint32_t root = 0, root_mask = 0;
-    bool box_any = false;
-    int32_t box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
+    WorldBox box;
 };
 
 struct och_world {
@@ -141,10 +173,9 @@ struct och_world {
     GpuStore S{};
     EditWork W;                       // for W.n_cap records and as many rows, grown on demand and kept
     void *d_upload = nullptr;         // W.n_cap host records' way to the device
-    uint32_t used = 1, root = 0, root_mask = 0;
+    uint32_t used = 1;
+    WorldSnapshot now;                // the current state
     uint64_t strokes = 0, generation = 0;
-    bool box_any = false;
-    int32_t box_lo[3] = {0, 0, 0}, box_hi[3] = {0, 0, 0};
     // och_world_read.h: freed after the destructor's body, the stream gone by then (hipFree waits for the device)
     och::DevBuf<uint8_t> d_read;      // a host grid's, or host coordinates' and ids', way through the device
     och::DevBuf<ulonglong2> d_lbox;   // the local boxes of ids [1, boxed) of generation lbox_generation
@@ -154,8 +185,8 @@ struct och_world {
     // reused) and the diff's frontier, count and scan buffers for diff_cap pairs a level, kept
     std::map<uint64_t, WorldSnapshot> snapshots;
     uint64_t next_snapshot = 1;
-    // a checkout changed root and root_mask on the host only: the next stroke, which starts from the
-    // head's root word, uploads them first (from head_up, which outlives the copy)
+    // a checkout changed now.root and now.root_mask on the host only: the next stroke, which starts from
+    // the head's root word, uploads them first (from head_up, which outlives the copy)
     bool head_stale = false;
     uint32_t head_up[2] = {0, 0};
     och::DevBuf<uint8_t> d_diff;
@@ -173,19 +204,74 @@ struct och_world {
 
 namespace {
 
-// The head's words after the stroke's (or the adoption's) last dispatch: used,
-// root and mask into the world; synchronises st.
-int world_read_head(och_world &w, const GpuStore &S, uint32_t *used, uint32_t *root, uint32_t *mask, uint32_t *box)
+PhaseTimer world_phase(const och_world &w) { return PhaseTimer{"world ", 4, w.st}; }
+
+// The host's reading of a device box.
+WorldBox box_decode(const uint32_t box[6])
+{
+    WorldBox b;
+    b.any = box[0] != kNoBox[0];
+    for (int a = 0; a < 3 && b.any; ++a) {
+        b.lo[a] = (int32_t)box[a];
+        b.hi[a] = (int32_t)box[3 + a] + 1;
+    }
+    return b;
+}
+
+void box_union(WorldBox &into, const WorldBox &b)
+{
+    if (!b.any) return;
+    for (int a = 0; a < 3; ++a) {
+        into.lo[a] = into.any ? std::min(into.lo[a], b.lo[a]) : b.lo[a];
+        into.hi[a] = into.any ? std::max(into.hi[a], b.hi[a]) : b.hi[a];
+    }
+    into.any = true;
+}
+
+// Where a call's array of `bytes` stands on the device: a device array is its
+// own place, a host array's is the world's staging buffer, grown when it has
+// to be (nullptr: no memory for it).
+void *world_stage(och_world &w, const void *array, size_t bytes, bool on_device)
+{
+    if (on_device) return const_cast<void *>(array);
+    return w.d_read.reserve(bytes) == hipSuccess ? w.d_read.d : nullptr;
+}
+
+// A copy to the host; one of no bytes is left out.
+struct ReadBack {
+    void *to;
+    const void *from;
+    size_t bytes;
+};
+
+// Queue the copies, then synchronise the stream whatever they returned: the
+// destinations may be the caller's frame's, and nothing writes there once it
+// has gone.  Fails if a copy or the synchronise failed.
+int world_read_back(och_world &w, std::initializer_list<ReadBack> copies)
+{
+    hipError_t ce = hipSuccess;
+    for (const ReadBack &c : copies)
+        if (ce == hipSuccess && c.bytes) ce = hipMemcpyAsync(c.to, c.from, c.bytes, hipMemcpyDeviceToHost, w.st);
+    const hipError_t se = hipStreamSynchronize(w.st);
+    return ce == hipSuccess && se == hipSuccess ? OCH_OK : OCH_E_HIP;
+}
+
+// A store's head after the last dispatch on it: the ids in use, the root and
+// its mask, the device box.
+struct WorldHead {
+    uint32_t used = 0, root = 0, mask = 0, box[6] = {0};
+};
+
+int world_read_head(och_world &w, const GpuStore &S, WorldHead *H)
 {
     uint32_t h[kHeadWords] = {0};
-    GPU_TRY(hipMemcpyAsync(h, S.next, sizeof h, hipMemcpyDeviceToHost, w.st));
-    GPU_TRY(hipStreamSynchronize(w.st));
+    if (const int rs = world_read_back(w, {{h, S.next, sizeof h}})) return rs;
     if (h[1] & 4u) return och::report(OCH_E_HIP, "och_world: a row outside its level");
     if (h[1]) return och::report(OCH_E_HIP, "och_world: the store overflowed after its capacity check");
-    *used = std::min(h[0], S.cap);
-    *root = h[kHeadRoot];
-    *mask = h[kHeadRoot + 1];
-    if (box) std::memcpy(box, h + kHeadBox, 24);
+    H->used = std::min(h[0], S.cap);
+    H->root = h[kHeadRoot];
+    H->mask = h[kHeadRoot + 1];
+    std::memcpy(H->box, h + kHeadBox, sizeof H->box);
     return OCH_OK;
 }
 
@@ -217,7 +303,7 @@ int world_reserve(och_world &w, uint32_t n)
 int world_edit(och_world &w, const void *records, uint32_t n, bool on_device)
 {
     const hipStream_t st = w.st;
-    PhaseTimer phase{"world ", 4, st};
+    PhaseTimer phase = world_phase(w);
     if (const int rs = world_reserve(w, n)) return rs;
     const void *d_in = records;
     if (!on_device) {
@@ -234,46 +320,40 @@ int world_edit(och_world &w, const void *records, uint32_t n, bool on_device)
         return OCH_OK;
     }
     // before anything is interned: see the head of this file
-    if ((uint64_t)w.used + rows_total > w.S.cap) return OCH_E_CAPACITY;
-    static const uint32_t no_box[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0};
+    if ((uint64_t)w.used + rows_total > w.S.cap) return report_build(OCH_E_CAPACITY, "och_world", "");
     uint32_t *head = w.head();
     if (w.head_stale) {
-        w.head_up[0] = w.root;
-        w.head_up[1] = w.root_mask;
+        w.head_up[0] = w.now.root;
+        w.head_up[1] = w.now.root_mask;
         GPU_TRY(hipMemcpyAsync(head + kHeadRoot, w.head_up, sizeof w.head_up, hipMemcpyHostToDevice, st));
         w.head_stale = false;
     }
-    GPU_TRY(hipMemcpyAsync(head + kHeadBox, no_box, sizeof no_box, hipMemcpyHostToDevice, st));
+    GPU_TRY(hipMemcpyAsync(head + kHeadBox, kNoBox, sizeof kNoBox, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_world_box, blocks(m), dim3(256), 0, st, w.W.keys[0], w.W.words[0], m, head + kHeadBox);
     GPU_TRY(hipGetLastError());
     const uint32_t *d_new = nullptr;
     if (const int ls = edit_levels(st, w.W, w.S, head + kHeadRoot, m, counts, w.depth, &d_new)) return ls;
     hipLaunchKernelGGL(k_world_root, dim3(1), dim3(64), 0, st, w.S, d_new, head);
     GPU_TRY(hipGetLastError());
-    uint32_t used = 0, root = 0, mask = 0, box[6];
-    if (const int hs = world_read_head(w, w.S, &used, &root, &mask, box)) return hs;
+    WorldHead H;
+    if (const int hs = world_read_head(w, w.S, &H)) return hs;
     if (!phase("levels")) return OCH_E_HIP;
     if (phase.on)
-        std::fprintf(stderr, "[och_build] world: %u records, %u keys, %u new ids, %u of %u used\n", n, m, used - w.used, used,
+        std::fprintf(stderr, "[och_build] world: %u records, %u keys, %u new ids, %u of %u used\n", n, m, H.used - w.used, H.used,
                      w.S.cap);
-    w.used = used;
-    w.root = root;
-    w.root_mask = mask;
-    if (box[0] != 0xFFFFFFFFu)
-        for (int a = 0; a < 3; ++a) {
-            w.box_lo[a] = w.box_any ? std::min(w.box_lo[a], (int32_t)box[a]) : (int32_t)box[a];
-            w.box_hi[a] = w.box_any ? std::max(w.box_hi[a], (int32_t)box[3 + a] + 1) : (int32_t)box[3 + a] + 1;
-        }
-    w.box_any = w.box_any || box[0] != 0xFFFFFFFFu;
+    w.used = H.used;
+    w.now.root = H.root;
+    w.now.root_mask = H.mask;
+    box_union(w.now.box, box_decode(H.box));
     ++w.strokes;
     return OCH_OK;
 }
 
 // A fresh store of `cap` ids holding the 1-based pool R names (reached, on the
 // device), in a scope of its own on the world's stream; T takes the adoption's
-// rows.  used / root / mask: the store's after the adoption.
+// rows.  H: the store's head after the adoption.
 int world_adopt(och_world &w, GpuScope &T, const EditReach &R, uint32_t cap, std::unique_ptr<GpuScope> &scope, GpuStore &S,
-                uint32_t *used, uint32_t *root, uint32_t *mask)
+                WorldHead *H)
 {
     scope.reset(new GpuScope(w.st));
     if (const int cs = gpu_store_create(*scope, cap, false, S)) return cs;
@@ -282,13 +362,27 @@ int world_adopt(och_world &w, GpuScope &T, const EditReach &R, uint32_t cap, std
     if (const int as = edit_adopt(w.st, R, S, TW, w.depth)) return as;
     hipLaunchKernelGGL(k_world_root, dim3(1), dim3(64), 0, w.st, S, R.d_map + R.root, S.next);
     GPU_TRY(hipGetLastError());
-    return world_read_head(w, S, used, root, mask, nullptr);
+    return world_read_head(w, S, H);
+}
+
+// A compaction's end: the freshly adopted store becomes the world's.  Nothing
+// of the world has changed before; the old store goes with `scope`, after a
+// synchronise of the stream.
+void world_install(och_world &w, std::unique_ptr<GpuScope> &scope, const GpuStore &S, const WorldHead &H)
+{
+    w.store_scope.swap(scope);
+    w.S = S;
+    w.used = H.used;
+    w.now.root = H.root;
+    w.now.root_mask = H.mask;
+    w.head_stale = false;   // the new store's head holds the adopted root (k_world_root)
+    ++w.generation;
 }
 
 int world_create(och_world &w, const uint32_t *nodes, uint32_t n_nodes, uint32_t root, uint32_t capacity)
 {
     GPU_TRY(hipStreamCreateWithFlags(&w.st, hipStreamNonBlocking));
-    PhaseTimer phase{"world ", 4, w.st};
+    PhaseTimer phase = world_phase(w);
     GpuScope T(w.st);
     EditReach R;
     if (const int us = edit_upload(T, R, nodes, n_nodes, root)) return us;
@@ -297,22 +391,26 @@ int world_create(och_world &w, const uint32_t *nodes, uint32_t n_nodes, uint32_t
     const uint64_t cap = capacity ? capacity : 2 * R.reach + 64ull * (uint64_t)w.depth;
     if (cap < R.reach + 1) return OCH_E_CAPACITY;
     if (cap >= kWorldCapLimit) return och::report(OCH_E_INVALID, "och_world_create: a capacity of 2^29 - 1 ids or more");
-    if (const int as = world_adopt(w, T, R, (uint32_t)cap, w.store_scope, w.S, &w.used, &w.root, &w.root_mask)) return as;
+    WorldHead H;
+    if (const int as = world_adopt(w, T, R, (uint32_t)cap, w.store_scope, w.S, &H)) return as;
     if (!phase("adopt")) return OCH_E_HIP;
-    w.box_any = och::occupied_box(nodes, n_nodes, root, w.depth, 1, w.box_lo, w.box_hi);
+    w.used = H.used;
+    w.now.root = H.root;
+    w.now.root_mask = H.mask;
+    w.now.box.any = och::occupied_box(nodes, n_nodes, root, w.depth, 1, w.now.box.lo, w.now.box.hi);
     phase("box");
     return OCH_OK;
 }
 
 int world_compact(och_world &w)
 {
-    PhaseTimer phase{"world ", 4, w.st};
+    PhaseTimer phase = world_phase(w);
     GpuScope T(w.st);
     EditReach R;
-    if (w.root) {
+    if (w.now.root) {
         DevicePool dev;
         uint32_t n = 0;
-        if (const int rs = renumber_gpu(w.S, w.used, w.root, w.depth, T, nullptr, &n, false, &dev)) return rs;
+        if (const int rs = renumber_gpu(w.S, w.used, w.now.root, w.depth, T, nullptr, &n, false, &dev)) return rs;
         // the renumbered pool's depths are id ranges: lv_cnt as the reach would give them, the ids as a list
         R.d_pool = const_cast<uint32_t *>(dev.nodes);
         R.n_nodes = n;
@@ -335,16 +433,11 @@ int world_compact(och_world &w)
     }
     std::unique_ptr<GpuScope> scope;
     GpuStore S;
-    uint32_t used = 0, root = 0, mask = 0;
-    if (const int as = world_adopt(w, T, R, w.S.cap, scope, S, &used, &root, &mask)) return as;
+    WorldHead H;
+    if (const int as = world_adopt(w, T, R, w.S.cap, scope, S, &H)) return as;
     if (!phase("adopt")) return OCH_E_HIP;
-    if (phase.on) std::fprintf(stderr, "[och_build] world: compacted %u ids to %u\n", w.used, used);
-    w.store_scope.swap(scope);   // the old store goes with `scope`, after a synchronise of the stream
-    w.S = S;
-    w.used = used;
-    w.root = root;
-    w.root_mask = mask;
-    ++w.generation;
+    if (phase.on) std::fprintf(stderr, "[och_build] world: compacted %u ids to %u\n", w.used, H.used);
+    world_install(w, scope, S, H);
     return OCH_OK;
 }
 
@@ -358,7 +451,7 @@ int world_flush(och_world &w, och_gpu_pool *pool)
     if (whole && *v.published)
         if (const int ds = och::pool_drain(pool)) return ds;
     const uint32_t lo = whole ? 0u : *v.published, hi = w.used;
-    PhaseTimer phase{"world ", 4, w.st};
+    PhaseTimer phase = world_phase(w);
     int st = OCH_OK;
     if (hi > lo) {
         if (hipMemcpyAsync(v.raw + (size_t)lo * 8, w.S.nodes + (size_t)lo * 8, (size_t)(hi - lo) * 32, hipMemcpyDeviceToDevice,
@@ -372,8 +465,8 @@ int world_flush(och_world &w, och_gpu_pool *pool)
     // complete on return: the launch that takes the new root starts after its nodes are there
     if (st == OCH_OK && hipStreamSynchronize(w.st) != hipSuccess) st = OCH_E_HIP;
     if (st == OCH_OK)
-        st = och::pool_commit(pool, w.root, w.root ? w.root | w.root_mask << 24 : 0u, v.packed != nullptr, 0,
-                              w.box_any ? w.box_lo : nullptr, w.box_any ? w.box_hi : nullptr);
+        st = och::pool_commit(pool, w.now.root, w.now.root ? w.now.root | w.now.root_mask << 24 : 0u, v.packed != nullptr, 0,
+                              w.now.box.any ? w.now.box.lo : nullptr, w.now.box.any ? w.now.box.hi : nullptr);
     if (st != OCH_OK) {
         // below `published` nothing was written, so the pool still shows its last flush -- unless it was being rewritten
         if (whole && *v.published) (void)och::pool_mark_torn(pool);
@@ -396,12 +489,26 @@ int world_usable(const och_world *w, const char *who)
     return OCH_OK;
 }
 
-// A world call's status: reported, and a HIP failure breaks the world.
-int world_status(och_world *w, int st)
+constexpr bool kBreaks = true, kStays = false;       // what a HIP failure does to the world
+constexpr bool kPoolTexts = true, kOwnTexts = false;
+
+// An entry that works on the device, around its body: the usable check, the
+// world's device current, then the body's status.  HIP, NOMEM and NODEV come
+// back bare and get their text here, under `report_as`; every other failure
+// was reported where it was found.  kBreaks: the entry writes the store, so a
+// HIP failure leaves it unknown and the world refuses every later call; an
+// entry that only reads, or builds beside the store, leaves the world usable.
+// kPoolTexts (flush): only HIP is bare, the rest is the pool layer's, reported.
+template <class Body>
+int world_call(och_world *w, const char *entry, const char *report_as, bool breaks, bool pool_texts, Body body)
 {
-    if (st == OCH_E_HIP) w->broken = true;
-    if (st == OCH_OK || st == OCH_E_INVALID) return st;   // INVALID is reported where it is found
-    return report_build(st, "och_world", "allocation failed");
+    if (const int us = world_usable(w, entry)) return us;
+    och::DeviceGuard g(w->device);
+    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
+    const int st = body();
+    if (st == OCH_E_HIP && breaks) w->broken = true;
+    const bool bare = st == OCH_E_HIP || (!pool_texts && (st == OCH_E_NOMEM || st == OCH_E_NODEV));
+    return bare ? report_build(st, report_as, "allocation failed") : st;
 }
 
 }  // namespace
@@ -450,15 +557,13 @@ OCH_API int och_world_info(const och_world *w, och_world_stats *info)
     if (const int us = world_usable(w, "och_world_info")) return us;
     info->capacity = w->S.cap;
     info->used = w->used;
-    info->root = w->root;
+    info->root = w->now.root;
     info->depth = w->depth;
     info->device = w->device;
     info->strokes = w->strokes;
     info->generation = w->generation;
-    for (int a = 0; a < 3; ++a) {
-        info->box_lo[a] = w->box_any ? w->box_lo[a] : 0;
-        info->box_hi[a] = w->box_any ? w->box_hi[a] : 0;
-    }
+    std::memcpy(info->box_lo, w->now.box.lo, sizeof info->box_lo);   // all 0 without a voxel
+    std::memcpy(info->box_hi, w->now.box.hi, sizeof info->box_hi);
     return OCH_OK;
 }
 
@@ -466,77 +571,67 @@ OCH_API int och_world_edit(och_world *w, const void *records, uint64_t n, int on
 {
     if (n >= (1ull << 31)) return och::report(OCH_E_INVALID, "och_world_edit: a list holds fewer than 2^31 records");
     if (!records && n) return och::report(OCH_E_INVALID, "och_world_edit: records is null");
-    if (const int us = world_usable(w, "och_world_edit")) return us;
-    if (!n) return OCH_OK;
-    och::DeviceGuard g(w->device);
-    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
-    return world_status(w, world_edit(*w, records, (uint32_t)n, on_device != 0));
+    if (!n) return world_usable(w, "och_world_edit");
+    return world_call(w, "och_world_edit", "och_world", kBreaks, kOwnTexts,
+                      [&] { return world_edit(*w, records, (uint32_t)n, on_device != 0); });
 }
 
 OCH_API int och_world_pool_create(och_world *w, och_gpu_pool **out)
 {
     if (!out) return och::report(OCH_E_INVALID, "och_world_pool_create: out is NULL");
     *out = nullptr;
-    if (const int us = world_usable(w, "och_world_pool_create")) return us;
-    och::DeviceGuard g(w->device);
-    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
-    och_gpu_pool *pool = nullptr;
-    if (const int cs = och::pool_create_for_world(w->device, w->depth, w->S.cap, w->id, &pool)) return cs;
-    och::WorldPoolView v;
-    int st = och::pool_world_view(pool, w->id, &v);
-    if (st == OCH_OK) {
-        *v.generation = w->generation;   // nothing published: the first flush writes ids [0, used)
-        st = world_flush(*w, pool);
-    }
-    if (st != OCH_OK) {
-        (void)och_gpu_pool_destroy(pool);
-        return st == OCH_E_HIP ? report_build(st, "och_world", "") : st;
-    }
-    *out = pool;
-    return OCH_OK;
+    return world_call(w, "och_world_pool_create", "och_world", kStays, kPoolTexts, [&] {
+        och_gpu_pool *pool = nullptr;
+        if (const int cs = och::pool_create_for_world(w->device, w->depth, w->S.cap, w->id, &pool)) return cs;
+        och::WorldPoolView v;
+        int st = och::pool_world_view(pool, w->id, &v);
+        if (st == OCH_OK) {
+            *v.generation = w->generation;   // nothing published: the first flush writes ids [0, used)
+            st = world_flush(*w, pool);
+        }
+        if (st == OCH_OK)
+            *out = pool;
+        else
+            (void)och_gpu_pool_destroy(pool);
+        return st;
+    });
 }
 
 OCH_API int och_world_flush(och_world *w, och_gpu_pool *pool)
 {
-    if (const int us = world_usable(w, "och_world_flush")) return us;
-    if (!pool) return och::report(OCH_E_INVALID, "och_world_flush: pool is NULL");
-    och::DeviceGuard g(w->device);
-    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
-    const int st = world_flush(*w, pool);
-    return st == OCH_E_HIP ? report_build(st, "och_world", "") : st;
+    return world_call(w, "och_world_flush", "och_world", kStays, kPoolTexts, [&] {
+        if (!pool) return och::report(OCH_E_INVALID, "och_world_flush: pool is NULL");
+        return world_flush(*w, pool);
+    });
 }
 
 OCH_API int och_world_download(och_world *w, och_host_pool *out)
 {
     if (!out) return och::report(OCH_E_INVALID, "och_world_download: out is NULL");
-    if (const int us = world_usable(w, "och_world_download")) return us;
-    och::DeviceGuard g(w->device);
-    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
-    const auto t_start = std::chrono::steady_clock::now();
-    PhaseTimer phase{"world ", 4, w->st};
-    BuildStats vs;
-    uint32_t root = w->root, n_out = 0;
-    uint32_t *nodes = nullptr;
-    int st = OCH_OK;
-    if (!root) {
-        st = empty_pool(&nodes, &n_out, root);
-    } else {
-        GpuScope T(w->st);
-        DevicePool dev;
-        st = renumber_gpu(w->S, w->used, root, w->depth, T, &nodes, &n_out, phase.on, &dev);
-        if (st == OCH_OK && (st = pool_stats_gpu(T, dev, n_out, w->depth, vs)) != OCH_OK) std::free(nodes);
-    }
-    if (st != OCH_OK) return report_build(st, "och_world", "allocation failed");   // reads only: the world stays usable
-    phase("download");
-    return finish_pool(out, nodes, n_out, root, 1, w->depth, vs, t_start);
+    return world_call(w, "och_world_download", "och_world", kStays, kOwnTexts, [&] {
+        const auto t_start = std::chrono::steady_clock::now();
+        PhaseTimer phase = world_phase(*w);
+        BuildStats vs;
+        uint32_t root = w->now.root, n_out = 0;
+        uint32_t *nodes = nullptr;
+        int st = OCH_OK;
+        if (!root) {
+            st = empty_pool(&nodes, &n_out, root);
+        } else {
+            GpuScope T(w->st);
+            DevicePool dev;
+            st = renumber_gpu(w->S, w->used, root, w->depth, T, &nodes, &n_out, phase.on, &dev);
+            if (st == OCH_OK && (st = pool_stats_gpu(T, dev, n_out, w->depth, vs)) != OCH_OK) std::free(nodes);
+        }
+        if (st != OCH_OK) return st;
+        phase("download");
+        return finish_pool(out, nodes, n_out, root, 1, w->depth, vs, t_start);
+    });
 }
 
 OCH_API int och_world_compact(och_world *w)
 {
-    if (const int us = world_usable(w, "och_world_compact")) return us;
-    och::DeviceGuard g(w->device);
-    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
     // the old store is replaced only once the new one is whole: a failure leaves the world as it was
-    const int st = w->snapshots.empty() ? world_compact(*w) : world_compact_history(*w);
-    return st == OCH_OK || st == OCH_E_INVALID ? st : report_build(st, "och_world", "allocation failed");
+    return world_call(w, "och_world_compact", "och_world", kStays, kOwnTexts,
+                      [&] { return w->snapshots.empty() ? world_compact(*w) : world_compact_history(*w); });
 }

@@ -4,8 +4,9 @@
 //
 // Snapshots.  The store is append-only (och_world.h): no row an earlier root
 // reaches ever changes, so an earlier state of the world is its root.  A
-// snapshot is a handle to (root, child mask, the world's box at the call), host
-// state only; a checkout puts the three back and launches nothing (the next
+// snapshot is a handle to a copy of the world's state (och_world::now: root,
+// child mask, the box at the call), host state only; a checkout assigns the
+// copy back and launches nothing (the next
 // stroke, which starts from the root word in the store's head, uploads it
 // first: 8 bytes, only after a checkout).  used, strokes, generation and the
 // store stay as they are, so strokes after a checkout branch off and the state
@@ -32,7 +33,7 @@
 //                   candidate survives when its two words differ; the pair's
 //                   survivors are a byte of the wavefront's ballot.  At height
 //                   0 the words are voxel ids and the survivors' box is
-//                   reduced per wavefront (k_world_box's way).
+//                   reduced per wavefront (box_reduce, as k_world_box).
 //   scan         -- hipcub's inclusive sum of the pairs' counts, 64-bit.
 //   read-back    -- the level's total (8 bytes, one synchronise): the next
 //                   frontier's size, or n at height 0, where it is compared
@@ -80,7 +81,7 @@ __device__ inline void diff_words(const GpuStore &S, const uint32_t *__restrict_
 }
 
 // cnt[i] = the child words of pair i that differ.  Leaf level (interior = 0):
-// the box of the differing voxels too (box: 0xFFFFFFFF x 3, 0 x 3 before).
+// the box of the differing voxels too (box: kNoBox before).
 __global__ __launch_bounds__(256) void k_diff_count(GpuStore S, const uint32_t *__restrict__ fa, const uint32_t *__restrict__ fb,
                                                     const uint64_t *__restrict__ keys, uint32_t f, int interior,
                                                     uint32_t *__restrict__ cnt, uint32_t *__restrict__ box)
@@ -93,26 +94,7 @@ __global__ __launch_bounds__(256) void k_diff_count(GpuStore S, const uint32_t *
     const uint32_t lane = threadIdx.x & 63u;
     if (q < (size_t)f * 8 && (lane & 7u) == 0) cnt[q >> 3] = (uint32_t)__popcll((b >> lane) & 0xFFull);
     if (interior || !b) return;   // the same in every lane
-    uint32_t lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0, 0, 0};
-    if (differ) {
-        const uint64_t key = keys[q >> 3] << 3 | (q & 7u);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) lo[a] = hi[a] = compact3(key >> a);
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int o = 32; o; o >>= 1) {
-            lo[a] = min(lo[a], (uint32_t)__shfl_xor(lo[a], o));
-            hi[a] = max(hi[a], (uint32_t)__shfl_xor(hi[a], o));
-        }
-    if (lane == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            atomicMin(box + a, lo[a]);
-            atomicMax(box + 3 + a, hi[a]);
-        }
-    }
+    box_reduce(differ, [&] { return keys[q >> 3] << 3 | (q & 7u); }, true, box);
 }
 
 // Survivor j of the level: pos[] is the inclusive sum of k_diff_count's cnt[].
@@ -231,21 +213,16 @@ int diff_walk(och_world &w, uint32_t ra, uint32_t rb, void *records, uint64_t ca
     int cur = 0;
     for (int h = w.depth - 1; h >= 0 && f; --h) {
         const int interior = h > 0 ? 1 : 0;
-        static const uint32_t no_box[6] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, 0};
         uint32_t box[6] = {0};
         uint64_t total = 0;
         ds.pairs += f;
-        if (!interior) GPU_TRY(hipMemcpyAsync(D.box, no_box, sizeof no_box, hipMemcpyHostToDevice, st));
+        if (!interior) GPU_TRY(hipMemcpyAsync(D.box, kNoBox, sizeof kNoBox, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_diff_count, blocks((size_t)f * 8), dim3(256), 0, st, w.S, D.fa[cur], D.fb[cur], D.keys[cur], f, interior,
                            D.cnt, D.box);
         GPU_TRY(hipGetLastError());
         size_t tb = w.diff_temp_bytes;
         GPU_TRY(hipcub::DeviceScan::InclusiveSum(D.temp, tb, DiffCounts(D.cnt, DiffWiden()), D.pos, (int)f, st));
-        // whatever the copies return, the stream is synchronised before `total` and `box` go
-        hipError_t ce = hipMemcpyAsync(&total, D.pos + (f - 1), 8, hipMemcpyDeviceToHost, st);
-        if (ce == hipSuccess && !interior) ce = hipMemcpyAsync(box, D.box, sizeof box, hipMemcpyDeviceToHost, st);
-        const hipError_t se = hipStreamSynchronize(st);
-        if (ce != hipSuccess || se != hipSuccess) return OCH_E_HIP;
+        if (const int rs = world_read_back(w, {{&total, D.pos + (f - 1), 8}, {box, D.box, interior ? 0 : sizeof box}})) return rs;
         if (total >= (1ull << 31)) return och::report(OCH_E_INVALID, kDiffTooMany);
         if (interior) {
             if (total > w.diff_cap) {
@@ -262,27 +239,20 @@ int diff_walk(och_world &w, uint32_t ra, uint32_t rb, void *records, uint64_t ca
             continue;
         }
         ds.n = total;
-        if (total && box[0] != 0xFFFFFFFFu)
-            for (int a = 0; a < 3; ++a) {
-                ds.box_lo[a] = (int32_t)box[a];
-                ds.box_hi[a] = (int32_t)box[3 + a] + 1;
-            }
+        const WorldBox changed = box_decode(box);   // no voxel, all 0, exactly when total is 0
+        std::memcpy(ds.box_lo, changed.lo, sizeof ds.box_lo);
+        std::memcpy(ds.box_hi, changed.hi, sizeof ds.box_hi);
         *out = ds;
         if (!records || !total) return OCH_OK;
         if (total > capacity)
             return och::fail(OCH_E_CAPACITY, "och_world_diff: %llu records, the buffer holds %llu", (unsigned long long)total,
                              (unsigned long long)capacity);
-        uint32_t *d_records = static_cast<uint32_t *>(records);
-        if (!on_device) {
-            if (w.d_read.reserve((size_t)total * 16) != hipSuccess) return OCH_E_NOMEM;
-            d_records = reinterpret_cast<uint32_t *>(w.d_read.d);
-        }
+        uint32_t *d_records = static_cast<uint32_t *>(world_stage(w, records, (size_t)total * 16, on_device));
+        if (!d_records) return OCH_E_NOMEM;
         hipLaunchKernelGGL(k_diff_emit, blocks((size_t)f * 8), dim3(256), 0, st, w.S, D.fa[cur], D.fb[cur], D.keys[cur], f, 0, D.pos,
                            nullptr, nullptr, nullptr, d_records);
         GPU_TRY(hipGetLastError());
-        if (!on_device) GPU_TRY(hipMemcpyAsync(records, d_records, (size_t)total * 16, hipMemcpyDeviceToHost, st));
-        GPU_TRY(hipStreamSynchronize(st));
-        return OCH_OK;
+        return world_read_back(w, {{records, d_records, on_device ? 0 : (size_t)total * 16}});
     }
     *out = ds;   // a level without survivors: only words at or above cap differed
     return OCH_OK;
@@ -290,7 +260,7 @@ int diff_walk(och_world &w, uint32_t ra, uint32_t rb, void *records, uint64_t ca
 
 int world_diff(och_world &w, uint32_t ra, uint32_t rb, void *records, uint64_t capacity, bool on_device, och_diff_stats *out)
 {
-    PhaseTimer phase{"world ", 4, w.st};
+    PhaseTimer phase = world_phase(w);
     if (ra == rb) {   // equal ids: equal content
         *out = och_diff_stats{};
         return OCH_OK;
@@ -310,11 +280,7 @@ int world_diff(och_world &w, uint32_t ra, uint32_t rb, void *records, uint64_t c
 int world_snapshot_of(const och_world &w, uint64_t handle, const char *who, WorldSnapshot *s)
 {
     if (handle == OCH_WORLD_CURRENT) {
-        s->root = w.root;
-        s->root_mask = w.root_mask;
-        s->box_any = w.box_any;
-        std::memcpy(s->box_lo, w.box_lo, sizeof s->box_lo);
-        std::memcpy(s->box_hi, w.box_hi, sizeof s->box_hi);
+        *s = w.now;
         return OCH_OK;
     }
     const auto it = w.snapshots.find(handle);
@@ -327,9 +293,9 @@ int world_snapshot_of(const och_world &w, uint64_t handle, const char *who, Worl
 int world_compact_history(och_world &w)
 {
     const hipStream_t st = w.st;
-    PhaseTimer phase{"world ", 4, st};
+    PhaseTimer phase = world_phase(w);
     std::vector<uint32_t> seeds;
-    if (w.root) seeds.push_back(w.root);
+    if (w.now.root) seeds.push_back(w.now.root);
     for (const auto &s : w.snapshots)
         if (s.second.root) seeds.push_back(s.second.root);
     std::sort(seeds.begin(), seeds.end());
@@ -340,15 +306,9 @@ int world_compact_history(och_world &w)
     GpuScope T(st);
     EditReach R;
     R.d_pool = w.S.nodes + 8;   // id's row at d_pool[(id - 1) * 8]
-    R.n_nodes = n;
-    R.root = w.root;
     uint32_t *d_new = nullptr;
-    if (!T.alloc(&R.d_placed, ((size_t)n + 1) * 4) || !T.alloc(&R.d_map, ((size_t)n + 1) * 4) || !T.alloc(&R.d_order, (size_t)n * 4) ||
-        !T.alloc(&R.d_head, 8) || !T.alloc(&d_new, (size_t)n_seeds * 4))
-        return OCH_E_NOMEM;
-    GPU_TRY(hipMemsetAsync(R.d_placed, 0, ((size_t)n + 1) * 4, st));
-    GPU_TRY(hipMemsetAsync(R.d_map, 0, ((size_t)n + 1) * 4, st));
-    GPU_TRY(hipMemsetAsync(R.d_head, 0, 8, st));
+    if (const int as = edit_reach_arrays(T, R, n, w.now.root, nullptr)) return as;
+    if (!T.alloc(&d_new, (size_t)n_seeds * 4)) return OCH_E_NOMEM;
     if (n_seeds) {
         GPU_TRY(hipMemcpyAsync(R.d_order, seeds.data(), (size_t)n_seeds * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_history_seed, blocks(n_seeds), dim3(256), 0, st, R.d_order, n_seeds, R.d_placed);
@@ -359,14 +319,13 @@ int world_compact_history(och_world &w)
     if (!phase("reach")) return OCH_E_HIP;
     std::unique_ptr<GpuScope> scope;
     GpuStore S;
-    uint32_t used = 0, root = 0, mask = 0;
-    if (const int as = world_adopt(w, T, R, w.S.cap, scope, S, &used, &root, &mask)) return as;
+    WorldHead H;
+    if (const int as = world_adopt(w, T, R, w.S.cap, scope, S, &H)) return as;
     std::vector<uint32_t> moved(n_seeds);
     if (n_seeds) {
         hipLaunchKernelGGL(k_history_gather, blocks(n_seeds), dim3(256), 0, st, R.d_map, R.d_order, n_seeds, d_new);
         GPU_TRY(hipGetLastError());
-        GPU_TRY(hipMemcpyAsync(moved.data(), d_new, (size_t)n_seeds * 4, hipMemcpyDeviceToHost, st));
-        GPU_TRY(hipStreamSynchronize(st));
+        if (const int rs = world_read_back(w, {{moved.data(), d_new, (size_t)n_seeds * 4}})) return rs;
     }
     if (!phase("adopt")) return OCH_E_HIP;
     auto new_id = [&](uint32_t old) {
@@ -374,16 +333,10 @@ int world_compact_history(och_world &w)
     };
     for (uint32_t s : seeds)
         if (!new_id(s)) return och::report(OCH_E_HIP, "och_world_compact: a root was lost in the adoption");
-    if (phase.on) std::fprintf(stderr, "[och_build] world: compacted %u ids to %u, %u roots kept\n", w.used, used, n_seeds);
+    if (phase.on) std::fprintf(stderr, "[och_build] world: compacted %u ids to %u, %u roots kept\n", w.used, H.used, n_seeds);
     // nothing of the world has changed so far: a failure above leaves the old store and every handle in place
     for (auto &s : w.snapshots) s.second.root = new_id(s.second.root);   // the child masks are content: unchanged
-    w.store_scope.swap(scope);   // the old store goes with `scope`, after a synchronise of the stream
-    w.S = S;
-    w.used = used;
-    w.root = root;
-    w.root_mask = mask;
-    w.head_stale = false;   // the new store's head holds the adopted root (k_world_root)
-    ++w.generation;
+    world_install(w, scope, S, H);
     return OCH_OK;
 }
 
@@ -408,12 +361,8 @@ OCH_API int och_world_checkout(och_world *w, uint64_t snapshot)
     if (const int us = world_usable(w, "och_world_checkout")) return us;
     WorldSnapshot s;
     if (const int ss = world_snapshot_of(*w, snapshot, "och_world_checkout", &s)) return ss;
-    w->head_stale = w->head_stale || s.root != w->root;   // the next stroke uploads the root it starts from
-    w->root = s.root;
-    w->root_mask = s.root_mask;
-    w->box_any = s.box_any;
-    std::memcpy(w->box_lo, s.box_lo, sizeof s.box_lo);
-    std::memcpy(w->box_hi, s.box_hi, sizeof s.box_hi);
+    w->head_stale = w->head_stale || s.root != w->now.root;   // the next stroke uploads the root it starts from
+    w->now = s;
     return OCH_OK;
 }
 
@@ -445,13 +394,10 @@ OCH_API int och_world_diff(och_world *w, uint64_t from, uint64_t to, void *recor
                            och_diff_stats *stats)
 {
     if (!stats) return och::report(OCH_E_INVALID, "och_world_diff: stats is NULL");
-    if (const int us = world_usable(w, "och_world_diff")) return us;
-    WorldSnapshot a, b;
-    if (const int ss = world_snapshot_of(*w, from, "och_world_diff", &a)) return ss;
-    if (const int ss = world_snapshot_of(*w, to, "och_world_diff", &b)) return ss;
-    och::DeviceGuard g(w->device);
-    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
-    const int st = world_diff(*w, a.root, b.root, records, capacity, on_device != 0, stats);
-    // reads only: the world stays usable; INVALID and CAPACITY are reported where they are found
-    return st == OCH_OK || st == OCH_E_INVALID || st == OCH_E_CAPACITY ? st : report_build(st, "och_world_diff", "allocation failed");
+    return world_call(w, "och_world_diff", "och_world_diff", kStays, kOwnTexts, [&] {
+        WorldSnapshot a, b;
+        if (const int ss = world_snapshot_of(*w, from, "och_world_diff", &a)) return ss;
+        if (const int ss = world_snapshot_of(*w, to, "och_world_diff", &b)) return ss;
+        return world_diff(*w, a.root, b.root, records, capacity, on_device != 0, stats);
+    });
 }

@@ -174,8 +174,8 @@ __global__ __launch_bounds__(256) void k_world_lbox(GpuStore S, uint32_t first, 
     lbox[id] = out;
 }
 
-// The root's local box into the head as k_world_box leaves a stroke's (min x y z,
-// max x y z, inclusive; 0xFFFFFFFF x 3, 0 x 3: no voxel), for the head's one read-back.
+// The root's local box into the head as k_world_box leaves a stroke's (a device
+// box, kNoBox without a voxel), for the head's one read-back.
 __global__ __launch_bounds__(64) void k_world_lbox_root(const ulonglong2 *__restrict__ lbox, uint32_t root, uint32_t *__restrict__ head)
 {
     if (blockIdx.x || threadIdx.x) return;
@@ -184,27 +184,26 @@ __global__ __launch_bounds__(64) void k_world_lbox_root(const ulonglong2 *__rest
     rb.y = 0;
     if (root) rb = lbox[root];
     for (int ax = 0; ax < 3; ++ax) {
-        head[kHeadBox + ax] = rb.x == kNoLbox ? 0xFFFFFFFFu : (uint32_t)((rb.x >> (21 * ax)) & 0x1FFFFFu);
-        head[kHeadBox + 3 + ax] = rb.x == kNoLbox ? 0u : (uint32_t)((rb.y >> (21 * ax)) & 0x1FFFFFu);
+        head[kHeadBox + ax] = rb.x == kNoLbox ? kNoBox[0] : (uint32_t)((rb.x >> (21 * ax)) & 0x1FFFFFu);
+        head[kHeadBox + 3 + ax] = rb.x == kNoLbox ? kNoBox[3] : (uint32_t)((rb.y >> (21 * ax)) & 0x1FFFFFu);
     }
 }
 
 int world_at(och_world &w, const int32_t *coords, uint32_t n, uint32_t *ids, bool on_device)
 {
     const hipStream_t st = w.st;
-    PhaseTimer phase{"world ", 4, st};
+    PhaseTimer phase = world_phase(w);
+    // host arrays: the ids' n words of the staging buffer, then the coordinates' 3 n
+    uint32_t *d_ids = static_cast<uint32_t *>(world_stage(w, ids, (size_t)n * 16, on_device));
+    if (!d_ids) return OCH_E_NOMEM;
     const int32_t *d_coords = coords;
-    uint32_t *d_ids = ids;
     if (!on_device) {
-        if (w.d_read.reserve((size_t)n * 16) != hipSuccess) return OCH_E_NOMEM;
-        d_coords = reinterpret_cast<const int32_t *>(w.d_read.d);
-        d_ids = reinterpret_cast<uint32_t *>(w.d_read.d + (size_t)n * 12);
-        GPU_TRY(hipMemcpyAsync(w.d_read.d, coords, (size_t)n * 12, hipMemcpyHostToDevice, st));
+        d_coords = reinterpret_cast<const int32_t *>(d_ids + n);
+        GPU_TRY(hipMemcpyAsync(d_ids + n, coords, (size_t)n * 12, hipMemcpyHostToDevice, st));
     }
-    hipLaunchKernelGGL(k_world_at, blocks(n), dim3(256), 0, st, w.S, w.root, w.depth, d_coords, n, d_ids);
+    hipLaunchKernelGGL(k_world_at, blocks(n), dim3(256), 0, st, w.S, w.now.root, w.depth, d_coords, n, d_ids);
     GPU_TRY(hipGetLastError());
-    if (!on_device) GPU_TRY(hipMemcpyAsync(ids, d_ids, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    GPU_TRY(hipStreamSynchronize(st));
+    if (const int rs = world_read_back(w, {{ids, d_ids, on_device ? 0 : (size_t)n * 4}})) return rs;
     phase("at");
     return OCH_OK;
 }
@@ -213,16 +212,13 @@ int world_at(och_world &w, const int32_t *coords, uint32_t n, uint32_t *ids, boo
 int world_read_box(och_world &w, const int32_t lo[3], const int32_t hi[3], int kind, void *grid, uint64_t cells, bool on_device)
 {
     const hipStream_t st = w.st;
-    PhaseTimer phase{"world ", 4, st};
+    PhaseTimer phase = world_phase(w);
     const size_t bytes = (size_t)cells * (kind == OCH_VOXELS_GRID_U8 ? 1 : 4);
-    void *d_grid = grid;
-    if (!on_device) {
-        if (w.d_read.reserve(bytes) != hipSuccess) return OCH_E_NOMEM;
-        d_grid = w.d_read.d;
-    }
+    void *d_grid = world_stage(w, grid, bytes, on_device);
+    if (!d_grid) return OCH_E_NOMEM;
     ReadBox B{};
     const int64_t dim = (int64_t)1 << w.depth;
-    bool meets = w.root != 0;
+    bool meets = w.now.root != 0;
     uint64_t bricks = 1;
     for (int a = 0; a < 3; ++a) {
         const int64_t clo = std::max<int64_t>(lo[a], 0), chi = std::min<int64_t>(hi[a], dim);
@@ -246,15 +242,11 @@ int world_read_box(och_world &w, const int32_t lo[3], const int32_t hi[3], int k
     GPU_TRY(hipMemsetAsync(flag, 0, 4, st));
     GPU_TRY(hipMemsetAsync(d_grid, 0, bytes, st));
     if (meets) {
-        hipLaunchKernelGGL(k_world_read, dim3(std::min((B.bricks + 3u) / 4u, kReadMaxBlocks)), dim3(256), 0, st, w.S, w.root, w.depth, B, d_grid, flag);
+        hipLaunchKernelGGL(k_world_read, dim3(std::min((B.bricks + 3u) / 4u, kReadMaxBlocks)), dim3(256), 0, st, w.S, w.now.root, w.depth, B, d_grid, flag);
         GPU_TRY(hipGetLastError());
     }
-    // `over` is this frame's: whatever the copies return, the stream is synchronised before it goes
     uint32_t over = 0;
-    hipError_t ce = hipMemcpyAsync(&over, flag, 4, hipMemcpyDeviceToHost, st);
-    if (ce == hipSuccess && !on_device) ce = hipMemcpyAsync(grid, d_grid, bytes, hipMemcpyDeviceToHost, st);
-    const hipError_t se = hipStreamSynchronize(st);
-    if (ce != hipSuccess || se != hipSuccess) return OCH_E_HIP;
+    if (const int rs = world_read_back(w, {{&over, flag, 4}, {grid, d_grid, on_device ? 0 : bytes}})) return rs;
     phase("read_box");
     if (over) return och::fail(OCH_E_INVALID, "och_world_read_box: voxel id %u does not fit a u8 grid", over);
     return OCH_OK;
@@ -263,7 +255,7 @@ int world_read_box(och_world &w, const int32_t lo[3], const int32_t hi[3], int k
 int world_tighten(och_world &w)
 {
     const hipStream_t st = w.st;
-    PhaseTimer phase{"world ", 4, st};
+    PhaseTimer phase = world_phase(w);
     if (w.d_lbox.n < w.S.cap) {
         w.boxed = 1;
         if (w.d_lbox.reserve(w.S.cap) != hipSuccess) return OCH_E_NOMEM;
@@ -277,18 +269,14 @@ int world_tighten(och_world &w)
             hipLaunchKernelGGL(k_world_lbox, blocks(w.used - first), dim3(256), 0, st, w.S, first, w.used, h, w.d_lbox.d);
             GPU_TRY(hipGetLastError());
         }
-    hipLaunchKernelGGL(k_world_lbox_root, dim3(1), dim3(64), 0, st, w.d_lbox.d, w.root, w.head());
+    hipLaunchKernelGGL(k_world_lbox_root, dim3(1), dim3(64), 0, st, w.d_lbox.d, w.now.root, w.head());
     GPU_TRY(hipGetLastError());
-    uint32_t used = 0, root = 0, mask = 0, box[6];
-    if (const int hs = world_read_head(w, w.S, &used, &root, &mask, box)) return hs;
+    WorldHead H;
+    if (const int hs = world_read_head(w, w.S, &H)) return hs;
     if (!phase("tighten")) return OCH_E_HIP;
     if (phase.on) std::fprintf(stderr, "[och_build] world: local boxes of ids [%u, %u)\n", first, w.used);
     w.boxed = w.used;
-    w.box_any = box[0] != 0xFFFFFFFFu;
-    for (int a = 0; a < 3; ++a) {
-        w.box_lo[a] = w.box_any ? (int32_t)box[a] : 0;
-        w.box_hi[a] = w.box_any ? (int32_t)box[3 + a] + 1 : 0;
-    }
+    w.now.box = box_decode(H.box);
     return OCH_OK;
 }
 
@@ -298,12 +286,9 @@ OCH_API int och_world_at(och_world *w, const int32_t *coords, uint64_t n, uint32
 {
     if (n >= (1ull << 31)) return och::report(OCH_E_INVALID, "och_world_at: a call takes fewer than 2^31 coordinates");
     if ((!coords || !ids) && n) return och::report(OCH_E_INVALID, "och_world_at: coords or ids is null");
-    if (const int us = world_usable(w, "och_world_at")) return us;
-    if (!n) return OCH_OK;
-    och::DeviceGuard g(w->device);
-    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
-    const int st = world_at(*w, coords, (uint32_t)n, ids, on_device != 0);
-    return st == OCH_OK ? st : report_build(st, "och_world_at", "allocation failed");   // reads only: the world stays usable
+    if (!n) return world_usable(w, "och_world_at");
+    return world_call(w, "och_world_at", "och_world_at", kStays, kOwnTexts,
+                      [&] { return world_at(*w, coords, (uint32_t)n, ids, on_device != 0); });
 }
 
 OCH_API int och_world_read_box(och_world *w, const int32_t lo[3], const int32_t hi[3], int kind, void *grid, size_t capacity_bytes,
@@ -311,18 +296,12 @@ OCH_API int och_world_read_box(och_world *w, const int32_t lo[3], const int32_t 
 {
     uint64_t cells = 0;
     if (const int cs = och::read_box_cells("och_world_read_box", lo, hi, kind, grid, capacity_bytes, &cells)) return cs;
-    if (const int us = world_usable(w, "och_world_read_box")) return us;
-    if (!cells) return OCH_OK;
-    och::DeviceGuard g(w->device);
-    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
-    const int st = world_read_box(*w, lo, hi, kind, grid, cells, on_device != 0);
-    return st == OCH_OK || st == OCH_E_INVALID ? st : report_build(st, "och_world_read_box", "allocation failed");
+    if (!cells) return world_usable(w, "och_world_read_box");
+    return world_call(w, "och_world_read_box", "och_world_read_box", kStays, kOwnTexts,
+                      [&] { return world_read_box(*w, lo, hi, kind, grid, cells, on_device != 0); });
 }
 
 OCH_API int och_world_tighten(och_world *w)
 {
-    if (const int us = world_usable(w, "och_world_tighten")) return us;
-    och::DeviceGuard g(w->device);
-    if (!g.ok) return report_build(OCH_E_HIP, "och_world", "");
-    return world_status(w, world_tighten(*w));
+    return world_call(w, "och_world_tighten", "och_world", kBreaks, kOwnTexts, [&] { return world_tighten(*w); });
 }

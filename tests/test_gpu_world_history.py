@@ -187,6 +187,24 @@ def test_sixty_four(ort, gpu_device, parents):
         check_diff(world, 0, s, world.download(), base, back)
 
 
+@pytest.mark.parametrize("parents", [63, 64, 65, 257])
+def test_one_box_reduction(ort, gpu_device, parents):
+    """The stroke's box (World.info) and the diff's box come from one wavefront reduction: `parents` distinct
+    random voxels into an empty world, a partial, a whole and more than one wavefront, more than one workgroup."""
+    depth = 6
+    rng = np.random.default_rng(parents)
+    cells = rng.choice(1 << 3 * depth, parents, replace=False)
+    rec = np.stack([cells & 63, cells >> 6 & 63, cells >> 12, rng.integers(1, 6, parents)], 1).astype(np.uint32)
+    with ort.World((np.zeros((0, 8), np.uint32), 0, depth), capacity=10_000) as world:
+        s = world.snapshot()
+        world.edit(rec)
+        lo = tuple(int(v) for v in rec[:, :3].min(0))
+        hi = tuple(int(v) + 1 for v in rec[:, :3].max(0))
+        info, (none, st) = world.info(), world.diff(s, 0, records=False)
+        assert none is None and st["n"] == parents
+        assert (tuple(info["box_lo"]), tuple(info["box_hi"])) == (tuple(st["box_lo"]), tuple(st["box_hi"])) == (lo, hi)
+
+
 # ------------------------------------------------------------ 5. depths 1, 2 and 21; an empty world
 
 @pytest.mark.parametrize("depth", [1, 2])

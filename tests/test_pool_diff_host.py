@@ -225,6 +225,36 @@ def test_null_world(ort):
     assert status(ort, "och_world_diff", None, 0, 0, None, 0, 0, None) == INVALID and "stats" in last_error(ort)
 
 
+WORLD_ENTRIES = ["info", "edit", "pool_create", "flush", "download", "compact", "at", "read_box", "tighten", "snapshot",
+                 "checkout", "release", "snapshots", "diff"]
+
+
+@pytest.mark.parametrize("entry", WORLD_ENTRIES)
+def test_null_world_every_entry(ort, entry):
+    """Every och_world_* entry that takes a world, with a NULL world and otherwise valid arguments: INVALID,
+    "<entry>: world is NULL", and every output as it was (och_world_pool_create hands out no pool: its handle is NULL)."""
+    from octree_ray_tracing_amd._lib import DiffStats, HostPool, WorldStats
+    fill = 0xAB
+    out = np.full(128, fill, np.uint8)                     # any entry's output: a struct, a handle, ids, a grid, records
+    p = out.ctypes.data
+    recs = np.array([[1, 2, 3, 4]], np.uint32)
+    coords = np.array([[1, 2, 3]], np.int32)
+    lo, hi = np.zeros(3, np.int32), np.full(3, 2, np.int32)
+    pool = C.c_void_p(p)                                   # never looked at: any non-NULL pool
+    args = {"info": (C.cast(p, C.POINTER(WorldStats)),), "edit": (recs.ctypes.data, 1, 0),
+            "pool_create": (C.cast(p, C.POINTER(C.c_void_p)),), "flush": (pool,), "download": (C.cast(p, C.POINTER(HostPool)),),
+            "compact": (), "at": (coords.ctypes.data, 1, p, 0), "read_box": (lo.ctypes.data, hi.ctypes.data, 1, p, 64, 0),
+            "tighten": (), "snapshot": (C.cast(p, C.POINTER(C.c_uint64)),), "checkout": (1,), "release": (1,),
+            "snapshots": (p, 8, C.cast(p + 32, C.POINTER(C.c_uint32))), "diff": (0, 0, p + 40, 1, 0, C.cast(p, C.POINTER(DiffStats)))}
+    assert max(C.sizeof(WorldStats), C.sizeof(HostPool), 40 + 16) <= out.size and C.sizeof(DiffStats) <= 40
+    assert status(ort, f"och_world_{entry}", None, *args[entry]) == INVALID
+    assert last_error(ort) == f"och_world_{entry}: world is NULL"
+    if entry == "pool_create":
+        assert not out[:8].any() and (out[8:] == fill).all()
+    else:
+        assert (out == fill).all()
+
+
 # ------------------------------------------------------------ symbols, the Python side, a C99 host
 
 NAMES = {"och_world_snapshot", "och_world_checkout", "och_world_release", "och_world_snapshots", "och_world_diff",
