@@ -860,8 +860,10 @@ OCH_API int och_world_info(const och_world *world, och_world_stats *info);
  * the stroke's unique in-range keys > capacity: one id per row of the
  * records' own tree, ignoring what the rows share with the store, so the
  * answer depends on the records alone.  Call och_world_compact and retry.
- * The box grows by the box of the stroke's in-range records with id != 0;
- * removals never shrink it (och_world_tighten does). */
+ * The box grows by the box of the stroke's surviving in-range records with
+ * id != 0 -- surviving: after last wins, so a coordinate set and then removed
+ * within one list does not count; removals never shrink it
+ * (och_world_tighten does). */
 OCH_API int och_world_edit(och_world *world, const void *records, uint64_t n, int on_device);
 /* A pool of the current world on the world's device: index_base 1, the
  * world's depth, miss t = +INF, capacity slots (och_pool_info.n_nodes), its

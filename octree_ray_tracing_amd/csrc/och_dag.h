@@ -31,6 +31,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "och_hash.h"
 #include "och_internal.h"
 
 namespace {
@@ -67,26 +68,7 @@ void parallel_for(int threads, uint64_t n, const std::function<void(uint64_t, in
     for (auto &th : pool) th.join();
 }
 
-__host__ __device__ inline uint64_t mix64(uint64_t h)
-{
-    h ^= h >> 33;
-    h *= 0xFF51AFD7ED558CCDull;
-    h ^= h >> 33;
-    h *= 0xC4CEB9FE1A85EC53ull;
-    h ^= h >> 33;
-    return h;
-}
-
-// The hash of a node's key, level h and child words c: the host store's and
-// the device probe's (a table slot is its low bits).
-__host__ __device__ inline uint64_t node_hash(const uint32_t c[8], int h)
-{
-    uint64_t hs = mix64((uint64_t)h * 0x9E3779B97F4A7C15ull ^ ((uint64_t)c[1] << 32 | c[0]));
-    hs = mix64(hs ^ ((uint64_t)c[3] << 32 | c[2]));
-    hs = mix64(hs ^ ((uint64_t)c[5] << 32 | c[4]));
-    hs = mix64(hs ^ ((uint64_t)c[7] << 32 | c[6]));
-    return hs;
-}
+using och_hash::node_hash;
 
 // Lock-free interning of (level, 8 child words) -> node id.  Ids are handed
 // out by one atomic counter; a lost insert race leaves an unused id behind
