@@ -995,6 +995,76 @@ OCH_API int och_world_snapshots(const och_world *world, uint64_t *ids, uint32_t 
 OCH_API int och_world_diff(och_world *world, uint64_t from, uint64_t to, void *records, uint64_t capacity,
                            int on_device, och_diff_stats *stats);
 
+/* ------------------------------------------------------------ world: regions */
+/* Strokes whose shape is a box, at a cost that follows the box's surface.  A
+ * box is a union of maximal aligned cubes, and a cube of side 2^h that lies
+ * wholly inside it is one child word at height h: 0 for a clear, the id of the
+ * uniform subtree of that height for a fill, the word another root holds there
+ * for a restore.  Only the cells that straddle the box's faces get new rows.
+ * Both strokes are append-only like och_world_edit: frames in flight and other
+ * snapshots stay valid, OCH_E_CAPACITY leaves the world unchanged, and a HIP
+ * failure inside them breaks the world.  The part of a box outside the tree is
+ * ignored; hi[a] <= lo[a] on an axis, or nothing left after clipping, is a
+ * stroke that changes nothing (strokes + 1, OCH_OK, stats all 0), as an edit
+ * whose records all lie outside the tree.
+ * Out of scope: shapes other than boxes; copying a box to another place; fills
+ * conditional on the old voxel; replicated worlds. */
+typedef struct och_region_stats {
+    uint64_t cubes;      /* child words written: the maximal aligned cubes inside the box that were emitted */
+    uint64_t cells;      /* straddling cells expanded = rows rebuilt, summed over the levels */
+    uint64_t new_ids;    /* ids the stroke consumed */
+    int32_t  lo[3], hi[3];  /* the box after clipping to [0, dim); lo = hi = 0: nothing inside the tree */
+} och_region_stats;      /* 48 bytes */
+
+/* Host only, no device: the maximal aligned cubes of lo <= (x, y, z) < hi
+ * clipped to a tree of `depth` (1..21) -- the cubes of side 2^h, aligned to
+ * 2^h, that lie inside the box while their parent cube does not.  keys[i] is
+ * cube i's Morton key at its height heights[i] (its corner is the key's
+ * coordinates times 2^h; key = x bit 0, y bit 1, z bit 2 per level), in
+ * ascending height and ascending key within a height: the order in which the
+ * region strokes inject them.  cubes_per_height[h] counts them; cells_per_height[H]
+ * counts the cells of side 2^H that straddle the box (meet it without lying
+ * inside): the rows a fill rebuilds.  Both arrays hold 22 entries (heights
+ * 0..21; the whole tree is one cube at height depth) and either may be NULL;
+ * *count is the cubes' total.  keys = heights = NULL with capacity 0 gives the
+ * counts only, from closed forms.  OCH_E_INVALID: a NULL lo, hi or count,
+ * depth outside 1..21, only one of keys and heights; OCH_E_CAPACITY: more
+ * cubes than capacity, the counts complete and nothing written to keys. */
+OCH_API int och_box_cubes(const int32_t lo[3], const int32_t hi[3], int depth,
+                          uint64_t *keys, uint8_t *heights, uint64_t capacity,
+                          uint64_t cubes_per_height[22], uint64_t cells_per_height[22], uint64_t *count);
+/* Set every voxel of the box to id (0 removes; any uint32): the world is left
+ * exactly as och_world_edit of the box's records would leave it, content and
+ * canonical och_world_download alike, without a record: for any box
+ * stats.cubes and stats.cells are och_box_cubes' totals.  A box that covers
+ * the whole tree makes the root the uniform subtree of height depth, or 0.
+ * OCH_E_CAPACITY, with the world unchanged, when used + cells + T > capacity,
+ * T = the greatest height with a cube for id != 0 (the uniform subtrees made
+ * on the way), else 0: the answer depends on the box alone.  OCH_E_INVALID: a
+ * NULL lo or hi, a NULL or broken world, a height with 2^31 entries or more.
+ * id != 0 grows the world's box by the clipped box; a clear leaves it
+ * (och_world_tighten makes it exact).  One read-back, of the store's head. */
+OCH_API int och_world_fill_box(och_world *world, const int32_t lo[3], const int32_t hi[3], uint32_t id,
+                               och_region_stats *stats /* may be NULL */);
+/* Inside the clipped box the content of `snapshot`, outside it the current
+ * content.  The snapshot is a live handle of this world; OCH_WORLD_CURRENT is
+ * a stroke that changes nothing.  The walk drops every cell whose ids under
+ * the two roots are equal (och_world_diff's rule), so the cost follows the
+ * part of the box's surface and interior that differs: stats.cubes counts the
+ * maximal cubes inside the box whose content differs, stats.cells the
+ * straddling cells whose content inside the box differs.  A box that covers
+ * the whole tree makes the snapshot's root the current one (cubes = 1 when the
+ * roots differ).  OCH_E_CAPACITY, with the world unchanged, when used + the
+ * straddling cells the walk expanded (those whose two ids differ, at least
+ * stats.cells) > capacity.  OCH_E_INVALID: a NULL lo or hi, a NULL or broken
+ * world, an unknown or released handle, a height with 2^31 differing cubes or
+ * 2^28 differing cells or more.  The world's box grows by the part of the
+ * clipped box inside the snapshot's box.  One 8-byte read-back per level on
+ * the way down, one of 4 bytes per level on the way up; the buffers are kept
+ * and grown on demand, as och_world_diff's. */
+OCH_API int och_world_restore_box(och_world *world, uint64_t snapshot, const int32_t lo[3], const int32_t hi[3],
+                                  och_region_stats *stats /* may be NULL */);
+
 /* ------------------------------------------------------------ editor */
 /* Interactive editing (the demo's place/remove, ORT/test_och_h_octree.cpp:
  * 301-435): h_octree::set / at (ORT/och_h_octree.h:176-258) over a host pool of

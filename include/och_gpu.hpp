@@ -272,6 +272,28 @@ inline och_diff_stats pool_diff(const och_host_pool &a, const och_host_pool &b, 
     return st;
 }
 
+// The maximal aligned cubes of the box lo <= (x, y, z) < hi clipped to a tree of
+// `depth` (och_box_cubes, host only): their Morton keys and heights in
+// ascending height and key, with the per-height counts of the cubes and of the
+// cells that straddle the box (22 entries each).
+struct box_cube_list {
+    std::vector<uint64_t> keys;
+    std::vector<uint8_t> heights;
+    uint64_t cubes_per_height[22], cells_per_height[22];
+};
+inline box_cube_list box_cubes(const int32_t lo[3], const int32_t hi[3], int depth)
+{
+    box_cube_list out;
+    uint64_t n = 0;
+    check(och_box_cubes(lo, hi, depth, nullptr, nullptr, 0, out.cubes_per_height, out.cells_per_height, &n), "och_box_cubes");
+    out.keys.resize(n);
+    out.heights.resize(n);
+    if (n)
+        check(och_box_cubes(lo, hi, depth, out.keys.data(), out.heights.data(), n, out.cubes_per_height, out.cells_per_height, &n),
+              "och_box_cubes");
+    return out;
+}
+
 // A world that stays on one GPU between brush strokes (och_world_*): edit()
 // applies a record list as edit_voxels would, flush() publishes the stroke's
 // new nodes to a tree made by make_pool(), download() gives the canonical pool;
@@ -345,6 +367,21 @@ public:
     {
         och_diff_stats st;
         check(och_world_diff(w_, from, to, records, capacity, on_device ? 1 : 0, &st), "och_world_diff");
+        return st;
+    }
+    // Every voxel of the box [lo, hi) becomes id (0 removes), as edit() of the box's records would leave
+    // the world, at a cost that follows the box's surface; OCH_E_CAPACITY leaves the world as it was.
+    och_region_stats fill_box(const int32_t lo[3], const int32_t hi[3], uint32_t id)
+    {
+        och_region_stats st;
+        check(och_world_fill_box(w_, lo, hi, id, &st), "och_world_fill_box");
+        return st;
+    }
+    // Inside the box the content of the snapshot, outside it the current content: undo for a region.
+    och_region_stats restore_box(uint64_t snapshot, const int32_t lo[3], const int32_t hi[3])
+    {
+        och_region_stats st;
+        check(och_world_restore_box(w_, snapshot, lo, hi, &st), "och_world_restore_box");
         return st;
     }
 

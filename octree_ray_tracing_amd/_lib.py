@@ -72,6 +72,12 @@ class DiffStats(C.Structure):
     _fields_ = [("n", C.c_uint64), ("pairs", C.c_uint64), ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3)]
 
 
+class RegionStats(C.Structure):
+    """och_region_stats: what och_world_fill_box and och_world_restore_box report."""
+    _fields_ = [("cubes", C.c_uint64), ("cells", C.c_uint64), ("new_ids", C.c_uint64), ("lo", C.c_int32 * 3),
+                ("hi", C.c_int32 * 3)]
+
+
 class TerrainParams(C.Structure):
     _fields_ = [("depth", C.c_int32), ("tunnels", C.c_int32), ("dedup", C.c_int32),
                 ("rand_kind", C.c_int32), ("threads", C.c_int32), ("use_gpu", C.c_int32)]
@@ -187,6 +193,9 @@ PROTOTYPES = {
     "och_world_release": (C.c_int, [_P, C.c_uint64]),
     "och_world_snapshots": (C.c_int, [_P, _P, _u32, C.POINTER(_u32)]),
     "och_world_diff": (C.c_int, [_P, C.c_uint64, C.c_uint64, _P, C.c_uint64, C.c_int, C.POINTER(DiffStats)]),
+    "och_box_cubes": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_uint64, _P, _P, C.POINTER(C.c_uint64)]),
+    "och_world_fill_box": (C.c_int, [_P, _P, _P, _u32, C.POINTER(RegionStats)]),
+    "och_world_restore_box": (C.c_int, [_P, C.c_uint64, _P, _P, C.POINTER(RegionStats)]),
     "och_pool_pack": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "och_pool_at": (_u32, [_P, _u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "och_pool_occupied_box": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _P]),

@@ -311,6 +311,27 @@ def box_records(lo, hi, id: int) -> np.ndarray:
     return rec.reshape(-1, 4)
 
 
+def _box_args(lo, hi, who: str):
+    """(lo, hi as int32[3]) of a box stroke, checked as read_box checks its corners."""
+    return _read_box_args(lo, hi, np.uint8, who)[:2]
+
+
+def box_cubes(lo, hi, depth: int):
+    """The maximal aligned cubes of the box lo <= (x, y, z) < hi clipped to a tree of `depth`
+    (och_box_cubes, host only): (keys, heights, cubes_per_height, cells_per_height).  keys[i] is cube i's
+    Morton key at height heights[i] (side 2^h, corner = the key's coordinates times 2^h), in ascending
+    height and ascending key within a height; cubes_per_height[h] counts them and cells_per_height[H]
+    the cells of side 2^H that straddle the box, both np.uint64 of length depth + 1.  What
+    World.fill_box writes and rebuilds: its stats' cubes and cells are the two sums."""
+    lo, hi = _box_args(lo, hi, "box_cubes")
+    cubes, cells, n = (C.c_uint64 * 22)(), (C.c_uint64 * 22)(), C.c_uint64()
+    call("och_box_cubes", lo, hi, int(depth), None, None, 0, cubes, cells, C.byref(n))
+    keys, heights = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint8)
+    if n.value:
+        call("och_box_cubes", lo, hi, int(depth), keys.ctypes.data, heights.ctypes.data, n.value, cubes, cells, C.byref(n))
+    return keys, heights, np.array(cubes[:int(depth) + 1], np.uint64), np.array(cells[:int(depth) + 1], np.uint64)
+
+
 def occupied_box(nodes: np.ndarray, root: int, depth: int, index_base: int = 1):
     """Bounding box of the pool's voxels (och_pool_occupied_box): (lo, hi) in
     voxel units, voxel (x, y, z) inside iff lo <= (x, y, z) < hi; lo = hi = 0

@@ -9,7 +9,8 @@
 // three world headers share (the state record, the box convention, the entry
 // wrapper, the staging and read-back steps); what reads that world back on the
 // device (at, a box to a grid, the exact box) is och_world_read.h; snapshots
-// of that world, checkout and the diff of two roots are och_world_history.h.
+// of that world, checkout and the diff of two roots are och_world_history.h;
+// its box-shaped strokes (fill, clear, restore) are och_world_region.h.
 // One translation unit: the headers are included here and nowhere else.
 //
 // The reference builds its tree by recursive create_volume + per-voxel
@@ -43,6 +44,7 @@
 #include "och_world.h"
 #include "och_world_read.h"
 #include "och_world_history.h"
+#include "och_world_region.h"
 
 namespace {
 

@@ -102,6 +102,21 @@ int pool_world_view(och_gpu_pool *pool, uint64_t world, WorldPoolView *view);
 int read_box_cells(const char *who, const int32_t lo[3], const int32_t hi[3], int kind, const void *grid,
                    size_t capacity_bytes, uint64_t *cells);
 
+// The maximal aligned cubes of the box lo <= (x, y, z) < hi clipped to a tree
+// of `depth`, counted (och_pool.cpp, for och_box_cubes and the region strokes
+// of och_world_region.h).  Per axis at height H, touch = ceil(hi / 2^H) -
+// floor(lo / 2^H) cells meet the box and in = max(0, floor(hi / 2^H) -
+// ceil(lo / 2^H)) lie inside it: cells[H] = prod touch - prod in straddle it,
+// cubes[h] = prod in(h) - 8 prod in(h + 1) are inside while their parent is not.
+struct BoxCubes {
+    bool any = false;                             // something of the box lies inside the tree
+    int32_t lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // the clipped box; all 0 without one
+    uint64_t cubes[22] = {0}, cells[22] = {0};    // by height, 0 .. depth
+    uint64_t n_cubes = 0, n_cells = 0;
+    int top = -1;                                 // the greatest height with a cube
+};
+BoxCubes box_cube_counts(const int32_t lo[3], const int32_t hi[3], int depth);
+
 // n_views views of one positive width and height (och_api.cpp).
 int check_views(const och_camera *cams, int n_views);
 

@@ -1022,3 +1022,96 @@ OCH_API int och_pool_diff(const uint32_t *nodes_a, uint32_t n_a, uint32_t root_a
     write.walk(has_a, root_a, has_b, root_b, depth - 1, origin);
     return OCH_OK;
 }
+
+och::BoxCubes och::box_cube_counts(const int32_t lo[3], const int32_t hi[3], int depth)
+{
+    BoxCubes c;
+    const int64_t dim = (int64_t)1 << depth;
+    int64_t l[3], h[3];
+    bool any = true;
+    for (int a = 0; a < 3; ++a) {
+        l[a] = std::max<int64_t>(lo[a], 0);
+        h[a] = std::min<int64_t>(hi[a], dim);
+        any = any && l[a] < h[a];
+    }
+    if (!any) return c;
+    c.any = true;
+    uint64_t in[23];   // prod in_a by height, 0 .. depth + 1
+    for (int H = 0; H <= depth + 1; ++H) {
+        uint64_t touch = 1, inside = 1;
+        for (int a = 0; a < 3; ++a) {
+            const int64_t s = (int64_t)1 << H;
+            touch *= (uint64_t)(((h[a] + s - 1) >> H) - (l[a] >> H));
+            inside *= (uint64_t)std::max<int64_t>(0, (h[a] >> H) - ((l[a] + s - 1) >> H));
+        }
+        in[H] = inside;
+        if (H <= depth) c.cells[H] = touch - inside;
+    }
+    for (int H = 0; H <= depth; ++H) {
+        c.cubes[H] = in[H] - 8 * in[H + 1];
+        c.n_cubes += c.cubes[H];
+        c.n_cells += c.cells[H];
+        if (c.cubes[H]) c.top = H;
+    }
+    for (int a = 0; a < 3; ++a) {
+        c.lo[a] = (int32_t)l[a];
+        c.hi[a] = (int32_t)h[a];
+    }
+    return c;
+}
+
+OCH_API int och_box_cubes(const int32_t lo[3], const int32_t hi[3], int depth, uint64_t *keys, uint8_t *heights,
+                          uint64_t capacity, uint64_t cubes_per_height[22], uint64_t cells_per_height[22], uint64_t *count)
+{
+    if (!lo || !hi) return fail(OCH_E_INVALID, "och_box_cubes: lo or hi is NULL");
+    if (!count) return fail(OCH_E_INVALID, "och_box_cubes: count is NULL");
+    if (depth < 1 || depth > 21) return fail(OCH_E_INVALID, "och_box_cubes: depth must be 1..21 (a Morton key has 3 * depth bits)");
+    if ((keys == nullptr) != (heights == nullptr) || (!keys && capacity))
+        return fail(OCH_E_INVALID, "och_box_cubes: keys and heights go together, and capacity counts their entries");
+    const och::BoxCubes c = och::box_cube_counts(lo, hi, depth);
+    if (cubes_per_height) std::copy(c.cubes, c.cubes + 22, cubes_per_height);
+    if (cells_per_height) std::copy(c.cells, c.cells + 22, cells_per_height);
+    *count = c.n_cubes;
+    if (!keys || !c.n_cubes) return OCH_OK;
+    if (c.n_cubes > capacity)
+        return fail(OCH_E_CAPACITY, "och_box_cubes: %llu cubes, the buffers hold %llu", (unsigned long long)c.n_cubes,
+                    (unsigned long long)capacity);
+    // top-down, a level's straddling cells in Morton order, child digits ascending: each height's
+    // cubes come out in ascending Morton order; height h's go to [first[h], first[h] + cubes[h])
+    uint64_t first[22] = {0}, at[22] = {0};
+    for (int h = 1; h <= depth; ++h) first[h] = at[h] = first[h - 1] + c.cubes[h - 1];
+    struct Cell {
+        uint64_t key;
+        int32_t o[3];
+    };
+    auto emit = [&](int h, uint64_t key) {
+        keys[at[h]] = key;
+        heights[at[h]++] = (uint8_t)h;
+    };
+    if (c.top == depth) {   // the whole tree
+        emit(depth, 0);
+        return OCH_OK;
+    }
+    std::vector<Cell> front{{0, {0, 0, 0}}}, next;
+    for (int H = depth; H >= 1 && !front.empty(); --H) {
+        const int32_t s = (int32_t)1 << (H - 1);
+        next.clear();
+        for (const Cell &f : front)
+            for (int k = 0; k < 8; ++k) {
+                const Cell ch{f.key << 3 | (uint64_t)k, {f.o[0] + (k & 1) * s, f.o[1] + ((k >> 1) & 1) * s, f.o[2] + ((k >> 2) & 1) * s}};
+                bool inside = true, outside = false;
+                for (int a = 0; a < 3; ++a) {
+                    inside = inside && c.lo[a] <= ch.o[a] && ch.o[a] + s <= c.hi[a];
+                    outside = outside || ch.o[a] >= c.hi[a] || ch.o[a] + s <= c.lo[a];
+                }
+                if (inside)
+                    emit(H - 1, ch.key);
+                else if (!outside)
+                    next.push_back(ch);
+            }
+        front.swap(next);
+    }
+    for (int h = 0; h <= depth; ++h)
+        if (at[h] != first[h] + c.cubes[h]) return fail(OCH_E_INVALID, "och_box_cubes: the walk and the closed forms disagree");
+    return OCH_OK;
+}

@@ -48,7 +48,8 @@
 // paths; 0-based pools; depth 22.  Reading the world back (at, a box to a grid,
 // the exact box after removals) is och_world_read.h, with what stays out of
 // scope there; remembering earlier roots (snapshot, checkout, the diff of two
-// roots) is och_world_history.h.
+// roots) is och_world_history.h; strokes whose shape is a box (fill, clear,
+// restore from a snapshot) are och_world_region.h.
 #pragma once
 #include <map>
 #include <memory>
@@ -192,6 +193,8 @@ struct och_world {
     och::DevBuf<uint8_t> d_diff;
     uint32_t diff_cap = 0;
     size_t diff_temp_bytes = 0;
+    // och_world_region.h: a region stroke's cubes, frontiers, counts and scan storage, sized by its box, kept
+    och::DevBuf<uint8_t> d_region;
 
     uint32_t *head() const { return S.next; }
     ~och_world()

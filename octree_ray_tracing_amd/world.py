@@ -13,13 +13,14 @@ import numpy as np
 
 from . import _lib
 from ._lib import HostPool, OchError, call
-from .builder import VOXELS_GRID_U8, NodePool, _capacity, _host_records, _read_box_args, diff_stats_dict
+from .builder import VOXELS_GRID_U8, NodePool, _box_args, _capacity, _host_records, _read_box_args, diff_stats_dict
 from .tracer import HOctree
 
 
 class World:
     """A 1-based DAG resident on one GPU: edit() applies a record list as edit_voxels would, make_pool()
     and flush() show it, download() gives the canonical pool, compact() drops what strokes left behind;
+    fill_box() and restore_box() set or restore a whole box at a cost that follows its surface;
     at() and read_box() ask it what it holds without a download, tighten() makes its box exact;
     snapshot(), checkout() and release() remember and restore earlier states (UndoStack, below), diff()
     gives what changed between two of them."""
@@ -259,6 +260,39 @@ class World:
         if n:
             call("och_world_diff", h, a, b, out.ctypes.data, n, 0, C.byref(st))
         return out, diff_stats_dict(st)
+
+    # -- regions (och_world_fill_box / och_world_restore_box)
+
+    @staticmethod
+    def _region_stats(st) -> dict:
+        return {"cubes": int(st.cubes), "cells": int(st.cells), "new_ids": int(st.new_ids), "lo": tuple(st.lo),
+                "hi": tuple(st.hi)}
+
+    def fill_box(self, lo, hi, id: int) -> dict:
+        """One stroke: every voxel of the box lo <= (x, y, z) < hi becomes id (0 removes), as
+        edit(box_records(lo, hi, id)) would leave the world, without a record (och_world_fill_box): a cube of
+        side 2^h inside the box is one child word, only the cells that straddle its faces get new nodes.
+        The part of the box outside the tree is ignored.  Returns {"cubes", "cells", "new_ids", "lo", "hi"}:
+        box_cubes' two totals, the ids consumed and the clipped box.  OchError CAPACITY leaves the world
+        unchanged: compact() and retry."""
+        h = self._open("fill_box")
+        lo, hi = _box_args(lo, hi, "World.fill_box")
+        if isinstance(id, bool) or not isinstance(id, (int, np.integer)) or not 0 <= int(id) <= 0xFFFFFFFF:
+            raise ValueError(f"World.fill_box: id is an integer inside uint32, not {id!r}")
+        st = _lib.RegionStats()
+        call("och_world_fill_box", h, lo, hi, int(id), C.byref(st))
+        return self._region_stats(st)
+
+    def restore_box(self, s: int, lo, hi) -> dict:
+        """One stroke: inside the box the content of snapshot s, outside it the current content
+        (och_world_restore_box): undo for a region.  The cost follows what differs inside the box.  Returns
+        fill_box's dict; cubes and cells count only what differs."""
+        h = self._open("restore_box")
+        s = self._handle(s, "restore_box")
+        lo, hi = _box_args(lo, hi, "World.restore_box")
+        st = _lib.RegionStats()
+        call("och_world_restore_box", h, s, lo, hi, C.byref(st))
+        return self._region_stats(st)
 
 
 class UndoStack:
