@@ -1054,12 +1054,17 @@ OCH_API int och_world_fill_box(och_world *world, const int32_t lo[3], const int3
  * maximal cubes inside the box whose content differs, stats.cells the
  * straddling cells whose content inside the box differs.  A box that covers
  * the whole tree makes the snapshot's root the current one (cubes = 1 when the
- * roots differ).  OCH_E_CAPACITY, with the world unchanged, when used + the
- * straddling cells the walk expanded (those whose two ids differ, at least
- * stats.cells) > capacity.  OCH_E_INVALID: a NULL lo or hi, a NULL or broken
+ * roots differ).  A restore that finds no differing cube -- OCH_WORLD_CURRENT,
+ * equal roots, a box outside the tree, or two states that differ outside the
+ * box only -- changes nothing but strokes (+ 1): it consumes no id, is never
+ * refused for capacity and leaves the world's box as it is.  Otherwise:
+ * OCH_E_CAPACITY, with the world unchanged, when used + the straddling cells
+ * the walk expanded (those whose two ids differ, the root cell included; at
+ * least stats.cells) > capacity, and the world's box grows by the part of the
+ * clipped box inside the snapshot's box (a whole-tree restore consumes no id
+ * and is never refused).  OCH_E_INVALID: a NULL lo or hi, a NULL or broken
  * world, an unknown or released handle, a height with 2^31 differing cubes or
- * 2^28 differing cells or more.  The world's box grows by the part of the
- * clipped box inside the snapshot's box.  One 8-byte read-back per level on
+ * 2^28 differing cells or more.  One 8-byte read-back per level on
  * the way down, one of 4 bytes per level on the way up; the buffers are kept
  * and grown on demand, as och_world_diff's. */
 OCH_API int och_world_restore_box(och_world *world, uint64_t snapshot, const int32_t lo[3], const int32_t hi[3],

@@ -237,6 +237,134 @@ def test_restore_is_the_composition(ort, gpu_device, depth):
         same_build(world.download(), ort.build_voxels(want, use_gpu=False))
 
 
+# ------------------------------------------------------------ 3b. a restore that outgrows its buffers
+
+# och_world_restore_box starts with room for min(the box's cubes, 2^16) cubes and a frontier of min(the
+# widest level, 2^14) cells; a level that outgrows either ends the walk, which starts over from the roots
+# with larger buffers.  BIG is the smallest cube-shaped box with odd faces that does both: every count
+# below is recomputed from the box by the closed forms of tests/world_model.py, held to ort.box_cubes.
+BIG_DEPTH, BIG_LO, BIG_HI = 7, (1, 1, 1), (127, 127, 127)
+FIRST_CUBES, FIRST_FRONT = 1 << 16, 1 << 14
+
+
+def closed_forms(ort, lo, hi, depth):
+    """(cubes per height, cells per height) of the box, in Python integers, held to ort.box_cubes."""
+    from world_model import box_counts, clip_box
+    cubes, cells, _ = box_counts(clip_box(lo, hi, depth), depth)
+    _, _, want_cubes, want_cells = ort.box_cubes(lo, hi, depth)
+    assert cubes == [int(v) for v in want_cubes] and cells == [int(v) for v in want_cells]
+    return cubes, cells
+
+
+def box_of(grid, lo, hi):
+    return grid[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]]
+
+
+@pytest.fixture(scope="module")
+def big(ort):
+    """The depth-7 base (some 20 000 voxels with ids 1..5), its dense grid, and the composition that the large
+    restore must leave: the base inside BIG, a shell of 9 outside it.  Built once, on the CPU, and never written to."""
+    n = 1 << BIG_DEPTH
+    base = ort.build_voxels(random_records(77, 20_000, BIG_DEPTH), depth=BIG_DEPTH)
+    old = whole_grid(base)
+    shell = np.full((n, n, n), 9, np.uint32)
+    box_of(shell, BIG_LO, BIG_HI)[...] = box_of(old, BIG_LO, BIG_HI)
+    for a in (old, shell):
+        a.setflags(write=False)
+    return base, old, shell, ort.build_voxels(shell, use_gpu=False)
+
+
+def same_content(world, grid, tree=None, ort=None):
+    n = grid.shape[0]
+    assert np.array_equal(world.read_box((0, 0, 0), (n, n, n), np.uint32), grid)
+    same_build(world.download(), tree if tree is not None else ort.build_voxels(grid, use_gpu=False))   # the CPU builder
+
+
+def small_restore(world, ort, frm, grid, frm_grid):
+    """A restore of a few cubes, (9, 9, 9)..(12, 12, 12): its stats against the dense grids, the new grid."""
+    lo, hi = (9, 9, 9), (12, 12, 12)
+    st = world.restore_box(frm, lo, hi)
+    assert (st["cubes"], st["cells"]) == differing(BIG_DEPTH, lo, hi, grid, frm_grid) and st["cubes"] > 1
+    grid = grid.copy()
+    box_of(grid, lo, hi)[...] = box_of(frm_grid, lo, hi)
+    return st, grid
+
+
+def test_restore_outgrows_its_buffers(ort, gpu_device, big):
+    base, old, shell, shell_tree = big
+    n = 1 << BIG_DEPTH
+    cubes, cells = closed_forms(ort, BIG_LO, BIG_HI, BIG_DEPTH)
+    # two restarts: the frontier at height 1 outgrows its first size while the cubes above height 0 still
+    # fit, then, in the second walk, the cubes of height 0 outgrow theirs
+    assert cells[1] > FIRST_FRONT and sum(cubes[1:]) <= FIRST_CUBES < sum(cubes) and max(cells[2:]) <= FIRST_FRONT
+    nines = np.full((n, n, n), 9, np.uint32)
+    with ort.World(base, capacity=200_000) as world:
+        s = world.snapshot()
+        assert world.fill_box((0, 0, 0), (n, n, n), 9)["cubes"] == 1     # every cell now differs from s
+        filled = world.snapshot()
+        st = world.restore_box(s, BIG_LO, BIG_HI)
+        print("restore", st, "closed forms", sum(cubes), sum(cells), cubes, cells)
+        assert (st["cubes"], st["cells"], st["lo"], st["hi"]) == (sum(cubes), sum(cells), BIG_LO, BIG_HI)
+        same_content(world, shell, shell_tree)
+        # the grown buffers are kept: a small restore, a fill, and the large restore once more without a restart
+        small_st, grid = small_restore(world, ort, filled, shell, nines)
+        same_content(world, grid, ort=ort)
+        small_tree = world.download()
+        lo, hi = (30, 31, 32), (50, 41, 45)
+        check_stats(ort, world.fill_box(lo, hi, 4), lo, hi, BIG_DEPTH)
+        box_of(grid, lo, hi)[...] = 4
+        same_content(world, grid, ort=ort)
+        world.checkout(filled)
+        again = world.restore_box(s, BIG_LO, BIG_HI)
+        assert {k: again[k] for k in ("cubes", "cells", "lo", "hi")} == {k: st[k] for k in ("cubes", "cells", "lo", "hi")}
+        assert again["new_ids"] == 0                                     # the store holds every row of the first time
+        same_content(world, shell, shell_tree)
+        # pruned counts across many workgroups: only a thin slab inside the box differs from s
+        world.checkout(s)
+        lo, hi = (5, 5, 1), (120, 121, 3)                             # against the box's lower face, where its cubes are small
+        world.fill_box(lo, hi, 9)
+        now = old.copy()
+        box_of(now, lo, hi)[...] = 9
+        st = world.restore_box(s, BIG_LO, BIG_HI)
+        want = differing(BIG_DEPTH, BIG_LO, BIG_HI, now, old)
+        print("slab", st, want)
+        assert (st["cubes"], st["cells"]) == want and want[0] > 10_000
+        same_content(world, old, base)
+    # the same small restore where nothing has grown: the same stats and download
+    with ort.World(shell_tree, capacity=200_000) as world:
+        a = world.snapshot()
+        world.fill_box((0, 0, 0), (n, n, n), 9)
+        filled = world.snapshot()
+        world.checkout(a)
+        fresh_st, fresh_grid = small_restore(world, ort, filled, shell, nines)
+        assert {k: fresh_st[k] for k in ("cubes", "cells", "lo", "hi")} == {k: small_st[k] for k in ("cubes", "cells", "lo", "hi")}
+        same_build(world.download(), small_tree)
+
+
+def test_restore_outgrows_its_frontier_alone(ort, gpu_device, big):
+    """BIG again, in a fresh world, where the state differs from the snapshot in one voxel of each of the
+    64^3 - 62^3 = 23 816 cells of height 1 that straddle it (cells[1] of its closed forms): the frontier at
+    height 1 outgrows its 2^14 cells, one restart, while the differing cubes, one of height 0 per cell, stay
+    below 2^16."""
+    base, old, _, _ = big
+    cubes, cells = closed_forms(ort, BIG_LO, BIG_HI, BIG_DEPTH)
+    c = np.stack(np.meshgrid(*[np.arange(64)] * 3, indexing="ij"), -1).reshape(-1, 3)
+    c = c[((c == 0) | (c == 63)).any(1)]                                 # the cells of height 1 that straddle BIG
+    assert len(c) == cells[1] and FIRST_FRONT < len(c) <= FIRST_CUBES
+    voxels = np.clip(2 * c, BIG_LO[0], BIG_HI[0] - 1)                    # one voxel of each, inside the box
+    rec = np.concatenate([voxels, np.full((len(voxels), 1), 9)], 1).astype(np.uint32)
+    now = old.copy()
+    now[voxels[:, 2], voxels[:, 1], voxels[:, 0]] = 9
+    with ort.World(base, capacity=200_000) as world:
+        s = world.snapshot()
+        world.edit(rec)
+        assert np.array_equal(world.read_box((0, 0, 0), now.shape[::-1], np.uint32), now)
+        st = world.restore_box(s, BIG_LO, BIG_HI)
+        print("frontier alone", st, cells)
+        assert (st["cubes"], st["cells"]) == (len(c), sum(cells)) == differing(BIG_DEPTH, BIG_LO, BIG_HI, now, old)
+        same_content(world, old, base)
+
+
 # ------------------------------------------------------------ 4. shallow and deep
 
 @pytest.mark.parametrize("depth", [1, 2])

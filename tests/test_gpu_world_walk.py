@@ -11,7 +11,7 @@ import pytest
 from test_gpu_lit import make_light, render
 from test_gpu_tiled_batch import tiled_dev
 from test_gpu_world import BRUSH_POS, BRUSH_VIEW, random_rays
-from test_world_walk_host import WALKS, make_model
+from test_world_walk_host import REGION_STEPS, WALKS, make_model
 from world_model import Walk
 
 pytestmark = pytest.mark.gpu
@@ -25,8 +25,8 @@ def test_walk(ort, O, gpu_device, seed, depth, capacity, steps):
     tree = ort.build_voxels(base, depth=depth)
     t0 = time.perf_counter()
     with ort.World(tree, capacity=None if capacity is None else model.capacity) as world:
-        Walk(ort, world, model, seed, big=capacity == "roomy", O=O, on_gpu=True).run(steps)
-    print(f"walk {seed} depth {depth}: {steps} operations in {time.perf_counter() - t0:.1f} s")
+        Walk(ort, world, model, seed, big=capacity == "roomy", O=O, on_gpu=True).run(steps + REGION_STEPS)
+    print(f"walk {seed} depth {depth}: {steps + REGION_STEPS} operations in {time.perf_counter() - t0:.1f} s")
 
 
 # ------------------------------------------------------------ a used world's pool through the other frame kernels

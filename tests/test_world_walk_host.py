@@ -3,7 +3,10 @@ quotas that keep the walks from being vacuous.
 
 HostWorld has World's methods but no store: a stroke is ort.edit_voxels(use_gpu=False) with a random
 thread count, at() is NodePool.at behind a range check, read_box() NodePool.read_box, diff()
-NodePool.diff of two pools, tighten() ort.occupied_box.  The driver skips `used`, the loose box,
+NodePool.diff of two pools, tighten() ort.occupied_box, fill_box() the editor over ort.box_records,
+a clear of any size the tree's diff against an empty pool filtered to the box and applied, restore_box()
+its diff against the snapshot's tree likewise; their stats come from och_box_cubes' counts and, for a
+restore at depth <= 5, from differing() over the two dense grids.  The driver skips `used`, the loose box,
 refusals and pools for it (the model still meets them: the operation list is the GPU's).  That
 proves model, generator and driver against a second implementation before a GPU is involved, and
 gives the host editor its first randomised chains.
@@ -25,9 +28,11 @@ from world_model import Model, Walk
 # needs, None = the default, "roomy" = 40 000 ids (the two strokes of more than 1024 leaf-level
 # parents need some 2 000 rows each).  Depths 1 and 2: the root is, or sits directly on, a leaf-level
 # node; 6: the smallest at which one stroke can exceed 1024 leaf-level parents; 16 and 21: a few
-# hundred cells clustered around corner_records.
+# hundred cells clustered around corner_records; the second depth-21 walk has room for the box strokes' cells.
+# After its `steps` operations every walk runs REGION_STEPS more: the room that the box strokes' sequences need.
 WALKS = [(101, 1, 8, 80), (102, 2, 20, 80), (103, 3, 30, 90), (104, 4, 30, 90), (105, 5, None, 90), (106, 5, 40, 100),
-         (107, 6, "roomy", 70), (108, 6, 100, 80), (109, 16, 20, 80), (110, 21, 16, 80)]
+         (107, 6, "roomy", 70), (108, 6, 100, 80), (109, 16, 20, 80), (110, 21, 16, 80), (111, 21, 2000, 80)]
+REGION_STEPS = 50
 
 
 def base_records(seed, depth):
@@ -105,6 +110,56 @@ class HostWorld:
     def diff(self, a, b=0, device=False, records=True):
         return self._state(a).diff(self._state(b), records=records)
 
+    # -- box strokes: the record editor, with the records a diff of two pools gives where the box is large
+    def _clipped(self, lo, hi):
+        lo, hi = np.maximum(np.asarray(lo, np.int64), 0), np.minimum(np.asarray(hi, np.int64), 1 << self.depth)
+        return (lo, hi) if (lo < hi).all() else None
+
+    def _become(self, other, box):
+        """Inside the box the voxels of `other`: its diff against the current tree, filtered to the box, applied."""
+        rec, _ = self.tree.diff(other)
+        c = rec[:, :3].astype(np.int64)
+        rec = rec[((c >= box[0]) & (c < box[1])).all(1)]
+        if len(rec):
+            self.tree = self.ort.edit_voxels(self.tree, rec, use_gpu=False, threads=int(self.rng.integers(1, 6)))
+
+    def _counts(self, lo, hi):
+        """och_box_cubes' two totals, counts only (the cubes of a large box are too many to list)."""
+        import ctypes as C
+        cubes, cells, n = (C.c_uint64 * 22)(), (C.c_uint64 * 22)(), C.c_uint64()
+        assert self.ort.load().och_box_cubes((C.c_int32 * 3)(*lo), (C.c_int32 * 3)(*hi), self.depth, None, None, 0, cubes, cells,
+                                             C.byref(n)) == 0
+        assert sum(cubes) == n.value
+        return int(n.value), int(sum(cells))
+
+    def fill_box(self, lo, hi, id):
+        self.strokes += 1
+        box = self._clipped(lo, hi)
+        if box is None:
+            return {"cubes": 0, "cells": 0, "lo": (0, 0, 0), "hi": (0, 0, 0)}
+        if id:
+            self.tree = self.ort.edit_voxels(self.tree, self.ort.box_records(box[0], box[1], id), use_gpu=False,
+                                             threads=int(self.rng.integers(1, 6)))
+        else:
+            self._become(self.ort.build_voxels(np.zeros((0, 4), np.uint32), depth=self.depth, use_gpu=False), box)
+        cubes, cells = self._counts(box[0].tolist(), box[1].tolist())
+        return {"cubes": cubes, "cells": cells, "lo": tuple(box[0].tolist()), "hi": tuple(box[1].tolist())}
+
+    def restore_box(self, s, lo, hi):
+        from test_gpu_world_region import differing, whole_grid
+        self.strokes += 1
+        box = self._clipped(lo, hi)
+        if box is None:
+            return {"cubes": 0, "cells": 0, "lo": (0, 0, 0), "hi": (0, 0, 0)}
+        out = {"lo": tuple(box[0].tolist()), "hi": tuple(box[1].tolist())}
+        snap = self._state(s)
+        if self.depth <= 5:            # the counts from the two dense grids
+            a, b = whole_grid(self.tree), whole_grid(snap)
+            cubes, cells = differing(self.depth, box[0], box[1], a, b)
+            out.update(cubes=cubes, cells=cells)
+        self._become(snap, box)
+        return out
+
 
 @pytest.fixture(scope="module")
 def tallies():
@@ -116,9 +171,9 @@ def tallies():
 def test_walk_host(ort, tallies, seed, depth, capacity, steps):
     model, base = make_model(seed, depth, capacity)
     t0, tally = time.perf_counter(), collections.Counter()
-    Walk(ort, HostWorld(ort, depth, base, seed), model, seed, big=capacity == "roomy", tally=tally).run(steps)
+    Walk(ort, HostWorld(ort, depth, base, seed), model, seed, big=capacity == "roomy", tally=tally).run(steps + REGION_STEPS)
     tallies[seed] = tally
-    print(f"walk {seed} depth {depth}: {steps} operations in {time.perf_counter() - t0:.1f} s")
+    print(f"walk {seed} depth {depth}: {steps + REGION_STEPS} operations in {time.perf_counter() - t0:.1f} s")
 
 
 # quota -> (the tally's key, the least count); a third of each kind with a device form is counted below
@@ -139,7 +194,29 @@ QUOTAS = {"admitted strokes": ("admitted", 150), "refused strokes": ("refused", 
           "overhanging read_box calls": ("read_box_overhang", 3), "u8 refusals": ("read_box_u8_refused", 2),
           "revert_by_diff": ("revert_by_diff", 3), "no-change strokes": ("no_change", 1),
           "all-out-of-range strokes": ("outside", 1), "emptying strokes": ("emptying", 1),
-          "strokes where the two readings of the box rule differ": ("box_readings_differ", 1)}
+          "strokes where the two readings of the box rule differ": ("box_readings_differ", 1),
+          # box strokes (fill_box, restore_box)
+          "fills that change the content": ("fill_change", 3), "clears that change the content": ("clear_change", 3),
+          "restores that change the content": ("restore_change", 3),
+          "restores from a snapshot older than the current generation": ("restore_old", 3),
+          "box strokes directly after a root-changing checkout": ("region_after_checkout", 3),
+          "refused box strokes": ("region_refused", 3),
+          "a whole-tree clear, then a record stroke, flush and check_pool": ("seq_whole_clear", 1),
+          "a whole-tree restore, then flush and check_pool": ("seq_whole_restore", 1),
+          "a whole-tree restore, then a compaction with live snapshots, then tighten": ("seq_whole_restore_compact", 1),
+          "a restore into an empty world": ("restore_into_empty", 1), "a restore from an empty snapshot": ("restore_from_empty", 1),
+          "a restore of a box that holds no difference": ("restore_no_effect", 1),
+          "a fill whose uniform subtrees the store holds": ("fill_uniform_held", 1),
+          "the same fill after a compaction": ("fill_uniform_after_compaction", 1),
+          "a restore outside the tightened box, then flush and check_pool": ("seq_restore_outside_box", 1),
+          "a fill refused, and admitted after the compaction": ("retry_admitted_clear", 1),
+          "a restore refused, and admitted after the compaction": ("retry_admitted_restore", 1),
+          "a fill refused at used + need == capacity + 1": ("bound_refused_clear", 1),
+          "a fill admitted at used + need == capacity": ("bound_admitted_clear", 1),
+          "a restore refused at used + need == capacity + 1": ("bound_refused_restore", 1),
+          "a restore admitted at used + need == capacity": ("bound_admitted_restore", 1)}
+QUOTAS.update({f"a {kind} that changes the content with a face aligned to 2^{k} and no more": (f"{kind}_k{k}", 1)
+               for kind in ("fill", "clear", "restore") for k in range(5)})
 
 
 def test_quotas(ort, tallies):
@@ -150,7 +227,7 @@ def test_quotas(ort, tallies):
         if seed not in tallies:
             model, base = make_model(seed, depth, capacity)
             tallies[seed] = collections.Counter()
-            Walk(ort, HostWorld(ort, depth, base, seed), model, seed, big=capacity == "roomy", tally=tallies[seed]).run(steps)
+            Walk(ort, HostWorld(ort, depth, base, seed), model, seed, big=capacity == "roomy", tally=tallies[seed]).run(steps + REGION_STEPS)
         tally.update(tallies[seed])
     print(dict(tally))
     short = {name: (tally[key], least) for name, (key, least) in QUOTAS.items() if tally[key] < least}

@@ -21,10 +21,26 @@ The model is written from the header, not from the kernels:
   capacity     a stroke is refused, everything unchanged, exactly when used + the sum over h = 1..depth
                of |{k >> 3 h}| over its unique in-range keys > capacity.
   pools        the cells and box at a pool's last flush (at make_pool: the world's then).
+  fill_box     ("world: regions") every voxel of the clipped box becomes id.  Counts are closed forms of
+               the clipped box in Python integers: per axis and height the aligned intervals that meet it
+               and the ones inside it; cells[H] = prod meeting - prod inside, cubes[h] = inside(h) -
+               8 inside(h + 1).  Nothing inside the tree: strokes + 1, stats all 0.  A height with cubes +
+               cells >= 2^31: INVALID.  used + sum cells + T > capacity (T = the greatest height with a
+               cube for id != 0, else 0): REFUSED.  Otherwise held gains the non-empty node of the new
+               tree at every straddling cell and, for id != 0, the uniform subtrees of heights 1..T; the
+               box grows by the clipped box for id != 0.
+  restore_box  inside the clipped box the snapshot's content.  The two trees are walked from the root;
+               front = the straddling cells visited whose two nodes differ, cubes = the inside children
+               whose two words differ, cells = the visited cells with such a cube beneath them.  Handle
+               0, equal roots, a box outside the tree, or no differing cube: strokes + 1 and nothing
+               else, whatever the capacity.  Otherwise REFUSED when used + front > capacity; else held
+               gains the new non-empty nodes at the `cells` cells and the box grows by the clipped box
+               inside the snapshot's box.  The whole tree: the snapshot's root, cubes = 1, no id.
 
 The generator consults only the model, so a seed gives the same operation list on every backend.
 """
 import collections
+import itertools
 import types
 
 import numpy as np
@@ -36,6 +52,10 @@ from test_voxel_builder import ODD_IDS, ORIGIN, check_pool, corner_records, expe
 SKY = 0xFFFEBF00
 NOTHING = {"n": 0, "pairs": 0, "box_lo": (0, 0, 0), "box_hi": (0, 0, 0)}
 REFUSED = "refused"
+INVALID = "invalid"
+REGION_LIMIT = 1 << 31            # a height of a box stroke holds fewer cubes + cells than this
+FILL_VOXELS = 1 << 15             # the generator's fills with id != 0 stay at or below this many voxels
+NO_REGION = {"cubes": 0, "cells": 0, "new_ids": 0, "lo": (0, 0, 0), "hi": (0, 0, 0)}
 DIFF_FIRST_SIZE = 1024            # the diff buffers' first size, in pairs of one level
 
 
@@ -50,6 +70,55 @@ def box_union(a, b):
     if a is None or b is None:
         return a or b
     return tuple(min(p, q) for p, q in zip(a[0], b[0])), tuple(max(p, q) for p, q in zip(a[1], b[1]))
+
+
+def clip_box(lo, hi, depth):
+    """The box clipped to the tree as ((x, y, z), (x, y, z)) of Python integers, None where nothing is left."""
+    lo = tuple(max(int(v), 0) for v in lo)
+    hi = tuple(min(int(v), 1 << depth) for v in hi)
+    return (lo, hi) if all(l < h for l, h in zip(lo, hi)) else None
+
+
+def box_counts(box, depth):
+    """(cubes per height, cells per height, the greatest height with a cube) of a clipped box, from closed
+    forms: per axis at height h, the aligned intervals of length 2^h that meet [lo, hi) and the ones inside it."""
+    inside, cells = [], []
+    for h in range(depth + 1):
+        meet = ins = 1
+        for l, u in zip(*box):
+            meet *= ((u - 1) >> h) - (l >> h) + 1
+            ins *= max(0, (u >> h) - ((l + (1 << h) - 1) >> h))
+        inside.append(ins)
+        cells.append(meet - ins)
+    inside.append(0)
+    cubes = [inside[h] - 8 * inside[h + 1] for h in range(depth + 1)]
+    return cubes, cells, max(h for h in range(depth + 1) if cubes[h])
+
+
+def in_box(c, box):
+    return all(l <= v < u for v, l, u in zip(c, *box))
+
+
+def box_inside(a, b):
+    """Box a (or None: no voxels) lies inside box b."""
+    return a is None or (b is not None and all(p >= q for p, q in zip(a[0], b[0])) and all(p <= q for p, q in zip(a[1], b[1])))
+
+
+def box_meet(a, b):
+    if a is None or b is None:
+        return None
+    lo, hi = tuple(max(p, q) for p, q in zip(a[0], b[0])), tuple(min(p, q) for p, q in zip(a[1], b[1]))
+    return (lo, hi) if all(l < h for l, h in zip(lo, hi)) else None
+
+
+def coords_of(keys, levels):
+    """Morton keys (x bit 0, y bit 1, z bit 2 per level) of `levels` levels as an (n, 3) int64 array."""
+    k = np.asarray(keys, np.int64).reshape(-1)
+    out = np.zeros((len(k), 3), np.int64)
+    for i in range(levels):
+        for a in range(3):
+            out[:, a] |= ((k >> (3 * i + a)) & 1) << i
+    return out
 
 
 def records_of(cells):
@@ -73,7 +142,7 @@ class State:
 
 class Model:
     def __init__(self, depth, base_records, capacity=None):
-        self.depth, self.cons = depth, {}
+        self.depth, self.cons, self.rows = depth, {}, {0: (0,) * 8}
         cells = self._apply({}, base_records)
         self.now = self._state(cells, exact_box(cells))
         self.held = self.now.nodes()
@@ -97,6 +166,11 @@ class Model:
         c = np.asarray(coords, np.int64).reshape(-1, 3)
         return morton_keys(c[:, 0], c[:, 1], c[:, 2], self.depth)
 
+    def _intern(self, h, row):
+        node = self.cons.setdefault((h, row), len(self.cons) + 1)
+        self.rows[node] = row
+        return node
+
     def _state(self, cells, box):
         cur = dict(zip(self._keys(list(cells)).tolist(), cells.values()))
         levels = []
@@ -104,7 +178,7 @@ class Model:
             rows = {}
             for key, w in cur.items():
                 rows.setdefault(key >> 3, [0] * 8)[key & 7] = w
-            cur = {pk: self.cons.setdefault((h, tuple(row)), len(self.cons) + 1) for pk, row in rows.items()}
+            cur = {pk: self._intern(h, tuple(row)) for pk, row in rows.items()}
             levels.append(cur)
         return State(cells, levels, cur.get(0, 0), box)
 
@@ -156,6 +230,120 @@ class Model:
         self.strokes += 1
         self.version += 1
         return "stroke"
+
+    # -- box strokes
+    def _straddling(self, state, box):
+        """The non-empty nodes of `state` at the cells that straddle the box, found by classifying the
+        positions of its sparse levels."""
+        out = set()
+        lo, hi = np.array(box[0], np.int64), np.array(box[1], np.int64)
+        for h, level in enumerate(state.levels):
+            if not level:
+                continue
+            keys = list(level)
+            c = coords_of(keys, self.depth - h - 1) << (h + 1)
+            e = c + (1 << (h + 1))
+            meets = ((c < hi) & (e > lo)).all(1)
+            inside = ((c >= lo) & (e <= hi)).all(1)
+            out.update(level[keys[i]] for i in np.nonzero(meets & ~inside)[0].tolist())
+        return out
+
+    def fill_plan(self, lo, hi, id):
+        """(clipped box or None, cubes, cells, T, need, INVALID / REFUSED / None) of a fill, nothing changed."""
+        box = clip_box(lo, hi, self.depth)
+        if box is None:
+            return None, [], [], 0, 0, None
+        cubes, cells, top = box_counts(box, self.depth)
+        T = top if id else 0
+        need = sum(cells) + T
+        what = None
+        if any(a + b >= REGION_LIMIT for a, b in zip(cubes, cells)):
+            what = INVALID
+        elif self.used + need > self.capacity:
+            what = REFUSED
+        return box, cubes, cells, T, need, what
+
+    def fill_box(self, lo, hi, id):
+        """("outside" / INVALID / REFUSED / "fill", the stats or None)."""
+        box, cubes, cells, T, need, what = self.fill_plan(lo, hi, id)
+        if box is None:
+            self.strokes += 1
+            return "outside", dict(NO_REGION)
+        if what:
+            return what, None
+        new = {c: v for c, v in self.now.cells.items() if not in_box(c, box)}
+        if id:
+            assert np.prod([u - l for l, u in zip(*box)], dtype=object) <= 2 * FILL_VOXELS, box
+            (x0, y0, z0), (x1, y1, z1) = box
+            new.update(((x, y, z), id) for x in range(x0, x1) for y in range(y0, y1) for z in range(z0, z1))
+        self.now = self._state(new, box_union(self.now.box, box) if id else self.now.box)
+        before = len(self.held)
+        self.held |= self._straddling(self.now, box)
+        uniform = id
+        for h in range(T):
+            uniform = self._intern(h, (uniform,) * 8)
+            self.held.add(uniform)
+        self.strokes += 1
+        self.version += 1
+        return "fill", {"cubes": sum(cubes), "cells": sum(cells), "new_ids": len(self.held) - before, "lo": box[0], "hi": box[1]}
+
+    def restore_plan(self, s, box):
+        """(front, cubes, the cells with a differing cube beneath them as (height, key)) of the walk of the
+        current tree and snapshot s's from the root, for a clipped box that is not the whole tree."""
+        lo, hi = box
+        rows_of, count, cells = self.rows, [0, 0], []
+
+        def visit(H, key, o, na, nb):
+            count[0] += 1
+            ra, rb, half, found = rows_of[na], rows_of[nb], 1 << (H - 1), False
+            for k in range(8):
+                if ra[k] == rb[k]:
+                    continue
+                c = (o[0] + (k & 1) * half, o[1] + ((k >> 1) & 1) * half, o[2] + ((k >> 2) & 1) * half)
+                if any(c[a] >= hi[a] or c[a] + half <= lo[a] for a in range(3)):
+                    continue
+                if all(lo[a] <= c[a] and c[a] + half <= hi[a] for a in range(3)):
+                    count[1] += 1
+                    found = True
+                elif visit(H - 1, key << 3 | k, c, ra[k], rb[k]):
+                    found = True
+            if found:
+                cells.append((H, key))
+            return found
+
+        visit(self.depth, 0, (0, 0, 0), self.now.root, self.state(s).root)
+        return count[0], count[1], cells
+
+    def restore_box(self, s, lo, hi):
+        """("nothing" / "whole" / "no_effect" / REFUSED / "restore", the stats or None)."""
+        snap, box = self.state(s), clip_box(lo, hi, self.depth)
+        st = dict(NO_REGION) if box is None else dict(NO_REGION, lo=box[0], hi=box[1])
+        if box is None or snap.root == self.now.root:
+            self.strokes += 1
+            return "nothing", st
+        grown = box_union(self.now.box, box_meet(box, snap.box))
+        if box == ((0, 0, 0), (1 << self.depth,) * 3):
+            self.now = State(snap.cells, snap.levels, snap.root, grown)
+            self.strokes += 1
+            self.version += 1
+            return "whole", dict(st, cubes=1)
+        front, cubes, cells = self.restore_plan(s, box)
+        if not cubes:                  # the two states differ outside the box only: no id, no refusal, the box stays
+            self.strokes += 1
+            return "no_effect", st
+        if self.used + front > self.capacity:
+            return REFUSED, None
+        new = {c: v for c, v in self.now.cells.items() if not in_box(c, box)}
+        new.update((c, v) for c, v in snap.cells.items() if in_box(c, box))
+        self.now = self._state(new, grown)
+        before = len(self.held)
+        for H, key in cells:
+            node = self.now.levels[H - 1].get(key)
+            if node:
+                self.held.add(node)
+        self.strokes += 1
+        self.version += 1
+        return "restore", dict(st, cubes=cubes, cells=len(cells), new_ids=len(self.held) - before)
 
     # -- history
     def snapshot(self):
@@ -209,6 +397,11 @@ class Generator:
         self.script = ([(8, "big"), (15, "u8"), (20, "set_remove"), (40, "big")] if big else
                        [(15, "u8"), (20, "set_remove"), (25, "empty"), (35, "checkout_compact"), (50, "empty_now"),
                         (62, "checkout_compact")])
+        # the box strokes' sequences: the capacity ones in every walk, of the others every second one
+        regions = ["r_checkout", "r_whole", "r_across", "r_empty", "r_untouched", "r_uniform", "r_outside", "r_checkout"]
+        regions = [name for i, name in enumerate(regions) if (i + seed) % 2 == 0]
+        regions += ["r_pin_fill", "r_pin_restore", "r_refuse_fill", "r_refuse_restore"]
+        self.script += [(self.script[-1][0] + 3 + 5 * i, name) for i, name in enumerate(regions)]
 
     # -- coordinates and strokes
     def coords(self, n):
@@ -302,6 +495,143 @@ class Generator:
                 return np.array(c, np.int64)
         return None
 
+    # -- box strokes
+    def some_cell(self, states=None):
+        """A coordinate: mostly a voxel of the current state or of a snapshot, else anywhere."""
+        states = [self.m.now] + [st for st, _ in self.m.snapshots.values()] if states is None else states
+        states = [st for st in states if st.cells]
+        if states and self.rng.random() < 0.85:
+            cells = states[self.rng.integers(0, len(states))].cells
+            return np.array(next(itertools.islice(cells, int(self.rng.integers(0, min(len(cells), 64))), None)), np.int64)
+        return np.clip(self.coords(1)[0], 0, self.dim - 1)
+
+    def aligned_box(self, centre, kmax, side_max):
+        """A box near `centre` whose faces are multiples of 2^k plus or minus a few voxels, k in 0..kmax,
+        of side at most about side_max.  Gives (lo, hi, k)."""
+        rng = self.rng
+        k = int(rng.integers(0, kmax + 1))
+        while k and (1 << k) > side_max:
+            k -= 1
+        most = max(1, min(3, side_max >> k))
+        size = rng.integers(1, most + 1, 3) << k
+        lo = ((np.asarray(centre, np.int64) >> k) - rng.integers(0, most, 3)) << k
+        hi = lo + size
+        jitter = lambda: np.where(rng.random(3) < 0.6, 0, rng.integers(-2, 4, 3))
+        lo, hi = lo + jitter(), hi + jitter()
+        return lo, np.maximum(hi, lo + 1), k
+
+    def region_box(self, fill, centre=None, kinds=True):
+        """(lo, hi) for a box stroke: fill = True keeps the clipped box at or below FILL_VOXELS voxels."""
+        rng, m = self.rng, self.m
+        kind = ["aligned"] * 12 + ["overhang", "empty", "outside", "whole"]
+        kind = kind[rng.integers(0, len(kind))] if kinds and centre is None else "aligned"
+        if kind == "whole" and (not fill or m.depth <= 5):
+            return (0, 0, 0), (self.dim,) * 3
+        if kind == "outside":
+            return (self.dim, 0, -4), (self.dim + 4, 4, 0)
+        side_max = 16 if fill else max(self.dim >> 1, 1)
+        for _ in range(20):
+            lo, hi, _k = self.aligned_box(self.some_cell() if centre is None else centre, m.depth, side_max)
+            if kind == "overhang":
+                a = rng.integers(0, 3)
+                lo[a], hi[a] = (-3, max(hi[a] - lo[a], 1)) if rng.random() < 0.5 else (self.dim - max(hi[a] - lo[a], 1), self.dim + 5)
+            if kind == "empty":
+                a = rng.integers(0, 3)
+                hi[a] = lo[a] - rng.integers(0, 2)
+                break
+            box = clip_box(lo, hi, m.depth)
+            if box is None or not fill or int(np.prod([u - l for l, u in zip(*box)], dtype=object)) <= FILL_VOXELS:
+                break
+            side_max = max(side_max >> 1, 1)
+        return tuple(int(v) for v in lo), tuple(int(v) for v in hi)
+
+    def fill_box_op(self, id=None, centre=None, over=0.15):
+        """Budget-aware: mostly a box that the capacity admits, some on purpose over it."""
+        m, rng = self.m, self.rng
+        if id is None:
+            id = 0 if rng.random() < 0.5 else int(self.ids(1, odd=0.2)[0])
+        want_over = rng.random() < over
+        for _ in range(12):
+            lo, hi = self.region_box(bool(id), centre)
+            what = m.fill_plan(lo, hi, id)[5]
+            if what is None or (what == REFUSED and want_over) or (what == INVALID and rng.random() < 0.1):
+                break
+        else:
+            c = self.some_cell() if centre is None else np.asarray(centre, np.int64)
+            lo, hi = tuple(int(v) for v in c), tuple(int(v) + 1 for v in c)
+        return {"op": "fill_box", "lo": lo, "hi": hi, "id": id}
+
+    def restore_box_op(self, s=None, centre=None):
+        if s is None:
+            s = self.handle(zero=0.05, other_than=0)
+        lo, hi = self.region_box(False, centre)
+        return {"op": "restore_box", "s": s, "lo": lo, "hi": hi}
+
+    def box_with_need(self, need_of, accept, centres, tries=400):
+        """A box for which accept(need_of(lo, hi)) holds, or None: the scripted refusals and pinned bounds."""
+        for _ in range(tries):
+            lo, hi, _k = self.aligned_box(centres[self.rng.integers(0, len(centres))], self.m.depth, max(self.dim >> 1, 1))
+            lo, hi = tuple(int(v) for v in lo), tuple(int(v) for v in hi)
+            need = need_of(lo, hi)
+            if need is not None and accept(need):
+                return lo, hi
+        return None
+
+    def clear_need(self, lo, hi):
+        box, _, _, _, need, what = self.m.fill_plan(lo, hi, 0)
+        whole = box == ((0, 0, 0), (self.dim,) * 3)
+        return None if box is None or whole or what == INVALID else need
+
+    def restore_need(self, s):
+        def need(lo, hi):
+            box = clip_box(lo, hi, self.m.depth)
+            if box is None or box == ((0, 0, 0), (self.dim,) * 3) or self.m.state(s).root == self.m.now.root:
+                return None
+            front, cubes, _ = self.m.restore_plan(s, box)
+            return front if cubes else None
+        return need
+
+    def centres(self, state=None):
+        cells = list((state or self.m.now).cells)
+        return [np.array(c, np.int64) for c in cells[:200]] or [np.array((0, 0, 0), np.int64)]
+
+    def used_after_compaction(self):
+        m = self.m
+        return 1 + len(m.now.nodes().union(*(st.nodes() for st, _ in m.snapshots.values())))
+
+    def pin_ops(self, kind):
+        """Two strokes that pin the capacity bound from both sides: used + need == capacity + 1, refused, then
+        used + need == capacity, admitted.  kind "fill" (a clear) or "restore" (from the newest snapshot)."""
+        m = self.m
+        free = m.capacity - m.used
+        if kind == "fill":
+            need_of, centres, make = self.clear_need, self.centres(), lambda b: {"op": "fill_box", "lo": b[0], "hi": b[1], "id": 0}
+        else:
+            if not m.snapshots:
+                return []
+            s = max(m.snapshots)
+            need_of, centres = self.restore_need(s), self.centres(m.state(s))
+            make = lambda b: {"op": "restore_box", "s": s, "lo": b[0], "hi": b[1]}
+        over = self.box_with_need(need_of, lambda n: n == free + 1, centres)
+        exact = self.box_with_need(need_of, lambda n: n == free, centres)
+        return [dict(make(b), pin=True) for b in (over, exact) if b is not None]
+
+    def refuse_ops(self, kind):
+        """A stroke that the capacity refuses now and admits after a compaction, if the store holds enough
+        abandoned rows for one; the generator's compact-and-retry does the rest."""
+        m = self.m
+        free, free_then = m.capacity - m.used, m.capacity - self.used_after_compaction()
+        if kind == "fill":
+            need_of, centres, make = self.clear_need, self.centres(), lambda b: {"op": "fill_box", "lo": b[0], "hi": b[1], "id": 0}
+        else:
+            if not m.snapshots:
+                return []
+            s = max(m.snapshots)
+            need_of, centres = self.restore_need(s), self.centres(m.state(s))
+            make = lambda b: {"op": "restore_box", "s": s, "lo": b[0], "hi": b[1]}
+        box = self.box_with_need(need_of, lambda n: free < n <= free_then, centres) if free_then > free else None
+        return [make(box)] if box is not None else []
+
     # -- the other operations
     def handle(self, zero=0.2, other_than=None):
         """A live handle or 0 (the current state); other_than = a handle: mostly a state with another root
@@ -387,6 +717,106 @@ class Generator:
         self.pending.append({"op": "compact"})
         return {"op": "checkout", "s": s}
 
+    # -- the box strokes' sequences
+    def with_pool(self, ops):
+        """The operations behind a make_pool where the walk has no pool yet: they flush and check pool 0."""
+        if not self.pools:
+            self.pools += 1
+            ops = [{"op": "make_pool"}] + ops
+        self.pending.extend(ops[1:])
+        return ops[0]
+
+    def whole(self):
+        return {"lo": (0, 0, 0), "hi": (self.dim,) * 3}
+
+    def script_r_checkout(self):
+        # a checkout that changes the root, then a box stroke: the head's root word is behind the host's
+        s = self.handle(zero=0.0, other_than=0)
+        if self.m.state(s).root == self.m.now.root:
+            return None
+        centre = self.some_cell([self.m.state(s)])
+        follow = self.fill_box_op(id=[0, 3][self.step % 2], centre=centre, over=0) if self.rng.random() < 0.7 else \
+            self.restore_box_op(s=self.handle(zero=0.0, other_than=s), centre=centre)
+        self.pending.append(follow)
+        return {"op": "checkout", "s": s}
+
+    def script_r_whole(self):
+        # the root changes on the host alone (a whole-tree clear, a whole-tree restore): a record stroke, a
+        # flush without new ids, a compaction with the snapshot live and a tighten right after such a change
+        clear, back = dict(self.whole(), op="fill_box", id=0), dict(self.whole(), op="restore_box", s="last")
+        flush, check = {"op": "flush", "pool": 0}, {"op": "check_pool", "pool": 0}
+        return self.with_pool([{"op": "snapshot"}, clear, self.stroke("small_new"), flush, check, back, dict(flush), dict(check),
+                               self.stroke("small_new"), dict(back), {"op": "compact"}, {"op": "tighten"}])
+
+    def script_r_across(self):
+        # a restore from a snapshot whose ids a compaction has renumbered since
+        stroke = self.stroke("small_new")
+        c = stroke["records"][0, :3]
+        self.pending.extend([stroke, {"op": "compact"},
+                             {"op": "restore_box", "s": "last", "lo": tuple(int(v) - 1 for v in c), "hi": tuple(int(v) + 2 for v in c)}])
+        return {"op": "snapshot"}
+
+    def script_r_empty(self):
+        # an empty current state under a restore from a snapshot with voxels, then the reverse
+        if not self.m.cells:
+            return None
+        lo, hi = self.region_box(False, centre=self.some_cell([self.m.now]))
+        self.pending.extend([dict(self.whole(), op="fill_box", id=0), {"op": "snapshot"},
+                             {"op": "restore_box", "s": "prev", "lo": lo, "hi": hi}, {"op": "restore_box", "s": "last", "lo": lo, "hi": hi}])
+        return {"op": "snapshot"}
+
+    def script_r_untouched(self):
+        # the roots differ, and every difference lies outside the box
+        stroke = self.stroke("small_new")
+        touched = [tuple(c) for c in stroke["records"][:, :3].tolist()]
+        for _ in range(40):
+            lo, hi = self.region_box(False, kinds=False)
+            box = clip_box(lo, hi, self.m.depth)
+            if box is not None and box != ((0, 0, 0), (self.dim,) * 3) and not any(in_box(c, box) for c in touched):
+                self.pending.extend([stroke, {"op": "restore_box", "s": "last", "lo": lo, "hi": hi}])
+                return {"op": "snapshot"}
+        return None
+
+    def script_r_uniform(self):
+        # a fill whose uniform subtrees the store holds already, and the same fill after a compaction
+        if self.m.depth < 2:
+            return None
+        T = min(2, self.m.depth - 1)
+        fills = []
+        for c in (self.rng.integers(0, 1 << (self.m.depth - T), (3, 3)) << T).tolist():
+            fills.append({"op": "fill_box", "lo": tuple(c), "hi": tuple(v + (1 << T) for v in c), "id": 2000 + self.step})
+        self.pending.extend(fills[1:2] + [{"op": "compact"}] + fills[2:])
+        return fills[0]
+
+    def script_r_outside(self):
+        # a restore that brings voxels back outside the tightened box, then a frame: the pool's cull box
+        if not self.m.cells:
+            return None
+        c = self.some_cell([self.m.now])
+        half = self.dim >> 1
+        lo = tuple(int(v >= half) * half for v in c)
+        lo, hi = (lo[0], 0, 0), (lo[0] + half, self.dim, self.dim)       # the half of the tree, along x, that holds c
+        return self.with_pool([{"op": "snapshot"}, {"op": "fill_box", "lo": lo, "hi": hi, "id": 0}, {"op": "tighten"},
+                               {"op": "restore_box", "s": "last", "lo": tuple(int(v) - 1 for v in c), "hi": tuple(int(v) + 2 for v in c)},
+                               {"op": "flush", "pool": 0}, {"op": "check_pool", "pool": 0}])
+
+    def script_r_pin_fill(self):
+        self.pending.append({"op": "pin", "kind": "fill"})
+        return {"op": "compact"}
+
+    def script_r_pin_restore(self):
+        if not self.m.cells:
+            return None
+        self.pending.extend([dict(self.whole(), op="fill_box", id=0), {"op": "pin", "kind": "restore"}])
+        return {"op": "snapshot"}
+
+    def script_r_refuse_fill(self):
+        return {"op": "refuse", "kind": "fill"}
+
+    def script_r_refuse_restore(self):
+        self.pending.extend([self.stroke("scatter"), self.stroke("scatter"), {"op": "refuse", "kind": "restore"}])
+        return {"op": "snapshot"}
+
     def next(self):
         self.step += 1
         if self.pending:
@@ -398,15 +828,17 @@ class Generator:
                 return first
         table = [("edit", 30), ("snapshot", 8), ("checkout", 10), ("release", 3), ("compact", 5), ("tighten", 6),
                  ("make_pool", 3), ("flush", 6), ("check_pool", 5), ("diff", 10), ("at", 3), ("read_box", 6),
-                 ("download", 2), ("revert_by_diff", 3)]
+                 ("download", 2), ("revert_by_diff", 3), ("fill_box", 8), ("restore_box", 7)]
         names, weights = zip(*table)
         op = names[rng.choice(len(names), p=np.array(weights) / sum(weights))]
         if op == "edit":
             return self.stroke()
         if op == "checkout":
             s = self.handle(zero=0.1, other_than=0)
-            follow = rng.integers(0, 4)
-            if follow == 0:
+            follow = rng.integers(0, 5)
+            if follow == 4:
+                self.pending.append(self.fill_box_op(over=0) if rng.random() < 0.5 else self.restore_box_op())
+            elif follow == 0:
                 self.pending.append(self.stroke("scatter"))
             elif follow == 1:
                 self.pending.append({"op": "compact"})
@@ -427,6 +859,10 @@ class Generator:
                 self.pools += 1
                 return {"op": "make_pool"}
             return {"op": op, "pool": int(rng.integers(0, self.pools))}
+        if op == "fill_box":
+            return self.fill_box_op()
+        if op == "restore_box":
+            return self.restore_box_op()
         if op == "diff":
             return self.diff_op()
         if op == "at":
@@ -442,7 +878,7 @@ class Generator:
 
     def refused(self, op):
         """The header's advice after a refusal: compact and retry (once; the retry may be refused again)."""
-        if not op.get("retry"):
+        if not op.get("retry") and not op.get("pin"):
             self.pending.appendleft(dict(op, retry=True))
             self.pending.appendleft({"op": "compact"})
 
@@ -474,6 +910,8 @@ class Walk:
         self.last = None               # the operation before this one
         self.last_diff_parents = None
         self.compacted_since_tighten, self.tightened_at = True, None
+        self.trail = []                # the tags of the operations so far: what the sequences' quotas look at
+        self.uniform_fills = {}        # (id, T) of a fill's uniform subtrees -> the generation it ran in
         self.seed = seed
         self.check_info()
         self.check_content()
@@ -532,6 +970,8 @@ class Walk:
                 op = self.gen.next()
                 changed = getattr(self, "do_" + op["op"])(op)
                 self.check_info()
+                self.trail.append(op.get("tags", ()))
+                self.count_sequences()
                 if changed:
                     self.check_content()
                 self.last = op
@@ -539,6 +979,17 @@ class Walk:
             for pool, _ in self.pools:
                 if pool is not None:
                     pool.close()
+
+    SEQUENCES = {"region_after_checkout": ("checkout_moved", "region"),
+                 "seq_whole_clear": ("whole_clear", "stroke", "flush0", "check_pool0"),
+                 "seq_whole_restore": ("whole_restore", "flush0", "check_pool0"),
+                 "seq_whole_restore_compact": ("whole_restore", "compact_snapshots", "tighten"),
+                 "seq_restore_outside_box": ("restore_outside_box", "flush0", "check_pool0")}
+
+    def count_sequences(self):
+        for name, tags in self.SEQUENCES.items():
+            n = len(tags)
+            self.tally[name] += len(self.trail) >= n and all(tag in had for tag, had in zip(tags, self.trail[-n:]))
 
     def after_checkout(self):
         """The operation before this one was a checkout that changed the root (checkout(0) and a checkout of
@@ -563,6 +1014,7 @@ class Walk:
             return True                 # everything unchanged: the content is checked
         if what == "stroke":
             t["admitted"] += 1
+            op["tags"] = ("stroke",)
             named = rec[in_range(rec, m.depth) & (rec[:, 3] != 0)]       # the other reading: every record with id != 0
             lo, hi = before["box_lo"], before["box_hi"]
             if (lo, hi) != ((0, 0, 0), (0, 0, 0)) and len(named):
@@ -580,6 +1032,99 @@ class Walk:
             self.world.edit(rec if self.seed % 2 else to_u32(rec))
         return True
 
+    # -- box strokes
+    def check_region(self, got, want):
+        if not self.has_store:         # a stand-in says what it can: never new_ids
+            want = {k: want[k] for k in got}
+        assert got == want, (got, want, self.last)
+
+    def region_refused(self, op, what, before, call):
+        """The model refused the stroke: the world does, with everything unchanged."""
+        import pytest
+        t = self.tally
+        t["region_refused"] += what == REFUSED
+        t["region_invalid"] += what == INVALID
+        t["region_refused_again"] += what == REFUSED and bool(op.get("retry"))
+        if what == REFUSED:
+            self.gen.refused(op)
+        if self.has_store:
+            with pytest.raises(self.ort.OchError, match="CAPACITY" if what == REFUSED else "INVALID") as e:
+                call()
+            assert e.value.status == (-6 if what == REFUSED else -1)
+        assert self.m.info() == before
+        return True                    # everything unchanged: info and the content are checked
+
+    def alignments(self, st):
+        """The alignments k <= 4 of the clipped box's faces that lie inside the tree: c a multiple of 2^k and no more."""
+        faces = [c for c in st["lo"] + st["hi"] if 0 < c < 1 << self.m.depth]
+        return {k for k in ((c & -c).bit_length() - 1 for c in faces) if k <= 4}
+
+    def do_fill_box(self, op):
+        m, t, lo, hi, id = self.m, self.tally, op["lo"], op["hi"], op["id"]
+        before, cells, root, used = m.info(), m.cells, m.now.root, m.used
+        box, _, _, T, need, _ = m.fill_plan(lo, hi, id)
+        uniform, held = id, T > 0
+        for h in range(T):             # the uniform subtrees of heights 1..T: does the store hold them all?
+            uniform = m.cons.get((h, (uniform,) * 8))
+            held = held and uniform in m.held
+        what, st = m.fill_box(lo, hi, id)
+        kind = "fill" if id else "clear"
+        t["fill_box"] += 1
+        if what in (REFUSED, INVALID):
+            t["bound_refused_" + kind] += bool(op.get("pin")) and what == REFUSED and used + need == m.capacity + 1
+            return self.region_refused(op, what, before, lambda: self.world.fill_box(lo, hi, id))
+        self.check_region(self.world.fill_box(lo, hi, id), st)
+        changed = m.cells != cells
+        t[kind + "_change"] += changed
+        for k in self.alignments(st) if changed else ():
+            t[f"{kind}_k{k}"] += 1
+        t["retry_admitted_" + kind] += bool(op.get("retry")) and what == "fill"
+        t["bound_admitted_" + kind] += bool(op.get("pin")) and what == "fill" and used + need == m.capacity
+        if T > 0:
+            t["fill_uniform_held"] += held and self.uniform_fills.get((id, T)) == m.generation
+            t["fill_uniform_after_compaction"] += self.uniform_fills.get((id, T), m.generation) < m.generation
+            self.uniform_fills[id, T] = m.generation
+        host_only = what == "fill" and not id and box == ((0, 0, 0), (1 << m.depth,) * 3)
+        op["tags"] = ("whole_clear",) if host_only and root else ("region",) if what == "fill" and not host_only else ()
+        return True
+
+    def do_restore_box(self, op):
+        m, t, lo, hi = self.m, self.tally, op["lo"], op["hi"]
+        if isinstance(op["s"], str):
+            op["s"] = sorted(m.snapshots)[{"last": -1, "prev": -2}[op["s"]]]
+        s = op["s"]
+        before, cells, state, used = m.info(), m.cells, m.now, m.used
+        need = self.gen.restore_need(s)(lo, hi)
+        what, st = m.restore_box(s, lo, hi)
+        t["restore_box"] += 1
+        if what == REFUSED:
+            t["bound_refused_restore"] += bool(op.get("pin")) and used + need == m.capacity + 1
+            return self.region_refused(op, what, before, lambda: self.world.restore_box(s, lo, hi))
+        self.check_region(self.world.restore_box(s, lo, hi), st)
+        changed = m.cells != cells
+        t["restore_change"] += changed
+        for k in self.alignments(st) if changed else ():
+            t[f"restore_k{k}"] += 1
+        t["restore_old"] += bool(changed and s and m.snapshots[s][1] < m.generation)
+        t["restore_into_empty"] += changed and not cells
+        t["restore_from_empty"] += bool(changed and not m.state(s).cells)
+        t["restore_no_effect"] += what == "no_effect"
+        t["retry_admitted_restore"] += bool(op.get("retry")) and what == "restore"
+        t["bound_admitted_restore"] += bool(op.get("pin")) and what == "restore" and used + need == m.capacity
+        outside = changed and not box_inside(exact_box(m.cells), state.box)
+        op["tags"] = ((("whole_restore",) if what == "whole" else ("region",) if what == "restore" else ())
+                      + (("restore_outside_box",) if outside else ()))
+        return True
+
+    def do_pin(self, op):
+        ops = self.gen.pin_ops(op["kind"])
+        self.gen.pending.extendleft(reversed(ops))
+        return False
+
+    def do_refuse(self, op):
+        self.gen.pending.extendleft(reversed(self.gen.refuse_ops(op["kind"])))
+        return False
+
     def do_snapshot(self, op):
         assert self.world.snapshot() == self.m.snapshot()
         return False
@@ -589,6 +1134,7 @@ class Walk:
         self.m.checkout(op["s"])
         self.world.checkout(op["s"])
         op["moved"] = self.m.now.root != root
+        op["tags"] = ("checkout_moved",) if op["moved"] else ()
         self.tally["checkout_calls"] += 1
         self.tally["checkout"] += op["moved"]
         return True
@@ -611,6 +1157,7 @@ class Walk:
     def do_compact(self, op):
         m, t = self.m, self.tally
         t["compact"] += 1
+        op["tags"] = ("compact_snapshots",) if m.snapshots else ()
         t["compact_snapshots"] += bool(m.snapshots)
         t["compact_empty_now"] += bool(m.snapshots) and not m.cells and any(st.cells for st, _ in m.snapshots.values())
         t["compact_empty"] += not m.snapshots and not m.cells
@@ -624,6 +1171,7 @@ class Walk:
     def do_tighten(self, op):
         m, t = self.m, self.tally
         t["tighten"] += 1
+        op["tags"] = ("tighten",)
         t["tighten_after_checkout"] += self.after_checkout()
         t["tighten_first"] += self.compacted_since_tighten
         t["tighten_incremental"] += not self.compacted_since_tighten and self.tightened_at != m.strokes
@@ -644,6 +1192,7 @@ class Walk:
     def do_flush(self, op):
         pool, shown = self.pools[op["pool"]]
         self.tally["flush"] += 1
+        op["tags"] = (f"flush{op['pool']}",)
         self.tally["flush_whole"] += shown["generation"] != self.m.generation
         if pool is not None:
             self.world.flush(pool)
@@ -653,6 +1202,7 @@ class Walk:
     def do_check_pool(self, op):
         pool, shown = self.pools[op["pool"]]
         self.tally["check_pool"] += 1
+        op["tags"] = (f"check_pool{op['pool']}",)
         self.tally["check_pool_behind"] += self.m.strokes - shown["strokes"] >= 2
         if pool is None:
             return False
