@@ -16,11 +16,7 @@ from pathlib import Path
 import numpy as np
 
 from ._lib import DiffStats, EditParams, HostPool, OchError, TerrainParams, VoxelParams, call
-
-
-def diff_stats_dict(st: DiffStats) -> dict:
-    """och_diff_stats as NodePool.diff and World.diff return it."""
-    return {"n": int(st.n), "pairs": int(st.pairs), "box_lo": tuple(st.box_lo), "box_hi": tuple(st.box_hi)}
+from ._marshal import host_array, host_pool_result, nodes_arg, records_arg, struct_dict
 
 
 @dataclass
@@ -48,11 +44,11 @@ class NodePool:
         cells there read 0.  dtype is np.uint8 or np.uint32; OchError INVALID names an id that uint8
         cannot hold."""
         lo, hi, shape, kind = _read_box_args(lo, hi, dtype, "NodePool.read_box")
-        nodes = np.ascontiguousarray(self.nodes, np.uint32).reshape(-1, 8)
+        nodes, ptr, n = nodes_arg(self.nodes)
         grid = np.zeros(shape, dtype)
         # an empty grid still names a buffer: the call refuses NULL before it looks at the box
         target = grid if grid.size else np.zeros(1, dtype)
-        call("och_pool_read_box", nodes.ctypes.data, nodes.shape[0], int(self.root), int(self.depth), int(self.index_base),
+        call("och_pool_read_box", ptr, n, int(self.root), int(self.depth), int(self.index_base),
              lo, hi, kind, target.ctypes.data, grid.nbytes)
         return grid
 
@@ -67,18 +63,17 @@ class NodePool:
         if (other.depth, other.index_base) != (self.depth, self.index_base):
             raise ValueError(f"NodePool.diff: depth {other.depth} / index_base {other.index_base} against depth "
                              f"{self.depth} / index_base {self.index_base}")
-        a = np.ascontiguousarray(self.nodes, np.uint32).reshape(-1, 8)
-        b = a if other.nodes is self.nodes else np.ascontiguousarray(other.nodes, np.uint32).reshape(-1, 8)
+        a, a_ptr, a_n = nodes_arg(self.nodes)
+        b, b_ptr, b_n = (a, a_ptr, a_n) if other.nodes is self.nodes else nodes_arg(other.nodes)
         st = DiffStats()
-        args = (a.ctypes.data, a.shape[0], int(self.root), b.ctypes.data, b.shape[0], int(other.root), int(self.depth),
-                int(self.index_base))
+        args = (a_ptr, a_n, int(self.root), b_ptr, b_n, int(other.root), int(self.depth), int(self.index_base))
         call("och_pool_diff", *args, None, 0, C.byref(st))
         out = None
         if records:
             out = np.zeros((st.n, 4), np.uint32)
             if st.n:
                 call("och_pool_diff", *args, out.ctypes.data, st.n, C.byref(st))
-        return out, diff_stats_dict(st)
+        return out, struct_dict(st)
 
     # -- linearised node-pool file: a 64-byte header, then the
     # n x 8 little-endian uint32 slots exactly as och_gpu_pool_create takes them.
@@ -170,47 +165,10 @@ def build_terrain(depth: int, tunnels: bool = True, dedup: bool = True, rand_kin
 def _build(name: str, params) -> NodePool:
     hp = HostPool()
     call(name, C.byref(params), C.byref(hp))
-    try:
-        n = hp.n_nodes
-        arr = np.ctypeslib.as_array(hp.nodes, shape=(n * 8,)).reshape(n, 8).copy()
-    finally:
-        call("och_host_pool_free", C.byref(hp))
-    return NodePool(arr, hp.root, hp.depth, hp.index_base, hp.solid_voxels, list(hp.voxel_hist),
-                    hp.tree_nodes, hp.build_seconds)
+    return NodePool(*host_pool_result(hp))
 
 
 VOXELS_LIST, VOXELS_GRID_U8, VOXELS_GRID_U32 = 0, 1, 2
-
-
-def _device_records(voxels, use_gpu: bool, who: str):
-    """A CUDA tensor of records as (tensor to keep alive, device pointer, n), its writes complete."""
-    if not use_gpu:
-        raise ValueError(f"{who}: a device tensor needs use_gpu=True")
-    import torch
-
-    if voxels.dim() != 2 or voxels.shape[1] != 4 or voxels.dtype not in (torch.int32, torch.uint32):
-        raise ValueError(f"{who}: a device list is an (n, 4) int32 / uint32 tensor, not "
-                         f"{tuple(voxels.shape)} {voxels.dtype}")
-    if voxels.device.index != torch.cuda.current_device():
-        raise ValueError(f"{who}: the tensor is on {voxels.device}, the current device is "
-                         f"{torch.cuda.current_device()}")
-    voxels = voxels.contiguous()
-    torch.cuda.current_stream().synchronize()      # the build reads on a stream of its own
-    return voxels, voxels.data_ptr(), voxels.shape[0]
-
-
-def _host_records(voxels: np.ndarray, who: str) -> np.ndarray:
-    """An (n, 4) integer array of any width as contiguous uint32 records."""
-    if voxels.dtype.kind not in "iu":
-        raise ValueError(f"{who}: records are integers, not {voxels.dtype}")
-    if voxels.dtype.itemsize != 4:
-        wide = voxels.astype(np.int64)
-        if wide.size and not (0 <= wide[:, 3].min() and wide[:, 3].max() <= 0xFFFFFFFF):
-            raise ValueError(f"{who}: a voxel id outside uint32")
-        outside = ((wide[:, :3] < 0) | (wide[:, :3] > 0xFFFFFFFF)).any(axis=1)
-        wide[outside, :3] = 0xFFFFFFFF         # outside any tree: ignored
-        voxels = wide.astype(np.uint32)
-    return np.ascontiguousarray(voxels).view(np.uint32)
 
 
 def _capacity(capacity, who: str) -> int:
@@ -229,31 +187,26 @@ def build_voxels(voxels, depth: int | None = None, use_gpu: bool = False, thread
     depth follows from the side).  A numpy array is host memory; a CUDA torch tensor (int32 / uint32
     records) is read where it lies, on the current device, and needs use_gpu=True.  capacity = node ids
     to reserve, 0 = the exact bound."""
-    if hasattr(voxels, "is_cuda") and not voxels.is_cuda:
-        voxels = voxels.numpy()
+    voxels = host_array(voxels)
     on_device = hasattr(voxels, "is_cuda")
-    if on_device:
-        voxels, ptr, n = _device_records(voxels, use_gpu, "build_voxels")
-        kind = VOXELS_LIST
-    else:
+    if not on_device:
         voxels = np.asarray(voxels)
-        if voxels.ndim == 2 and voxels.shape[1] == 4:
-            voxels = _host_records(voxels, "build_voxels")
-            kind, n = VOXELS_LIST, voxels.shape[0]
-        elif voxels.ndim == 3:
-            side = voxels.shape[0]
-            if voxels.shape != (side, side, side) or side < 2 or side & (side - 1):
-                raise ValueError(f"build_voxels: a grid is cubic with a power-of-two side >= 2, not {voxels.shape}")
-            if voxels.dtype not in (np.uint8, np.uint32):
-                raise ValueError(f"build_voxels: a grid holds uint8 or uint32 ids, not {voxels.dtype}")
-            if depth is not None and 1 << int(depth) != side:
-                raise ValueError(f"build_voxels: depth {depth} does not match a grid of side {side}")
-            depth = side.bit_length() - 1
-            voxels = np.ascontiguousarray(voxels)
-            kind, n = (VOXELS_GRID_U8 if voxels.dtype == np.uint8 else VOXELS_GRID_U32), 0
-        else:
-            raise ValueError(f"build_voxels: an (n, 4) record list or a cubic 3-D grid, not shape {voxels.shape}")
-        ptr = voxels.ctypes.data
+    if on_device or (voxels.ndim == 2 and voxels.shape[1] == 4):
+        voxels, ptr, n, on_device = records_arg(voxels, "build_voxels", use_gpu=use_gpu)
+        kind = VOXELS_LIST
+    elif voxels.ndim == 3:
+        side = voxels.shape[0]
+        if voxels.shape != (side, side, side) or side < 2 or side & (side - 1):
+            raise ValueError(f"build_voxels: a grid is cubic with a power-of-two side >= 2, not {voxels.shape}")
+        if voxels.dtype not in (np.uint8, np.uint32):
+            raise ValueError(f"build_voxels: a grid holds uint8 or uint32 ids, not {voxels.dtype}")
+        if depth is not None and 1 << int(depth) != side:
+            raise ValueError(f"build_voxels: depth {depth} does not match a grid of side {side}")
+        depth = side.bit_length() - 1
+        voxels = np.ascontiguousarray(voxels)
+        kind, ptr, n = (VOXELS_GRID_U8 if voxels.dtype == np.uint8 else VOXELS_GRID_U32), voxels.ctypes.data, 0
+    else:
+        raise ValueError(f"build_voxels: an (n, 4) record list or a cubic 3-D grid, not shape {voxels.shape}")
     if depth is None:
         raise ValueError("build_voxels: a record list needs depth")
     params = VoxelParams(int(depth), kind, ptr, int(n), int(on_device), int(bool(use_gpu)), int(threads),
@@ -276,21 +229,11 @@ def edit_voxels(tree, voxels, use_gpu: bool = False, threads: int = 0, capacity:
             raise OchError(-1, "och_edit_voxels", "a pool with index_base 1 (h_octree form), not an och::octree pool")
         tree = (tree.nodes, tree.root, tree.depth)
     nodes, root, depth = tree
-    nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 8)
-    if hasattr(voxels, "is_cuda") and not voxels.is_cuda:
-        voxels = voxels.numpy()
-    on_device = hasattr(voxels, "is_cuda")
-    if on_device:
-        voxels, ptr, n = _device_records(voxels, use_gpu, "edit_voxels")
-    else:
-        voxels = np.asarray(voxels)
-        if voxels.ndim != 2 or voxels.shape[1] != 4:
-            raise ValueError(f"edit_voxels: an (n, 4) record list, not shape {voxels.shape}")
-        voxels = _host_records(voxels, "edit_voxels")
-        ptr, n = voxels.ctypes.data, voxels.shape[0]
+    nodes, nodes_ptr, n_nodes = nodes_arg(nodes)
+    voxels, ptr, n, on_device = records_arg(voxels, "edit_voxels", use_gpu=use_gpu)
     if not 0 <= int(root) <= 0xFFFFFFFF:
         raise ValueError(f"edit_voxels: root {root} outside uint32")
-    params = EditParams(nodes.ctypes.data, nodes.shape[0], int(root), int(depth), ptr, int(n), int(on_device),
+    params = EditParams(nodes_ptr, n_nodes, int(root), int(depth), ptr, int(n), int(on_device),
                         int(bool(use_gpu)), int(threads), _capacity(capacity, "edit_voxels"))
     return _build("och_edit_voxels", params)
 
@@ -336,19 +279,18 @@ def occupied_box(nodes: np.ndarray, root: int, depth: int, index_base: int = 1):
     """Bounding box of the pool's voxels (och_pool_occupied_box): (lo, hi) in
     voxel units, voxel (x, y, z) inside iff lo <= (x, y, z) < hi; lo = hi = 0
     for a pool without voxels.  The kernels' cull box (OCH_OPT_CULL)."""
-    nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 8)
+    nodes, ptr, n = nodes_arg(nodes)
     lo, hi = (C.c_int32 * 3)(), (C.c_int32 * 3)()
-    call("och_pool_occupied_box", nodes.ctypes.data, nodes.shape[0], int(root), int(depth), int(index_base), lo, hi)
+    call("och_pool_occupied_box", ptr, n, int(root), int(depth), int(index_base), lo, hi)
     return tuple(lo), tuple(hi)
 
 
 def pack_pool(nodes: np.ndarray, root: int, depth: int, index_base: int = 1):
     """The packed device layout of a pool (och_pool_pack): (packed nodes, packed root)."""
-    nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 8)
+    nodes, ptr, n_nodes = nodes_arg(nodes)
     n, r = C.c_uint32(), C.c_uint32()
-    call("och_pool_pack", nodes.ctypes.data, nodes.shape[0], int(root), int(depth), int(index_base), None, 0,
-         C.byref(n), C.byref(r))
+    call("och_pool_pack", ptr, n_nodes, int(root), int(depth), int(index_base), None, 0, C.byref(n), C.byref(r))
     out = np.zeros((n.value, 8), np.uint32)
-    call("och_pool_pack", nodes.ctypes.data, nodes.shape[0], int(root), int(depth), int(index_base), out.ctypes.data,
-         n.value, C.byref(n), C.byref(r))
+    call("och_pool_pack", ptr, n_nodes, int(root), int(depth), int(index_base), out.ctypes.data, n.value, C.byref(n),
+         C.byref(r))
     return out, r.value

@@ -14,37 +14,21 @@ import numpy as np
 
 from . import _lib
 from ._lib import call
-from .tracer import HOctree, _np_ptr
+from ._marshal import ScopedHandle, nodes_arg, struct_dict
+from .tracer import HOctree
 
 
-class Editor:
+class Editor(ScopedHandle):
     """A capacity-bounded, 1-based node pool that supports set() edits."""
+    _destroy = "och_editor_destroy"
 
     def __init__(self, nodes: np.ndarray, root: int, depth: int, capacity: int | None = None):
-        nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1, 8)
+        nodes, ptr, n = nodes_arg(nodes)
         if capacity is None:
-            capacity = max(2 * nodes.shape[0], 64 * int(depth))
+            capacity = max(2 * n, 64 * int(depth))
         self.depth = int(depth)
         self._h = C.c_void_p()
-        call("och_editor_create", _np_ptr(nodes), nodes.shape[0], int(root), self.depth, int(capacity),
-             C.byref(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            call("och_editor_destroy", self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        call("och_editor_create", ptr, n, int(root), self.depth, int(capacity), C.byref(self._h))
 
     def set(self, x: int, y: int, z: int, v: int):
         """h_octree::set (ORT/och_h_octree.h:176-237): voxel (x, y, z) := v, 0 removes."""
@@ -57,7 +41,7 @@ class Editor:
     def stats(self) -> dict:
         st = _lib.EditorStats()
         call("och_editor_info", self._h, C.byref(st))
-        return {f: getattr(st, f) for f, _ in _lib.EditorStats._fields_}
+        return struct_dict(st)
 
     @property
     def root(self) -> int:

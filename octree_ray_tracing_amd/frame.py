@@ -16,6 +16,7 @@ import math
 import numpy as np
 
 from ._lib import COMM_ID_BYTES, EXCHANGE, Camera, call, load
+from ._marshal import Handle, nodes_arg, palette_arg, views
 from .tracer import GpuPool, shard_rows
 
 
@@ -124,13 +125,14 @@ def shade_lit_codes(codes16: np.ndarray, palette, light) -> np.ndarray:
     return shade_lit(code_table(palette)[c & np.uint16(0xFF)], (c >> np.uint16(8)).astype(np.uint8), light)
 
 
-class RcclComm:
+class RcclComm(Handle):
     """The library's own RCCL communicator (och_comm_*): one rank per process
     and GPU, as the driver's torch.distributed launch runs them.  Rank 0 makes
     the id, torch.distributed broadcasts it, every rank joins
     (ncclCommInitRank).  The sharded frame loop (och_gpu_render_sharded_steps_dev)
     exchanges its slices over it, so a frame's render, all-gather and shade
     are issued by one library call with no interpreter between them."""
+    _destroy = "och_comm_destroy"
 
     def __init__(self, uid: bytes, n_ranks: int, rank: int, device: int):
         if len(uid) != COMM_ID_BYTES:
@@ -202,19 +204,8 @@ class RcclComm:
         """ncclCommAbort (och_comm_abort), safe from another thread: this rank's
         collectives stop waiting for peers that never come.  close() still frees
         the handle."""
-        if getattr(self, "_h", None) and self._h.value:
+        if self._live():
             call("och_comm_abort", self._h)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            call("och_comm_destroy", self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class ShardedFrame:
@@ -417,16 +408,17 @@ class ShardedFrame:
         return self.exchange()
 
 
-class FrameGroup:
+class FrameGroup(Handle):
     """One process driving several GPUs (och_frame_group_*, the C++ host's
     form of SURVEY §8(e)): a pool replica per device, each renders its row
     chunks, one RCCL all-gather (ncclCommInitAll over the devices) and a
     shade + unshard per device.  `frames(rank)` is device `rank`'s copy of
     the [views][H][W] RGBA8 frames."""
+    _destroy = "och_frame_group_destroy"
 
     def __init__(self, nodes: np.ndarray, root: int, depth: int, devices=None, index_base: int = 1,
                  miss_t: float | None = None):
-        nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 8)
+        nodes, ptr, n_nodes = nodes_arg(nodes)
         if devices is None:
             from .tracer import device_list
             devices = device_list()
@@ -435,49 +427,32 @@ class FrameGroup:
             miss_t = math.inf if index_base == 1 else 0.0
         self._h = C.c_void_p()
         self.n = len(devices)
-        call("och_frame_group_create", C.cast(devs, C.c_void_p), len(devices), nodes.ctypes.data, nodes.shape[0],
+        call("och_frame_group_create", C.cast(devs, C.c_void_p), len(devices), ptr, n_nodes,
              int(root), int(depth), int(index_base), float(miss_t), C.byref(self._h))
         self._shape = None
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            call("och_frame_group_destroy", self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def set_palette(self, rgba: np.ndarray):
-        rgba = np.ascontiguousarray(rgba, np.uint32).reshape(-1)
-        if rgba.size % 6:
-            raise ValueError("palette must hold 6 colours per voxel id")
-        call("och_frame_group_set_palette", self._h, rgba.ctypes.data, rgba.size // 6)
+        rgba, ptr, n = palette_arg(rgba)
+        call("och_frame_group_set_palette", self._h, ptr, n)
 
     def set_option(self, name: str, value: int):
         call("och_frame_group_set_option", self._h, GpuPool.OPTIONS[name], int(value))
 
     def plan(self, cams, row_chunk: int = 8):
         """Cost-planned launch order on every device (och_frame_group_plan)."""
-        cams = list(cams) if isinstance(cams, (list, tuple)) else [cams]
-        arr = (Camera * len(cams))(*cams)
-        call("och_frame_group_plan", self._h, C.cast(arr, C.c_void_p), len(cams), int(row_chunk))
+        arr, n, _ = views(cams)
+        call("och_frame_group_plan", self._h, arr, n, int(row_chunk))
 
     def render(self, cams, row_chunk: int = 8, bounce: bool = False, light=None):
         """One frame on every device; light: a lit frame (och_frame_group_render_lit), not with bounce."""
         if bounce and light is not None:
             raise ValueError("lit and bounce together are out of scope")
-        cams = list(cams) if isinstance(cams, (list, tuple)) else [cams]
-        arr = (Camera * len(cams))(*cams)
+        arr, n, first = views(cams)
         if light is not None:
-            call("och_frame_group_render_lit", self._h, C.cast(arr, C.c_void_p), len(cams), int(row_chunk),
-                 C.byref(light))
+            call("och_frame_group_render_lit", self._h, arr, n, int(row_chunk), C.byref(light))
         else:
-            call("och_frame_group_render", self._h, C.cast(arr, C.c_void_p), len(cams), int(row_chunk),
-                 int(bool(bounce)))
-        self._shape = (len(cams), cams[0].height, cams[0].width)
+            call("och_frame_group_render", self._h, arr, n, int(row_chunk), int(bool(bounce)))
+        self._shape = (n, first.height, first.width)
 
     def render_steps(self, cams, n_steps: int, n_buffers: int = 3, row_chunk: int = 8, bounce: bool = False,
                      light=None):
@@ -486,15 +461,14 @@ class FrameGroup:
         light); download() gives the last."""
         if bounce and light is not None:
             raise ValueError("lit and bounce together are out of scope")
-        cams = list(cams) if isinstance(cams, (list, tuple)) else [cams]
-        arr = (Camera * len(cams))(*cams)
+        arr, n, first = views(cams)
         if light is not None:
-            call("och_frame_group_render_lit_steps", self._h, C.cast(arr, C.c_void_p), len(cams), int(n_steps),
-                 int(n_buffers), int(row_chunk), C.byref(light))
+            call("och_frame_group_render_lit_steps", self._h, arr, n, int(n_steps), int(n_buffers), int(row_chunk),
+                 C.byref(light))
         else:
-            call("och_frame_group_render_steps", self._h, C.cast(arr, C.c_void_p), len(cams), int(n_steps),
-                 int(n_buffers), int(row_chunk), int(bool(bounce)))
-        self._shape = (len(cams), cams[0].height, cams[0].width)
+            call("och_frame_group_render_steps", self._h, arr, n, int(n_steps), int(n_buffers), int(row_chunk),
+                 int(bool(bounce)))
+        self._shape = (n, first.height, first.width)
 
     def synchronize(self):
         call("och_frame_group_synchronize", self._h)

@@ -20,6 +20,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import Camera, Light, OchError, call
+from ._marshal import (ScopedHandle, _dev_ptr, _need, capacity_of, nodes_arg, palette_arg, rcp_lut_arg, struct_dict,
+                       views)
 
 
 class Direction(enum.IntEnum):
@@ -47,27 +49,6 @@ def _event_handle(e):
     return h.value if hasattr(h, "value") else int(h)
 
 
-def _dev_ptr(t) -> int:
-    """Device pointer of a torch tensor (or an int already)."""
-    if isinstance(t, int):
-        return t
-    if not t.is_cuda:
-        raise ValueError("expected a device tensor")
-    if not t.is_contiguous():
-        raise ValueError("expected a contiguous tensor")
-    return t.data_ptr()
-
-
-def _need(t, nbytes: int, what: str):
-    """A device buffer passed as a tensor must hold what the launch writes or
-    reads: the C ABI takes bare pointers (as the reference's interface takes
-    references), so the sizes are checked here.  Raw pointers pass unchecked."""
-    if hasattr(t, "numel") and hasattr(t, "element_size"):
-        have = t.numel() * t.element_size()
-        if have < nbytes:
-            raise ValueError(f"{what}: the buffer holds {have} B, the launch needs {nbytes} B")
-
-
 def host_rcp_lut() -> np.ndarray:
     """This host's RCPPS (_mm_rcp_ps, ORT/och_h_octree.h:316) as a 2^k table."""
     buf = np.empty(1 << 23, np.uint32)
@@ -77,15 +58,15 @@ def host_rcp_lut() -> np.ndarray:
 
 
 def rcp_from_lut(xbits: int, lut: np.ndarray) -> int:
-    lut = np.ascontiguousarray(lut, np.uint32)
-    return call("och_rcp_from_lut", xbits, _np_ptr(lut), int(round(math.log2(lut.size))))
+    lut, ptr, log2_entries = rcp_lut_arg(lut)
+    return call("och_rcp_from_lut", xbits, ptr, log2_entries)
 
 
 def rcp_lut_error(lut: np.ndarray) -> float:
     """Largest relative error of an RCPPS table over [-2, -1) (och_rcp_lut_error)."""
-    lut = np.ascontiguousarray(lut, np.uint32)
+    lut, ptr, log2_entries = rcp_lut_arg(lut)
     e = C.c_double()
-    call("och_rcp_lut_error", _np_ptr(lut), int(round(math.log2(lut.size))), C.byref(e))
+    call("och_rcp_lut_error", ptr, log2_entries, C.byref(e))
     return e.value
 
 
@@ -119,17 +100,18 @@ def light_check(light: Light) -> None:
     call("och_light_check", C.byref(light))
 
 
-class GpuPool:
+class GpuPool(ScopedHandle):
     """A node pool resident in HBM on one device, traced by the gfx950 kernels."""
+    _destroy = "och_gpu_pool_destroy"
 
     def __init__(self, nodes: np.ndarray, root: int, depth: int, index_base: int = 1,
                  miss_t: float | None = None, device: int = -1):
-        nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1, 8)
+        nodes, ptr, n = nodes_arg(nodes)
         if miss_t is None:
             miss_t = math.inf if index_base == 1 else 0.0
         self.depth, self.index_base, self.miss_t = int(depth), int(index_base), float(miss_t)
         self._h = C.c_void_p()
-        call("och_gpu_pool_create", _np_ptr(nodes), nodes.shape[0], int(root), int(depth),
+        call("och_gpu_pool_create", ptr, n, int(root), int(depth),
              int(index_base), float(miss_t), int(device), C.byref(self._h))
         self._palette_n = 0
 
@@ -142,45 +124,25 @@ class GpuPool:
         pool._palette_n = 0
         return pool
 
-    # -- lifetime
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            call("och_gpu_pool_destroy", self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     # -- configuration
     def info(self) -> dict:
         inf = _lib.PoolInfo()
         call("och_gpu_pool_info", self._h, C.byref(inf))
-        return {f: getattr(inf, f) for f, _ in _lib.PoolInfo._fields_}
+        return struct_dict(inf)
 
     def get_root(self) -> int:
         return self.info()["root"]
 
     def set_rcp_lut(self, lut: np.ndarray):
-        lut = np.ascontiguousarray(lut, np.uint32).reshape(-1)
-        if lut.size < 2 or lut.size & (lut.size - 1):
+        if np.size(lut) < 2 or np.size(lut) & (np.size(lut) - 1):
             raise ValueError("RCPPS table size must be a power of two")
-        call("och_gpu_set_rcp_lut", self._h, _np_ptr(lut), int(round(math.log2(lut.size))))
+        lut, ptr, log2_entries = rcp_lut_arg(lut)
+        call("och_gpu_set_rcp_lut", self._h, ptr, log2_entries)
 
     def set_palette(self, rgba: np.ndarray):
-        rgba = np.ascontiguousarray(rgba, np.uint32).reshape(-1)
-        if rgba.size % 6:
-            raise ValueError("palette must hold 6 colours per voxel id")
-        call("och_gpu_set_palette", self._h, _np_ptr(rgba), rgba.size // 6)
-        self._palette_n = rgba.size // 6
+        rgba, ptr, n = palette_arg(rgba)
+        call("och_gpu_set_palette", self._h, ptr, n)
+        self._palette_n = n
 
     def set_stream(self, stream):
         """Enqueue _dev work on a caller stream (torch.cuda.Stream or raw handle)."""
@@ -188,8 +150,8 @@ class GpuPool:
         call("och_gpu_set_stream", self._h, C.c_void_p(handle))
 
     def update(self, first: int, nodes: np.ndarray, root: int):
-        nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 8)
-        call("och_gpu_pool_update", self._h, int(first), nodes.shape[0], _np_ptr(nodes), int(root))
+        nodes, ptr, n = nodes_arg(nodes)
+        call("och_gpu_pool_update", self._h, int(first), n, ptr, int(root))
 
     # och_option (include/och_gpu.h); ids 0, 2, 3, 7, 9, 12, 13 were retired arms
     OPTIONS = {"block": 1, "layout": 4, "tile_order": 5, "bounce_compact": 6, "cull": 8, "timing": 10, "plan": 11,
@@ -256,43 +218,37 @@ class GpuPool:
 
     def trace_batch_dev(self, origins, dirs, hit_dir, hit_voxel, hit_time, push=None, n=None):
         """Device buffers (torch tensors), asynchronous on the pool's stream."""
-        if n is None:
-            n = dirs.numel() // 3
-        stride = 0 if origins.numel() == 3 else 3
-        self._need_batch(origins, dirs, n, stride, (hit_dir, hit_voxel, hit_time, push))
-        call("och_gpu_trace_batch_dev", self._h, _dev_ptr(origins), stride, _dev_ptr(dirs), int(n),
-             _dev_ptr(hit_dir), _dev_ptr(hit_voxel), _dev_ptr(hit_time),
-             None if push is None else _dev_ptr(push))
+        self._batch("och_gpu_trace_batch_dev", origins, dirs, n, (), (hit_dir, hit_voxel, hit_time), push)
 
     def trace_batch_tiled_dev(self, origins, dirs, width: int, hit_dir, hit_voxel, hit_time, push=None, n=None):
         """trace_batch_dev for rays laid out as a row-major image `width` wide: one 8x8 tile of
         neighbouring rays per wavefront (och_gpu_trace_batch_tiled_dev); records in the caller's order."""
-        if n is None:
-            n = dirs.numel() // 3
-        stride = 0 if origins.numel() == 3 else 3
-        self._need_batch(origins, dirs, n, stride, (hit_dir, hit_voxel, hit_time, push))
-        call("och_gpu_trace_batch_tiled_dev", self._h, _dev_ptr(origins), stride, _dev_ptr(dirs), int(n), int(width),
-             _dev_ptr(hit_dir), _dev_ptr(hit_voxel), _dev_ptr(hit_time), None if push is None else _dev_ptr(push))
+        self._batch("och_gpu_trace_batch_tiled_dev", origins, dirs, n, (int(width),), (hit_dir, hit_voxel, hit_time),
+                    push)
 
     def plan_batch_tiled(self, origins, dirs, width: int, n=None):
         """Plan the launch order of tiled batches of this geometry (och_gpu_plan_batch_tiled); used with
         set_option("tile_order", 2).  Synchronous."""
-        if n is None:
-            n = dirs.numel() // 3
-        stride = 0 if origins.numel() == 3 else 3
-        call("och_gpu_plan_batch_tiled", self._h, _dev_ptr(origins), stride, _dev_ptr(dirs), int(n), int(width))
+        self._batch("och_gpu_plan_batch_tiled", origins, dirs, n, (int(width),))
 
     def trace_bounce_batch_dev(self, origins, dirs, hit_dir, hit_voxel, hit_time, bounce_dir, bounce_voxel,
                                bounce_time, push=None, n=None):
         """Config 5: primary + one mirrored secondary ray per hit (device tensors, async)."""
+        self._batch("och_gpu_trace_bounce_batch_dev", origins, dirs, n, (),
+                    (hit_dir, hit_voxel, hit_time, bounce_dir, bounce_voxel, bounce_time), push)
+
+    def _batch(self, name, origins, dirs, n, width, records=None, push=None):
+        """A batch entry's call: n rays (default: what dirs holds) from one shared origin (stride 0) or one
+        each, `width` spliced in where the entry takes one; records: the buffers the launch writes, followed
+        by push (None: no such buffer), for an entry that has them."""
         if n is None:
             n = dirs.numel() // 3
         stride = 0 if origins.numel() == 3 else 3
-        self._need_batch(origins, dirs, n, stride, (hit_dir, hit_voxel, hit_time, bounce_dir, bounce_voxel,
-                                                    bounce_time, push))
-        call("och_gpu_trace_bounce_batch_dev", self._h, _dev_ptr(origins), stride, _dev_ptr(dirs), int(n),
-             _dev_ptr(hit_dir), _dev_ptr(hit_voxel), _dev_ptr(hit_time), _dev_ptr(bounce_dir),
-             _dev_ptr(bounce_voxel), _dev_ptr(bounce_time), None if push is None else _dev_ptr(push))
+        outs = ()
+        if records is not None:
+            self._need_batch(origins, dirs, n, stride, (*records, push))
+            outs = (*[_dev_ptr(r) for r in records], None if push is None else _dev_ptr(push))
+        call(name, self._h, _dev_ptr(origins), stride, _dev_ptr(dirs), int(n), *width, *outs)
 
     @staticmethod
     def _need_batch(origins, dirs, n, stride, outs):
@@ -302,10 +258,15 @@ class GpuPool:
             if o is not None:
                 _need(o, 4 * int(n), "hit records")
 
-    def _need_frames(self, buf, cams, row_chunk, shard, n_shards, bytes_per_pixel, what):
-        cams = cams if isinstance(cams, (list, tuple)) else [cams]
-        rows = self.slice_rows(cams[0].height, int(row_chunk), int(n_shards))
-        _need(buf, len(cams) * rows * cams[0].width * bytes_per_pixel, what)
+    @staticmethod
+    def _frame_views(cams, row_chunk):
+        """views(cams) and the row chunk, by default the whole frame as one chunk."""
+        arr, n, first = views(cams)
+        return arr, n, first, int(first.height if row_chunk is None else row_chunk)
+
+    def _need_frames(self, buf, n, first, row_chunk, n_shards, bytes_per_pixel, what):
+        """A shard's slices hold whole row chunks: n views of slice_rows rows each."""
+        _need(buf, n * self.slice_rows(first.height, row_chunk, int(n_shards)) * first.width * bytes_per_pixel, what)
 
     # -- frame path
     def raygen_dev(self, cam: Camera, dirs):
@@ -320,44 +281,50 @@ class GpuPool:
 
     def render_dev(self, cam: Camera, rgba_slice, row_chunk: int | None = None, shard: int = 0,
                    n_shards: int = 1):
-        if row_chunk is None:
-            row_chunk = cam.height
-        self._need_frames(rgba_slice, cam, row_chunk, shard, n_shards, 4, "rgba_slice")
-        call("och_gpu_render_dev", self._h, C.byref(cam), _dev_ptr(rgba_slice), int(row_chunk),
+        row_chunk = int(cam.height if row_chunk is None else row_chunk)
+        self._need_frames(rgba_slice, 1, cam, row_chunk, n_shards, 4, "rgba_slice")
+        call("och_gpu_render_dev", self._h, C.byref(cam), _dev_ptr(rgba_slice), row_chunk,
              int(shard), int(n_shards))
 
     def render_views_dev(self, cams, rgba_slices, row_chunk: int | None = None, shard: int = 0, n_shards: int = 1):
         """Several equal-size cameras in one launch; rgba_slices holds the views' slices back to back."""
-        arr = (Camera * len(cams))(*cams)
-        if row_chunk is None:
-            row_chunk = cams[0].height
-        self._need_frames(rgba_slices, cams, row_chunk, shard, n_shards, 4, "rgba_slices")
-        call("och_gpu_render_views_dev", self._h, C.cast(arr, C.c_void_p), len(cams), _dev_ptr(rgba_slices),
-             int(row_chunk), int(shard), int(n_shards))
+        self._plain_views("och_gpu_render_views_dev", cams, rgba_slices, 4, "rgba_slices", row_chunk, shard, n_shards)
+
+    def _plain_views(self, name, cams, buf, bytes_per_pixel, what, row_chunk, shard, n_shards, *bounce):
+        arr, n, first, row_chunk = self._frame_views(cams, row_chunk)
+        self._need_frames(buf, n, first, row_chunk, n_shards, bytes_per_pixel, what)
+        call(name, self._h, arr, n, _dev_ptr(buf), row_chunk, int(shard), int(n_shards), *bounce)
 
     def render_ssaa(self, cam: Camera, s: int) -> np.ndarray:
         """The frame of `cam` (the sample grid's camera: width and height multiples of s = 2, 4 or 8)
         supersampled s x s: (H / s, W / s) uint32, each byte the rounded mean of its block's samples
         (och_gpu_render_ssaa; frame.box_downsample states the definition on the host)."""
+        return self._ssaa("och_gpu_render_ssaa", cam, None, s)
+
+    def _ssaa(self, name, cam, light, s):
         s = int(s)
         out = np.empty((cam.height // s, cam.width // s) if s > 0 else (0, 0), np.uint32)
-        call("och_gpu_render_ssaa", self._h, C.byref(cam), s, _np_ptr(out), out.size)
+        call(name, self._h, C.byref(cam), *self._lit(light), s, _np_ptr(out), out.size)
         return out
+
+    @staticmethod
+    def _lit(light) -> tuple:
+        """The light a lit entry takes after its cameras, spliced into the unlit entry's arguments."""
+        return () if light is None else (C.byref(light),)
 
     def render_ssaa_views_dev(self, cams, s: int, rgba, capacity_pixels: int | None = None):
         """Several equal-size sample-grid cameras supersampled s x s in one launch (och_gpu_render_ssaa_views_dev):
         rgba (a device tensor of 4-byte words, or a raw pointer with capacity_pixels) receives the views'
         (H / s) x (W / s) frames back to back.  Asynchronous on the pool's stream."""
-        arr = (Camera * len(cams))(*cams)
+        self._ssaa_views("och_gpu_render_ssaa_views_dev", cams, None, s, rgba, capacity_pixels)
+
+    def _ssaa_views(self, name, cams, light, s, rgba, capacity_pixels):
+        arr, n, first = views(cams)
         s = int(s)
-        if s in (2, 4, 8) and cams:              # any other s the library refuses before it touches rgba
-            _need(rgba, 4 * len(cams) * (cams[0].width // s) * (cams[0].height // s), "rgba")
-        if capacity_pixels is None:
-            if not (hasattr(rgba, "numel") and hasattr(rgba, "element_size")):
-                raise ValueError("a raw pointer needs capacity_pixels")
-            capacity_pixels = rgba.numel() * rgba.element_size() // 4
-        call("och_gpu_render_ssaa_views_dev", self._h, C.cast(arr, C.c_void_p), len(cams), s, _dev_ptr(rgba),
-             int(capacity_pixels))
+        if s in (2, 4, 8) and n:                 # any other s the library refuses before it touches rgba
+            _need(rgba, 4 * n * (first.width // s) * (first.height // s), "rgba")
+        capacity_pixels = capacity_of(rgba, 4, capacity_pixels)
+        call(name, self._h, arr, n, *self._lit(light), s, _dev_ptr(rgba), capacity_pixels)
 
     def render_lit(self, cam: Camera, light: Light) -> np.ndarray:
         """The frame of `cam` with every face hit shaded by sun shadow and ambient occlusion
@@ -367,16 +334,11 @@ class GpuPool:
         return out
 
     def _lit_views(self, name, cams, light, buf, bytes_per_pixel, capacity_pixels, row_chunk, shard, n_shards):
-        arr = (Camera * len(cams))(*cams)
-        if row_chunk is None:
-            row_chunk = cams[0].height
-        self._need_frames(buf, list(cams), row_chunk, shard, n_shards, bytes_per_pixel, name)
-        if capacity_pixels is None:
-            if not (hasattr(buf, "numel") and hasattr(buf, "element_size")):
-                raise ValueError("a raw pointer needs capacity_pixels")
-            capacity_pixels = buf.numel() * buf.element_size() // bytes_per_pixel
-        call(name, self._h, C.cast(arr, C.c_void_p), len(cams), C.byref(light), _dev_ptr(buf), int(capacity_pixels),
-             int(row_chunk), int(shard), int(n_shards))
+        arr, n, first, row_chunk = self._frame_views(cams, row_chunk)
+        self._need_frames(buf, n, first, row_chunk, n_shards, bytes_per_pixel, name)
+        capacity_pixels = capacity_of(buf, bytes_per_pixel, capacity_pixels)
+        call(name, self._h, arr, n, C.byref(light), _dev_ptr(buf), capacity_pixels, row_chunk, int(shard),
+             int(n_shards))
 
     def render_lit_views_dev(self, cams, light: Light, rgba_slices, capacity_pixels: int | None = None,
                              row_chunk: int | None = None, shard: int = 0, n_shards: int = 1):
@@ -423,48 +385,20 @@ class GpuPool:
     def render_lit_steps_dev(self, cams, light: Light, frames, streams, n_steps: int, events=None,
                              row_chunk: int | None = None):
         """render_steps_dev with every frame a lit frame (och_gpu_render_lit_steps_dev)."""
-        if len(frames) != len(streams) or not frames:
-            raise ValueError("one stream per frame buffer")
-        arr = (Camera * len(cams))(*cams)
-        if row_chunk is None:
-            row_chunk = cams[0].height
-        sp = (C.c_void_p * len(streams))(*[getattr(s_, "cuda_stream", s_) for s_ in streams])
-        for f in frames:
-            self._need_frames(f, list(cams), row_chunk, 0, 1, 4, "frames")
-        fp = (C.c_void_p * len(frames))(*[_dev_ptr(f) for f in frames])
-        e0 = e1 = None
-        if events is not None:
-            if len(events) != n_steps:
-                raise ValueError("one event pair per step")
-            e0 = (C.c_void_p * n_steps)(*[_event_handle(a) for a, _ in events])
-            e1 = (C.c_void_p * n_steps)(*[_event_handle(b) for _, b in events])
-        call("och_gpu_render_lit_steps_dev", self._h, C.cast(arr, C.c_void_p), len(cams), C.byref(light), int(n_steps),
-             sp, fp, len(frames), e0, e1, int(row_chunk))
+        self._steps("och_gpu_render_lit_steps_dev", cams, light, frames, streams, n_steps, events, row_chunk)
 
     def render_lit_ssaa(self, cam: Camera, light: Light, s: int) -> np.ndarray:
         """The lit frame of `cam` (the sample grid's camera, as for render_ssaa) supersampled s x s:
         (H / s, W / s) uint32, every sample shaded as render_lit shades it, then the rounded mean
         (och_gpu_render_lit_ssaa; box_downsample(shade_lit(...)) states it on the host)."""
-        s = int(s)
-        out = np.empty((cam.height // s, cam.width // s) if s > 0 else (0, 0), np.uint32)
-        call("och_gpu_render_lit_ssaa", self._h, C.byref(cam), C.byref(light), s, _np_ptr(out), out.size)
-        return out
+        return self._ssaa("och_gpu_render_lit_ssaa", cam, light, s)
 
     def render_lit_ssaa_views_dev(self, cams, light: Light, s: int, rgba, capacity_pixels: int | None = None):
         """Several equal-size sample-grid cameras, lit and supersampled s x s in one launch
         (och_gpu_render_lit_ssaa_views_dev): rgba (a device tensor of 4-byte words, or a raw pointer with
         capacity_pixels) receives the views' (H / s) x (W / s) frames back to back.  Asynchronous on the
         pool's stream."""
-        arr = (Camera * len(cams))(*cams)
-        s = int(s)
-        if s in (2, 4, 8) and cams:              # any other s the library refuses before it touches rgba
-            _need(rgba, 4 * len(cams) * (cams[0].width // s) * (cams[0].height // s), "rgba")
-        if capacity_pixels is None:
-            if not (hasattr(rgba, "numel") and hasattr(rgba, "element_size")):
-                raise ValueError("a raw pointer needs capacity_pixels")
-            capacity_pixels = rgba.numel() * rgba.element_size() // 4
-        call("och_gpu_render_lit_ssaa_views_dev", self._h, C.cast(arr, C.c_void_p), len(cams), C.byref(light), s,
-             _dev_ptr(rgba), int(capacity_pixels))
+        self._ssaa_views("och_gpu_render_lit_ssaa_views_dev", cams, light, s, rgba, capacity_pixels)
 
     def render_steps_dev(self, cams, frames, streams, n_steps: int, events=None, row_chunk: int | None = None,
                          bounce: bool = False):
@@ -472,14 +406,16 @@ class GpuPool:
         (och_gpu_render_steps_dev): frame k on streams[k % B] into frames[k % B],
         B = len(frames) = len(streams); events = n_steps (start, stop) pairs of HIP
         events (raw handles or objects with ``h``) recorded by each frame's dispatch."""
+        self._steps("och_gpu_render_steps_dev", cams, None, frames, streams, n_steps, events, row_chunk,
+                    int(bool(bounce)))
+
+    def _steps(self, name, cams, light, frames, streams, n_steps, events, row_chunk, *bounce):
         if len(frames) != len(streams) or not frames:
             raise ValueError("one stream per frame buffer")
-        arr = (Camera * len(cams))(*cams)
-        if row_chunk is None:
-            row_chunk = cams[0].height
+        arr, n, first, row_chunk = self._frame_views(cams, row_chunk)
         sp = (C.c_void_p * len(streams))(*[getattr(s_, "cuda_stream", s_) for s_ in streams])
         for f in frames:
-            self._need_frames(f, list(cams), row_chunk, 0, 1, 4, "frames")
+            self._need_frames(f, n, first, row_chunk, 1, 4, "frames")
         fp = (C.c_void_p * len(frames))(*[_dev_ptr(f) for f in frames])
         e0 = e1 = None
         if events is not None:
@@ -487,27 +423,19 @@ class GpuPool:
                 raise ValueError("one event pair per step")
             e0 = (C.c_void_p * n_steps)(*[_event_handle(a) for a, _ in events])
             e1 = (C.c_void_p * n_steps)(*[_event_handle(b) for _, b in events])
-        call("och_gpu_render_steps_dev", self._h, C.cast(arr, C.c_void_p), len(cams), int(n_steps), sp, fp,
-             len(frames), e0, e1, int(row_chunk), int(bool(bounce)))
+        call(name, self._h, arr, n, *self._lit(light), int(n_steps), sp, fp, len(frames), e0, e1, row_chunk, *bounce)
 
     def plan_views(self, cams, row_chunk: int | None = None, shard: int = 0, n_shards: int = 1):
         """Plan the launch order of frames of this geometry (och_gpu_plan_views); used with
         set_option("tile_order", 2).  Synchronous."""
-        arr = (Camera * len(cams))(*cams)
-        if row_chunk is None:
-            row_chunk = cams[0].height
-        call("och_gpu_plan_views", self._h, C.cast(arr, C.c_void_p), len(cams), int(row_chunk), int(shard),
-             int(n_shards))
+        arr, n, _, row_chunk = self._frame_views(cams, row_chunk)
+        call("och_gpu_plan_views", self._h, arr, n, row_chunk, int(shard), int(n_shards))
 
     def render_bounce_views_dev(self, cams, rgba_slices, row_chunk: int | None = None, shard: int = 0,
                                 n_shards: int = 1):
         """Config 5 frames: one bounce per hit pixel, shaded (see och_gpu_render_bounce_views_dev)."""
-        arr = (Camera * len(cams))(*cams)
-        if row_chunk is None:
-            row_chunk = cams[0].height
-        self._need_frames(rgba_slices, cams, row_chunk, shard, n_shards, 4, "rgba_slices")
-        call("och_gpu_render_bounce_views_dev", self._h, C.cast(arr, C.c_void_p), len(cams), _dev_ptr(rgba_slices),
-             int(row_chunk), int(shard), int(n_shards))
+        self._plain_views("och_gpu_render_bounce_views_dev", cams, rgba_slices, 4, "rgba_slices", row_chunk, shard,
+                          n_shards)
 
     # Row deal (och_gpu_set_row_deal): which shard renders each row chunk.
     def set_row_deal(self, height: int, row_chunk: int, n_shards: int, chunk_shard=None):
@@ -528,10 +456,9 @@ class GpuPool:
 
     def chunk_costs(self, cams, row_chunk: int) -> np.ndarray:
         """Per-row-chunk cost of these views from one timed render (och_gpu_chunk_costs)."""
-        cams = list(cams) if isinstance(cams, (list, tuple)) else [cams]
-        arr = (Camera * len(cams))(*cams)
-        out = np.empty(-(-cams[0].height // int(row_chunk)), np.float32)
-        call("och_gpu_chunk_costs", self._h, C.cast(arr, C.c_void_p), len(cams), int(row_chunk), _np_ptr(out))
+        arr, n, first = views(cams)
+        out = np.empty(-(-first.height // int(row_chunk)), np.float32)
+        call("och_gpu_chunk_costs", self._h, arr, n, int(row_chunk), _np_ptr(out))
         return out
 
     def unshard_dev(self, gathered, frame, width: int, height: int, row_chunk: int, n_shards: int, n_views: int = 1):
@@ -547,12 +474,8 @@ class GpuPool:
 
     def render_codes_views_dev(self, cams, code_slices, row_chunk: int | None = None, shard: int = 0,
                                n_shards: int = 1, bounce: bool = False):
-        arr = (Camera * len(cams))(*cams)
-        if row_chunk is None:
-            row_chunk = cams[0].height
-        self._need_frames(code_slices, cams, row_chunk, shard, n_shards, 1, "code_slices")
-        call("och_gpu_render_codes_views_dev", self._h, C.cast(arr, C.c_void_p), len(cams), _dev_ptr(code_slices),
-             int(row_chunk), int(shard), int(n_shards), int(bool(bounce)))
+        self._plain_views("och_gpu_render_codes_views_dev", cams, code_slices, 1, "code_slices", row_chunk, shard,
+                          n_shards, int(bool(bounce)))
 
     def shade_unshard_dev(self, gathered_codes, frames, width: int, height: int, row_chunk: int, n_shards: int,
                           n_views: int = 1):

@@ -13,17 +13,19 @@ import numpy as np
 
 from . import _lib
 from ._lib import HostPool, OchError, call
-from .builder import VOXELS_GRID_U8, NodePool, _box_args, _capacity, _host_records, _read_box_args, diff_stats_dict
+from ._marshal import ScopedHandle, host_array, host_pool_result, nodes_arg, records_arg, struct_dict
+from .builder import VOXELS_GRID_U8, NodePool, _box_args, _capacity, _read_box_args
 from .tracer import HOctree
 
 
-class World:
+class World(ScopedHandle):
     """A 1-based DAG resident on one GPU: edit() applies a record list as edit_voxels would, make_pool()
     and flush() show it, download() gives the canonical pool, compact() drops what strokes left behind;
     fill_box() and restore_box() set or restore a whole box at a cost that follows its surface;
     at() and read_box() ask it what it holds without a download, tighten() makes its box exact;
     snapshot(), checkout() and release() remember and restore earlier states (UndoStack, below), diff()
     gives what changed between two of them."""
+    _destroy = "och_world_destroy"
 
     def __init__(self, tree, capacity: int | None = None, device: int = -1):
         """tree is a NodePool with index_base 1 or a (nodes, root, depth) tuple in that form, as edit_voxels
@@ -35,34 +37,17 @@ class World:
                 raise OchError(-1, "och_world_create", "a pool with index_base 1 (h_octree form), not an och::octree pool")
             tree = (tree.nodes, tree.root, tree.depth)
         nodes, root, depth = tree
-        nodes = np.ascontiguousarray(nodes, np.uint32).reshape(-1, 8)
+        nodes, ptr, n = nodes_arg(nodes, null_if_empty=True)
         if not 0 <= int(root) <= 0xFFFFFFFF:
             raise ValueError(f"World: root {root} outside uint32")
         self.depth = int(depth)
-        call("och_world_create", nodes.ctypes.data if nodes.size else None, nodes.shape[0], int(root), self.depth,
+        call("och_world_create", ptr, n, int(root), self.depth,
              _capacity(capacity or 0, "World"), int(device), C.byref(self._h))
         self.device = self.info()["device"]
 
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            call("och_world_destroy", self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     @property
     def closed(self) -> bool:
-        return not (getattr(self, "_h", None) and self._h.value)
+        return not self._live()
 
     def _open(self, who: str):
         if self.closed:
@@ -73,34 +58,16 @@ class World:
         """och_world_stats: capacity, used, root, depth, device, strokes, generation, box_lo, box_hi."""
         st = _lib.WorldStats()
         call("och_world_info", self._open("info"), C.byref(st))
-        out = {f: getattr(st, f) for f, _ in _lib.WorldStats._fields_}
-        out["box_lo"], out["box_hi"] = tuple(st.box_lo), tuple(st.box_hi)
-        return out
+        return struct_dict(st)
 
     def edit(self, records) -> None:
         """One stroke: an (n, 4) record list as edit_voxels takes it, a numpy array or a CUDA tensor
         (int32 / uint32) on the world's device.  OchError CAPACITY leaves the world unchanged:
         compact() and retry."""
-        if hasattr(records, "is_cuda") and not records.is_cuda:
-            records = records.numpy()
-        if hasattr(records, "is_cuda"):
-            h = self._open("edit")
-            import torch
-
-            if records.dim() != 2 or records.shape[1] != 4 or records.dtype not in (torch.int32, torch.uint32):
-                raise ValueError(f"World.edit: a device list is an (n, 4) int32 / uint32 tensor, not "
-                                 f"{tuple(records.shape)} {records.dtype}")
-            if records.device.index != self.device:
-                raise ValueError(f"World.edit: the tensor is on {records.device}, the world on device {self.device}")
-            records = records.contiguous()
-            torch.cuda.current_stream(records.device).synchronize()      # the stroke reads on the world's stream
-            call("och_world_edit", h, records.data_ptr(), records.shape[0], 1)
-            return
-        records = np.asarray(records)
-        if records.ndim != 2 or records.shape[1] != 4:
-            raise ValueError(f"World.edit: an (n, 4) record list, not shape {records.shape}")
-        records = _host_records(records, "World.edit")
-        call("och_world_edit", self._open("edit"), records.ctypes.data, records.shape[0], 0)
+        if getattr(records, "is_cuda", False):
+            self._open("edit")                    # a closed world refuses before a device tensor is touched
+        records, ptr, n, on_device = records_arg(records, "World.edit", device=self.device)
+        call("och_world_edit", self._open("edit"), ptr, n, int(on_device))
 
     def make_pool(self) -> HOctree:
         """A device pool of the current world on the world's device (och_world_pool_create); the caller
@@ -118,21 +85,14 @@ class World:
         return it for the same content.  The world is unchanged."""
         hp = HostPool()
         call("och_world_download", self._open("download"), C.byref(hp))
-        try:
-            n = hp.n_nodes
-            arr = np.ctypeslib.as_array(hp.nodes, shape=(n * 8,)).reshape(n, 8).copy()
-        finally:
-            call("och_host_pool_free", C.byref(hp))
-        return NodePool(arr, hp.root, hp.depth, hp.index_base, hp.solid_voxels, list(hp.voxel_hist), hp.tree_nodes,
-                        hp.build_seconds)
+        return NodePool(*host_pool_result(hp))
 
     def at(self, coords):
         """The voxels at (n, 3) coordinates (x, y, z) under the current root, unflushed strokes included
         (och_world_at); a coordinate outside the tree gives 0.  An integer array gives np.uint32 of shape
         (n,); an int32 CUDA tensor on the world's device is read where it lies and gives an int32 CUDA
         tensor holding the ids' bits.  Complete on return."""
-        if hasattr(coords, "is_cuda") and not coords.is_cuda:
-            coords = coords.numpy()
+        coords = host_array(coords)
         if hasattr(coords, "is_cuda"):
             import torch
 
@@ -245,7 +205,7 @@ class World:
         st = _lib.DiffStats()
         call("och_world_diff", h, a, b, None, 0, 0, C.byref(st))      # the summary sizes the output
         if not records:
-            return None, diff_stats_dict(st)
+            return None, struct_dict(st)
         n = int(st.n)
         if device:
             import torch
@@ -255,18 +215,13 @@ class World:
             if n:
                 torch.cuda.current_stream(dev).synchronize()              # the allocation's stream before the world's
                 call("och_world_diff", h, a, b, out.data_ptr(), n, 1, C.byref(st))
-            return out, diff_stats_dict(st)
+            return out, struct_dict(st)
         out = np.zeros((n, 4), np.uint32)
         if n:
             call("och_world_diff", h, a, b, out.ctypes.data, n, 0, C.byref(st))
-        return out, diff_stats_dict(st)
+        return out, struct_dict(st)
 
     # -- regions (och_world_fill_box / och_world_restore_box)
-
-    @staticmethod
-    def _region_stats(st) -> dict:
-        return {"cubes": int(st.cubes), "cells": int(st.cells), "new_ids": int(st.new_ids), "lo": tuple(st.lo),
-                "hi": tuple(st.hi)}
 
     def fill_box(self, lo, hi, id: int) -> dict:
         """One stroke: every voxel of the box lo <= (x, y, z) < hi becomes id (0 removes), as
@@ -281,7 +236,7 @@ class World:
             raise ValueError(f"World.fill_box: id is an integer inside uint32, not {id!r}")
         st = _lib.RegionStats()
         call("och_world_fill_box", h, lo, hi, int(id), C.byref(st))
-        return self._region_stats(st)
+        return struct_dict(st)
 
     def restore_box(self, s: int, lo, hi) -> dict:
         """One stroke: inside the box the content of snapshot s, outside it the current content
@@ -292,7 +247,7 @@ class World:
         lo, hi = _box_args(lo, hi, "World.restore_box")
         st = _lib.RegionStats()
         call("och_world_restore_box", h, s, lo, hi, C.byref(st))
-        return self._region_stats(st)
+        return struct_dict(st)
 
 
 class UndoStack:

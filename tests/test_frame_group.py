@@ -33,6 +33,7 @@ def test_group_one_device_matches_oracle(ort, O, gpu_device, bounce):
     pal = ort.VoxelData().get_colours()
     g = ort.FrameGroup(tree.nodes, tree.root, depth, devices=[0])
     g.set_palette(pal)
+    g.set_option("cull", 1)                     # every replica's option; the cull is exact (and on by default)
     cams = [ort.camera(tuple(ORIGIN), 0.3, p, 1.25, W, H) for p in PITCHES]
     ref_pool = O.OraclePool(tree.nodes, tree.root, depth, 1)
     want = []

@@ -57,6 +57,38 @@ def test_timing_modes_and_launch_events(ort, O, gpu_device):
     pool.close()
 
 
+def test_stamps_occupancy_and_device_list(ort, gpu_device):
+    """The diagnostic wrappers no other GPU test calls, on a depth-3 pool and 16 x 16 frames of two
+    views: a stamp buffer (och_gpu_set_stamp_buffer) gets per-wave records and leaves the frames as
+    the host render gives them, HIP answers the occupancy queries, this device is listed and counted,
+    and the pool's own synchronize waits for its stream."""
+    import torch
+    from test_voxel_builder import random_records
+    tree = ort.build_voxels(random_records(1, 100, 3), depth=3)
+    assert gpu_device in ort.device_list() and ort.device_count() >= len(ort.device_list()) >= 1
+    with ort.HOctree(tree.nodes, tree.root, 3, device=0) as pool:
+        pool.set_palette(ort.VoxelData().get_colours())
+        pool.set_stream(torch.cuda.current_stream())
+        assert pool.occupancy(0) >= 1 and pool.occupancy(2) >= 1
+        cams = [ort.camera((1.5, 1.5, 1.5), 0.3, p, 1.25, 16, 16) for p in (0.0, -0.6)]
+        want = np.stack([pool.render(c) for c in cams])
+        cap = 64                                                # waves; a record is four 8-byte words
+        stamps = torch.zeros(4 * cap, dtype=torch.int64, device="cuda")
+        frames = torch.zeros((2, 16, 16), dtype=torch.int32, device="cuda")
+        pool.set_stamp_buffer(stamps, cap)
+        pool.render_views_dev(cams, frames)
+        pool.set_stamp_buffer(None, 0)
+        pool.synchronize()
+        assert np.array_equal(frames.cpu().numpy().view(np.uint32), want)
+        records = stamps.cpu().numpy().reshape(cap, 4)
+        written = records[records[:, 1] != 0]
+        assert len(written) > 0 and (written[:, 1] >= written[:, 0]).all()   # start and end ticks of a wave
+        stamps.zero_()
+        pool.render_views_dev(cams, frames)                     # the buffer is off again
+        torch.cuda.synchronize()
+        assert not stamps.any()
+
+
 def test_render_steps_native_loop(ort, O, gpu_device):
     """och_gpu_render_steps_dev: the frame loop issued by the library -- frame k
     on stream k % B into buffer k % B, its dispatch recording event pair k --
