@@ -1007,8 +1007,10 @@ OCH_API int och_world_diff(och_world *world, uint64_t from, uint64_t to, void *r
  * ignored; hi[a] <= lo[a] on an axis, or nothing left after clipping, is a
  * stroke that changes nothing (strokes + 1, OCH_OK, stats all 0), as an edit
  * whose records all lie outside the tree.
- * Out of scope: shapes other than boxes; copying a box to another place; fills
- * conditional on the old voxel; replicated worlds. */
+ * A ball (och_world_fill_sphere, och_world_restore_sphere) is the second
+ * shape: the same cubes, cells and levels, classified against a sphere.
+ * Out of scope: shapes other than boxes and balls; copying a box to another
+ * place; fills conditional on the old voxel; replicated worlds. */
 typedef struct och_region_stats {
     uint64_t cubes;      /* child words written: the maximal aligned cubes inside the box that were emitted */
     uint64_t cells;      /* straddling cells expanded = rows rebuilt, summed over the levels */
@@ -1069,6 +1071,73 @@ OCH_API int och_world_fill_box(och_world *world, const int32_t lo[3], const int3
  * and grown on demand, as och_world_diff's. */
 OCH_API int och_world_restore_box(och_world *world, uint64_t snapshot, const int32_t lo[3], const int32_t hi[3],
                                   och_region_stats *stats /* may be NULL */);
+
+/* A ball, in integers and half-voxel units: voxel (x, y, z) has its centre at
+ * (2x+1, 2y+1, 2z+1); centre2[3] is twice the ball's centre (so it may sit on
+ * a voxel's centre, face, edge or corner) and `diameter` counts voxels.  The
+ * voxel is in the ball iff
+ *   (2x+1-centre2[0])^2 + (2y+1-centre2[1])^2 + (2z+1-centre2[2])^2 <= diameter^2.
+ * |centre2[a]| <= 2^24 and diameter <= 2^24, else OCH_E_INVALID: every offset
+ * then stays below 2^24.4 and the sum below 2^51, exact in 64-bit integers,
+ * and the range still reaches a ball over a whole tree of depth 21.  The
+ * aligned cube [c, c + 2^h)^3 is classified per axis, a = 2c+1-centre2 and
+ * b = 2(c+2^h)-1-centre2: its farthest offset is max(|a|, |b|), its nearest
+ * min(|a|, |b|) where a and b have one sign, else 0 for an odd and 1 for an
+ * even centre2[a]; inside iff the farthest offsets' squares sum to at most
+ * diameter^2, outside iff the nearest offsets' squares sum to more, straddling
+ * otherwise (it then holds a voxel inside and a voxel outside; a voxel never
+ * straddles).  The ball's axis box, lo[a] = ceil((centre2[a] - diameter - 1) / 2),
+ * hi[a] = floor((centre2[a] + diameter - 1) / 2) + 1, clipped to the tree, is
+ * a loose superset of its voxels: the lo and hi of the stats, and what the
+ * world's box grows by.
+ *
+ * och_sphere_cubes: och_box_cubes for a ball, its contract in every respect
+ * (host only; ascending height, then ascending key; counts only without keys
+ * and heights; OCH_E_CAPACITY with complete counts and nothing written;
+ * OCH_E_INVALID for a NULL centre2 or count, depth outside 1..21, only one of
+ * keys and heights), and OCH_E_INVALID for the argument range above.  There
+ * are no closed forms: the counts come from the top-down walk itself, counts
+ * only included, so a call costs what the ball's surface holds (cubes + 8 *
+ * cells classifications), not its volume. */
+OCH_API int och_sphere_cubes(const int32_t centre2[3], uint32_t diameter, int depth,
+                             uint64_t *keys, uint8_t *heights, uint64_t capacity,
+                             uint64_t cubes_per_height[22], uint64_t cells_per_height[22], uint64_t *count);
+/* Set every voxel of the ball to id (0 removes; any uint32): the world is left
+ * exactly as och_world_edit of the ball's records would leave it, content and
+ * canonical och_world_download alike; a record stroke of the same ball
+ * afterwards consumes no id.  stats.cubes and stats.cells are
+ * och_sphere_cubes' totals, stats.lo and stats.hi the clipped axis box (all 0
+ * where that is empty).  A ball that covers the tree makes the root the
+ * uniform subtree of height depth, or 0.  OCH_E_CAPACITY, with the world
+ * unchanged, when used + cells + T > capacity, T = the greatest height with a
+ * cube for id != 0, else 0; checked after the walk and before the first
+ * intern: the answer depends on ball and depth alone.  cubes = 0 -- no voxel
+ * of the ball lies in the tree: an empty axis box, diameter 0 with an even
+ * centre2 component, ... -- changes nothing but strokes (+ 1), is never
+ * refused for capacity and leaves the world's box alone.  id != 0 with
+ * cubes > 0 grows the world's box by the clipped axis box; a clear leaves it.
+ * OCH_E_INVALID: a NULL centre2, a NULL or broken world, the argument range,
+ * a height with 2^31 entries or more, a frontier of 2^28 cells or more.
+ * The walk keeps its counts on the device: two read-backs a stroke, of the
+ * walk's totals by height and of the store's head; where a level outgrew the
+ * sizes the walk was launched with, the walk (which interns nothing) runs
+ * again with larger ones. */
+OCH_API int och_world_fill_sphere(och_world *world, const int32_t centre2[3], uint32_t diameter, uint32_t id,
+                                  och_region_stats *stats /* may be NULL */);
+/* Inside the ball the content of `snapshot`, outside it the current content:
+ * och_world_restore_box' contract word for word with "box" read as "ball".
+ * The walk drops every child whose two words are equal; cubes and cells count
+ * only what differs; a restore that finds no differing cube changes nothing
+ * but strokes and is never refused; OCH_E_CAPACITY, with the world unchanged,
+ * when used + the straddling cells the walk expanded > capacity; the world's
+ * box grows by the clipped axis box inside the snapshot's box only when a cube
+ * differed; a ball over the whole tree makes the snapshot's root current, with
+ * cubes = 1.  OCH_E_INVALID as och_world_restore_box, and a NULL centre2 or
+ * the argument range.  One 8-byte read-back per level on the way down, one of
+ * 4 bytes per level on the way up: the cost follows what differs, not the
+ * ball's surface. */
+OCH_API int och_world_restore_sphere(och_world *world, uint64_t snapshot, const int32_t centre2[3], uint32_t diameter,
+                                     och_region_stats *stats /* may be NULL */);
 
 /* ------------------------------------------------------------ editor */
 /* Interactive editing (the demo's place/remove, ORT/test_och_h_octree.cpp:

@@ -294,6 +294,24 @@ inline box_cube_list box_cubes(const int32_t lo[3], const int32_t hi[3], int dep
     return out;
 }
 
+// The same of a ball (och_sphere_cubes, host only): centre2 is twice the
+// centre in voxels, diameter counts voxels.  The counts come from the walk
+// itself, whose cost follows the ball's surface.
+inline box_cube_list sphere_cubes(const int32_t centre2[3], uint32_t diameter, int depth)
+{
+    box_cube_list out;
+    uint64_t n = 0;
+    check(och_sphere_cubes(centre2, diameter, depth, nullptr, nullptr, 0, out.cubes_per_height, out.cells_per_height, &n),
+          "och_sphere_cubes");
+    out.keys.resize(n);
+    out.heights.resize(n);
+    if (n)
+        check(och_sphere_cubes(centre2, diameter, depth, out.keys.data(), out.heights.data(), n, out.cubes_per_height,
+                               out.cells_per_height, &n),
+              "och_sphere_cubes");
+    return out;
+}
+
 // A world that stays on one GPU between brush strokes (och_world_*): edit()
 // applies a record list as edit_voxels would, flush() publishes the stroke's
 // new nodes to a tree made by make_pool(), download() gives the canonical pool;
@@ -382,6 +400,19 @@ public:
     {
         och_region_stats st;
         check(och_world_restore_box(w_, snapshot, lo, hi, &st), "och_world_restore_box");
+        return st;
+    }
+    // The same two strokes for a ball: centre2 is twice the centre in voxels, diameter counts voxels.
+    och_region_stats fill_sphere(const int32_t centre2[3], uint32_t diameter, uint32_t id)
+    {
+        och_region_stats st;
+        check(och_world_fill_sphere(w_, centre2, diameter, id, &st), "och_world_fill_sphere");
+        return st;
+    }
+    och_region_stats restore_sphere(uint64_t snapshot, const int32_t centre2[3], uint32_t diameter)
+    {
+        och_region_stats st;
+        check(och_world_restore_sphere(w_, snapshot, centre2, diameter, &st), "och_world_restore_sphere");
         return st;
     }
 

@@ -73,7 +73,7 @@ class DiffStats(C.Structure):
 
 
 class RegionStats(C.Structure):
-    """och_region_stats: what och_world_fill_box and och_world_restore_box report."""
+    """och_region_stats: what the region strokes (och_world_fill_box, _restore_box, _fill_sphere, _restore_sphere) report."""
     _fields_ = [("cubes", C.c_uint64), ("cells", C.c_uint64), ("new_ids", C.c_uint64), ("lo", C.c_int32 * 3),
                 ("hi", C.c_int32 * 3)]
 
@@ -196,6 +196,9 @@ PROTOTYPES = {
     "och_box_cubes": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_uint64, _P, _P, C.POINTER(C.c_uint64)]),
     "och_world_fill_box": (C.c_int, [_P, _P, _P, _u32, C.POINTER(RegionStats)]),
     "och_world_restore_box": (C.c_int, [_P, C.c_uint64, _P, _P, C.POINTER(RegionStats)]),
+    "och_sphere_cubes": (C.c_int, [_P, _u32, C.c_int, _P, _P, C.c_uint64, _P, _P, C.POINTER(C.c_uint64)]),
+    "och_world_fill_sphere": (C.c_int, [_P, _P, _u32, _u32, C.POINTER(RegionStats)]),
+    "och_world_restore_sphere": (C.c_int, [_P, C.c_uint64, _P, _u32, C.POINTER(RegionStats)]),
     "och_pool_pack": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "och_pool_at": (_u32, [_P, _u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "och_pool_occupied_box": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _P]),

@@ -275,6 +275,57 @@ def box_cubes(lo, hi, depth: int):
     return keys, heights, np.array(cubes[:int(depth) + 1], np.uint64), np.array(cells[:int(depth) + 1], np.uint64)
 
 
+BALL_RANGE = 1 << 24      # |centre2[a]| and the diameter at most (include/och_gpu.h)
+
+
+def _ball_args(centre2, diameter, who: str):
+    """(centre2 as int32[3], diameter) of a ball, refused as the library refuses them."""
+    try:
+        c2 = list(centre2)
+    except TypeError:
+        raise ValueError(f"{who}: centre2 is three integers, not {centre2!r}") from None
+    if len(c2) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in c2):
+        raise ValueError(f"{who}: centre2 is three integers, not {centre2!r}")
+    if isinstance(diameter, bool) or not isinstance(diameter, (int, np.integer)):
+        raise ValueError(f"{who}: diameter is an integer, not {diameter!r}")
+    if any(abs(int(v)) > BALL_RANGE for v in c2) or not 0 <= int(diameter) <= BALL_RANGE:
+        raise ValueError(f"{who}: |centre2| and diameter are at most 2^24, diameter at least 0, not {centre2!r}, {diameter!r}")
+    return (C.c_int32 * 3)(*(int(v) for v in c2)), int(diameter)
+
+
+def sphere_records(centre2, diameter: int, id: int) -> np.ndarray:
+    """The (n, 4) uint32 records (x, y, z, id) of a ball: the voxels (x, y, z) with
+    (2x+1-centre2[0])^2 + (2y+1-centre2[1])^2 + (2z+1-centre2[2])^2 <= diameter^2 (centre2 is twice the
+    centre, diameter counts voxels; all integers), those inside the ball's axis box
+    ceil((centre2 - diameter - 1) / 2) <= (x, y, z) < floor((centre2 + diameter - 1) / 2) + 1, unclipped, in
+    box_records' order: what World.fill_sphere is held to.  A coordinate below 0 wraps as box_records' do."""
+    if isinstance(id, bool) or not isinstance(id, (int, np.integer)) or not 0 <= int(id) <= 0xFFFFFFFF:
+        raise ValueError(f"sphere_records: id is an integer inside uint32, not {id!r}")
+    c2, d = _ball_args(centre2, diameter, "sphere_records")
+    c2 = np.array(c2[:], np.int64)
+    lo, hi = (c2 - d) >> 1, ((c2 + d - 1) >> 1) + 1          # ceil((n - 1) / 2) = floor(n / 2)
+    off = [(2 * np.arange(lo[a], max(hi[a], lo[a]), dtype=np.int64) + 1 - c2[a]) ** 2 for a in range(3)]
+    z, y, x = np.nonzero(off[2][:, None, None] + off[1][None, :, None] + off[0][None, None, :] <= d * d)
+    rec = np.empty((x.size, 4), np.uint32)
+    rec[:, 0], rec[:, 1], rec[:, 2] = (lo[0] + x).astype(np.uint32), (lo[1] + y).astype(np.uint32), (lo[2] + z).astype(np.uint32)
+    rec[:, 3] = int(id)
+    return rec
+
+
+def sphere_cubes(centre2, diameter: int, depth: int):
+    """The maximal aligned cubes of a ball (sphere_records says which voxels) clipped to a tree of `depth`
+    (och_sphere_cubes, host only), in box_cubes' return shape: (keys, heights, cubes_per_height,
+    cells_per_height).  What World.fill_sphere writes and rebuilds.  There are no closed forms: the counts
+    come from the walk, whose cost follows the ball's surface."""
+    c2, d = _ball_args(centre2, diameter, "sphere_cubes")
+    cubes, cells, n = (C.c_uint64 * 22)(), (C.c_uint64 * 22)(), C.c_uint64()
+    call("och_sphere_cubes", c2, d, int(depth), None, None, 0, cubes, cells, C.byref(n))
+    keys, heights = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint8)
+    if n.value:
+        call("och_sphere_cubes", c2, d, int(depth), keys.ctypes.data, heights.ctypes.data, n.value, cubes, cells, C.byref(n))
+    return keys, heights, np.array(cubes[:int(depth) + 1], np.uint64), np.array(cells[:int(depth) + 1], np.uint64)
+
+
 def occupied_box(nodes: np.ndarray, root: int, depth: int, index_base: int = 1):
     """Bounding box of the pool's voxels (och_pool_occupied_box): (lo, hi) in
     voxel units, voxel (x, y, z) inside iff lo <= (x, y, z) < hi; lo = hi = 0

@@ -10,7 +10,7 @@
 // wrapper, the staging and read-back steps); what reads that world back on the
 // device (at, a box to a grid, the exact box) is och_world_read.h; snapshots
 // of that world, checkout and the diff of two roots are och_world_history.h;
-// its box-shaped strokes (fill, clear, restore) are och_world_region.h.
+// its box- and ball-shaped strokes (fill, clear, restore) are och_world_region.h.
 // One translation unit: the headers are included here and nowhere else.
 //
 // The reference builds its tree by recursive create_volume + per-voxel

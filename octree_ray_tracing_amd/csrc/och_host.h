@@ -9,6 +9,7 @@
 #include <utility>
 #include <vector>
 
+#include "och_ball.h"
 #include "och_internal.h"
 
 typedef struct ncclComm *ncclComm_t;    // as <rccl/rccl.h> declares it
@@ -116,6 +117,14 @@ struct BoxCubes {
     int top = -1;                                 // the greatest height with a cube
 };
 BoxCubes box_cube_counts(const int32_t lo[3], const int32_t hi[3], int depth);
+
+// The same of a ball (och_ball.h) for och_sphere_cubes: there are no closed
+// forms, the counts come from the top-down walk itself, whose cost follows the
+// ball's surface.  any, lo, hi: the ball's clipped axis box, a loose superset
+// (n_cubes may be 0 with any set).  keys and heights, both or neither: every
+// cube, ascending height then ascending Morton key, written only while
+// n_cubes <= capacity (the counts are complete either way).
+BoxCubes ball_cube_walk(const int32_t c2[3], uint32_t diameter, int depth, uint64_t *keys, uint8_t *heights, uint64_t capacity);
 
 // n_views views of one positive width and height (och_api.cpp).
 int check_views(const och_camera *cams, int n_views);

@@ -1115,3 +1115,81 @@ OCH_API int och_box_cubes(const int32_t lo[3], const int32_t hi[3], int depth, u
         if (at[h] != first[h] + c.cubes[h]) return fail(OCH_E_INVALID, "och_box_cubes: the walk and the closed forms disagree");
     return OCH_OK;
 }
+
+och::BoxCubes och::ball_cube_walk(const int32_t c2[3], uint32_t diameter, int depth, uint64_t *keys, uint8_t *heights, uint64_t capacity)
+{
+    BoxCubes c;
+    c.any = ball_axis_box(c2, diameter, depth, c.lo, c.hi);
+    if (!c.any) return c;
+    const Ball B = make_ball(c2, diameter);
+    struct Cell {
+        uint64_t key;
+        int32_t o[3];
+    };
+    // top-down, a level's straddling cells in Morton order, child digits ascending: each height's
+    // cubes come out in ascending Morton order; with `at`, height h's go to keys[at[h]...]
+    const auto walk = [&](uint64_t *at) {
+        const Cell root{0, {0, 0, 0}};
+        const int rc = ball_class(B, root.o, depth);
+        if (rc == 2) {   // the whole tree
+            if (at) {
+                keys[at[depth]] = 0;
+                heights[at[depth]++] = (uint8_t)depth;
+            } else {
+                c.cubes[depth] = 1;
+            }
+        }
+        if (rc != 1) return;
+        std::vector<Cell> front{root}, next;
+        for (int H = depth; H >= 1 && !front.empty(); --H) {
+            const int32_t s = (int32_t)1 << (H - 1);
+            if (!at) c.cells[H] = front.size();
+            next.clear();
+            for (const Cell &f : front)
+                for (int k = 0; k < 8; ++k) {
+                    const Cell ch{f.key << 3 | (uint64_t)k, {f.o[0] + (k & 1) * s, f.o[1] + ((k >> 1) & 1) * s, f.o[2] + ((k >> 2) & 1) * s}};
+                    const int cc = ball_class(B, ch.o, H - 1);
+                    if (cc == 1) {
+                        next.push_back(ch);
+                    } else if (cc == 2 && at) {
+                        keys[at[H - 1]] = ch.key;
+                        heights[at[H - 1]++] = (uint8_t)(H - 1);
+                    } else if (cc == 2) {
+                        ++c.cubes[H - 1];
+                    }
+                }
+            front.swap(next);
+        }
+    };
+    walk(nullptr);
+    for (int H = 0; H <= depth; ++H) {
+        c.n_cubes += c.cubes[H];
+        c.n_cells += c.cells[H];
+        if (c.cubes[H]) c.top = H;
+    }
+    if (keys && c.n_cubes && c.n_cubes <= capacity) {
+        uint64_t at[22] = {0};
+        for (int h = 1; h <= depth; ++h) at[h] = at[h - 1] + c.cubes[h - 1];
+        walk(at);
+    }
+    return c;
+}
+
+OCH_API int och_sphere_cubes(const int32_t centre2[3], uint32_t diameter, int depth, uint64_t *keys, uint8_t *heights,
+                             uint64_t capacity, uint64_t cubes_per_height[22], uint64_t cells_per_height[22], uint64_t *count)
+{
+    if (!centre2) return fail(OCH_E_INVALID, "och_sphere_cubes: centre2 is NULL");
+    if (!count) return fail(OCH_E_INVALID, "och_sphere_cubes: count is NULL");
+    if (depth < 1 || depth > 21) return fail(OCH_E_INVALID, "och_sphere_cubes: depth must be 1..21 (a Morton key has 3 * depth bits)");
+    if ((keys == nullptr) != (heights == nullptr) || (!keys && capacity))
+        return fail(OCH_E_INVALID, "och_sphere_cubes: keys and heights go together, and capacity counts their entries");
+    if (const char *range = och::ball_range_error(centre2, diameter)) return fail(OCH_E_INVALID, "och_sphere_cubes: %s", range);
+    const och::BoxCubes c = och::ball_cube_walk(centre2, diameter, depth, keys, heights, capacity);
+    if (cubes_per_height) std::copy(c.cubes, c.cubes + 22, cubes_per_height);
+    if (cells_per_height) std::copy(c.cells, c.cells + 22, cells_per_height);
+    *count = c.n_cubes;
+    if (keys && c.n_cubes > capacity)
+        return fail(OCH_E_CAPACITY, "och_sphere_cubes: %llu cubes, the buffers hold %llu", (unsigned long long)c.n_cubes,
+                    (unsigned long long)capacity);
+    return OCH_OK;
+}

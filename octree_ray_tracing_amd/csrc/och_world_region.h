@@ -1,6 +1,8 @@
 // och_world_region.h -- strokes of a resident world whose shape is a box
-// (och_world_fill_box, och_world_restore_box), at a cost that follows the box's
-// surface.  Included by och_builder.cpp only, after och_world_history.h.
+// (och_world_fill_box, och_world_restore_box) or a ball (och_world_fill_sphere,
+// och_world_restore_sphere), at a cost that follows the shape's surface.
+// Included by och_builder.cpp only, after och_world_history.h.  The text below
+// speaks of the box; a ball is the same walk with another classifier (the end).
 //
 // A box is a union of maximal aligned cubes.  A cube of side 2^h that lies
 // wholly inside the box is one child word at height h: 0 for a clear, the id
@@ -62,8 +64,21 @@
 // A height of 2^31 entries or more is refused; a restore also refuses a
 // frontier of 2^28 cells or more, whose children's counts share a 64-bit word.
 //
-// Out of scope: shapes other than boxes; copying a box to another place; fills
-// conditional on the old voxel; replicated worlds.
+// The walk is generic over the shape: region_class(shape, key, h) is all that
+// k_region_count and k_region_emit ask of it, and a restore is
+// world_restore_region<Shape>.  A ball (RegionBall, och_ball.h) is classified in
+// integers per axis, exactly.  It has no closed forms, and its fill never
+// prunes, so a fill's walk keeps its counts on the device (region_walk_dev):
+// each level's kernels read their frontier's size from the totals the level
+// above left (RegionTotals), their grids and the scan's length are a host-side
+// upper bound (ball_plan), and one read-back after the last level brings every
+// level's totals for the capacity check, the rows and the stats: a fill stroke
+// synchronises twice, for these and for the head.  Nothing rests on the bound:
+// the host holds each level's real frontier against what was launched, top
+// down, and walks again with more where one was cut short.
+//
+// Out of scope: shapes other than boxes and balls; copying a box to another
+// place; fills conditional on the old voxel; replicated worlds.
 #pragma once
 #include "och_world_history.h"
 
@@ -93,11 +108,20 @@ __device__ inline int region_class(const RegionBox &B, uint64_t key, int h)
     return outside ? 0 : inside ? 2 : 1;
 }
 
+// A ball (och_ball.h): the classifier is all a shape needs.
+using RegionBall = och::Ball;
+
+__device__ inline int region_class(const RegionBall &B, uint64_t key, int h)
+{
+    const int32_t c[3] = {(int32_t)(compact3(key) << h), (int32_t)(compact3(key >> 1) << h), (int32_t)(compact3(key >> 2) << h)};
+    return och::ball_class(B, c, h);
+}
+
 // Candidate q = 8 i + k, child k of cell i of the frontier at height H: its
 // key, whether it is a cube or a cell of the next frontier, and (restore) its
 // two words.  An interior word at or above cap reads as empty (k_world_at).
-template <bool kRestore>
-__device__ inline void region_child(const GpuStore &S, const RegionBox &B, const RegionFront &F, int H, size_t q, uint64_t &key,
+template <bool kRestore, class Shape>
+__device__ inline void region_child(const GpuStore &S, const Shape &B, const RegionFront &F, int H, size_t q, uint64_t &key,
                                     uint32_t &wa, uint32_t &wb, bool &cube, bool &cell)
 {
     cube = cell = false;
@@ -122,8 +146,8 @@ __device__ inline void region_child(const GpuStore &S, const RegionBox &B, const
 }
 
 // cnt[i] = cell i's cubes << 32 | its cells of the next frontier.
-template <bool kRestore>
-__global__ __launch_bounds__(256) void k_region_count(GpuStore S, RegionBox B, RegionFront F, int H, uint64_t *__restrict__ cnt)
+template <bool kRestore, class Shape>
+__device__ inline void region_count(const GpuStore &S, const Shape &B, const RegionFront &F, int H, uint64_t *__restrict__ cnt)
 {
     const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t key;
@@ -136,14 +160,20 @@ __global__ __launch_bounds__(256) void k_region_count(GpuStore S, RegionBox B, R
         cnt[q >> 3] = (uint64_t)__popcll((bc >> lane) & 0xFFull) << 32 | (uint64_t)__popcll((bf >> lane) & 0xFFull);
 }
 
+template <bool kRestore, class Shape>
+__global__ __launch_bounds__(256) void k_region_count(GpuStore S, Shape B, RegionFront F, int H, uint64_t *__restrict__ cnt)
+{
+    region_count<kRestore>(S, B, F, H, cnt);
+}
+
 // Survivor j of either kind: pos[] is the inclusive sum of k_region_count's
 // cnt[].  A cube: entry j of height H - 1 (cubes, and for a restore its word
 // under the snapshot).  A cell: cell j of the next frontier.  n_cubes and
 // N.f are what the buffers hold; the counts never exceed them.
-template <bool kRestore>
-__global__ __launch_bounds__(256) void k_region_emit(GpuStore S, RegionBox B, RegionFront F, int H, const uint64_t *__restrict__ pos,
-                                                     uint64_t *__restrict__ cubes, uint32_t *__restrict__ cube_words,
-                                                     uint32_t n_cubes, RegionFront N)
+template <bool kRestore, class Shape>
+__device__ inline void region_emit(const GpuStore &S, const Shape &B, const RegionFront &F, int H, const uint64_t *__restrict__ pos,
+                                   uint64_t *__restrict__ cubes, uint32_t *__restrict__ cube_words, uint32_t n_cubes,
+                                   const RegionFront &N)
 {
     const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t key;
@@ -171,14 +201,72 @@ __global__ __launch_bounds__(256) void k_region_emit(GpuStore S, RegionBox B, Re
     }
 }
 
-// The first frontier: the root cell, key 0, with its two ids.
-__global__ __launch_bounds__(64) void k_region_seed(RegionFront F, uint32_t ra, uint32_t rb, bool restore)
+template <bool kRestore, class Shape>
+__global__ __launch_bounds__(256) void k_region_emit(GpuStore S, Shape B, RegionFront F, int H, const uint64_t *__restrict__ pos,
+                                                     uint64_t *__restrict__ cubes, uint32_t *__restrict__ cube_words,
+                                                     uint32_t n_cubes, RegionFront N)
+{
+    region_emit<kRestore>(S, B, F, H, pos, cubes, cube_words, n_cubes, N);
+}
+
+// A fill's walk with its counts on the device: what the walk of a shape
+// without closed forms knows of its levels.  tot[h] = the cubes of height h
+// << 32 | the cells of height h (the frontier of level h), first[h] = the
+// cubes of the greater heights, where height h's start in the cubes' buffer.
+// Level H's kernels read tot[H] and first[H - 1], which level H + 1's emit (or
+// the seed) wrote a dispatch earlier, and write tot[H - 1] and first[H - 2].
+struct RegionTotals {
+    uint64_t tot[22], first[22];
+};
+
+// k_region_count for `F.f` cells launched, a host-side bound: the real
+// frontier is tot[H]'s cells, the cells beyond it count zero.  A frontier
+// above the bound is cut to it: the level's totals are then too small, which
+// the host sees in tot[H] itself.
+template <class Shape>
+__global__ __launch_bounds__(256) void k_region_count_dev(GpuStore S, Shape B, RegionFront F, int H,
+                                                          const RegionTotals *__restrict__ T, uint64_t *__restrict__ cnt)
+{
+    const uint32_t bound = F.f;
+    F.f = (uint32_t)min((uint64_t)bound, T->tot[H] & 0xFFFFFFFFull);
+    region_count<false>(S, B, F, H, cnt);
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (size_t)F.f * 8 && q < (size_t)bound * 8 && (q & 7u) == 0) cnt[q >> 3] = 0;
+}
+
+// k_region_emit likewise; pos[] has `F.f` entries, the last one the level's
+// totals, which one thread files for the level below.  The cubes go to
+// first[H - 1] of the buffer's n_cubes, and no further.
+template <class Shape>
+__global__ __launch_bounds__(256) void k_region_emit_dev(GpuStore S, Shape B, RegionFront F, int H, const uint64_t *__restrict__ pos,
+                                                         RegionTotals *__restrict__ T, uint64_t *__restrict__ cubes,
+                                                         uint64_t n_cubes, RegionFront N)
+{
+    const uint32_t bound = F.f;
+    const uint64_t first = T->first[H - 1];
+    F.f = (uint32_t)min((uint64_t)bound, T->tot[H] & 0xFFFFFFFFull);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const uint64_t total = pos[bound - 1];
+        T->tot[H - 1] = total;
+        if (H >= 2) T->first[H - 2] = first + (total >> 32);
+    }
+    const uint64_t room = first < n_cubes ? n_cubes - first : 0;
+    region_emit<false>(S, B, F, H, pos, cubes + min(first, n_cubes), nullptr, (uint32_t)min(room, (uint64_t)0xFFFFFFFFull), N);
+}
+
+// The first frontier: the root cell, key 0, with its two ids; T: a walk with
+// device counts starts from one cell of height `depth` and no cube.
+__global__ __launch_bounds__(64) void k_region_seed(RegionFront F, uint32_t ra, uint32_t rb, bool restore, RegionTotals *T, int depth)
 {
     if (blockIdx.x || threadIdx.x) return;
     F.keys[0] = 0;
     if (restore) {
         F.fa[0] = ra;
         F.fb[0] = rb;
+    }
+    if (T) {
+        T->tot[depth] = 1;
+        T->first[depth - 1] = 0;
     }
 }
 
@@ -223,6 +311,7 @@ struct RegionWork {
     uint64_t n_cubes = 0;
     RegionFront front[2] = {};       // .f: what each holds, n_front
     uint64_t *cnt = nullptr, *pos = nullptr;
+    RegionTotals *totals = nullptr;  // a walk with device counts: its levels' totals
     void *temp = nullptr;
     size_t temp_bytes = 0;
 };
@@ -250,7 +339,8 @@ int region_reserve(och_world &w, uint64_t n_cubes, uint64_t n_front, bool restor
         at_fa[s] = place(restore ? n_front * 4 : 0);
         at_fb[s] = place(restore ? n_front * 4 : 0);
     }
-    const size_t at_cnt = place(n_front * 8), at_pos = place(n_front * 8), at_temp = place(R.temp_bytes);
+    const size_t at_cnt = place(n_front * 8), at_pos = place(n_front * 8), at_totals = place(sizeof(RegionTotals)),
+                 at_temp = place(R.temp_bytes);
     if (w.d_region.reserve(bytes) != hipSuccess) return OCH_E_NOMEM;
     uint8_t *p = w.d_region.d;
     R.cubes = reinterpret_cast<uint64_t *>(p + at_cubes);
@@ -261,6 +351,7 @@ int region_reserve(och_world &w, uint64_t n_cubes, uint64_t n_front, bool restor
                                  restore ? reinterpret_cast<uint32_t *>(p + at_fb[s]) : nullptr, (uint32_t)n_front};
     R.cnt = reinterpret_cast<uint64_t *>(p + at_cnt);
     R.pos = reinterpret_cast<uint64_t *>(p + at_pos);
+    R.totals = reinterpret_cast<RegionTotals *>(p + at_totals);
     R.temp = p + at_temp;
     return OCH_OK;
 }
@@ -279,12 +370,12 @@ struct RegionPlan {
 // nothing is read back.  Restore (ra != rb): P is filled in as the levels'
 // totals come back; grow_cubes / grow_front != 0 on return: a level outgrew
 // the buffers, the caller reserves that much and walks again.
-template <bool kRestore>
-int region_walk(och_world &w, const RegionBox &B, const RegionWork &R, uint32_t ra, uint32_t rb, RegionPlan &P, uint64_t *grow_cubes,
+template <bool kRestore, class Shape>
+int region_walk(och_world &w, const Shape &B, const RegionWork &R, uint32_t ra, uint32_t rb, RegionPlan &P, uint64_t *grow_cubes,
                 uint64_t *grow_front)
 {
     const hipStream_t st = w.st;
-    hipLaunchKernelGGL(k_region_seed, dim3(1), dim3(64), 0, st, R.front[0], ra, rb, kRestore);
+    hipLaunchKernelGGL(k_region_seed, dim3(1), dim3(64), 0, st, R.front[0], ra, rb, kRestore, static_cast<RegionTotals *>(nullptr), 0);
     GPU_TRY(hipGetLastError());
     uint32_t f = 1;
     uint64_t at = 0;   // the cubes emitted so far
@@ -298,7 +389,7 @@ int region_walk(och_world &w, const RegionBox &B, const RegionWork &R, uint32_t 
             P.cells[H] = f;
             P.front += f;
         }
-        hipLaunchKernelGGL(k_region_count<kRestore>, blocks((size_t)f * 8), dim3(256), 0, st, w.S, B, F, H, R.cnt);
+        hipLaunchKernelGGL((k_region_count<kRestore, Shape>), blocks((size_t)f * 8), dim3(256), 0, st, w.S, B, F, H, R.cnt);
         GPU_TRY(hipGetLastError());
         size_t tb = R.temp_bytes;
         GPU_TRY(hipcub::DeviceScan::InclusiveSum(R.temp, tb, R.cnt, R.pos, (int)f, st));
@@ -309,7 +400,7 @@ int region_walk(och_world &w, const RegionBox &B, const RegionWork &R, uint32_t 
             P.cells[H - 1] = total & 0xFFFFFFFFull;
             P.first[H - 1] = at;
             if (at + P.cubes[H - 1] >= kRegionLimit || P.cells[H - 1] >= kRegionFrontLimit)
-                return och::report(OCH_E_INVALID, "och_world_restore_box: a height holds 2^31 differing cubes, or 2^28 differing cells, or more");
+                return och::report(OCH_E_INVALID, "och_world: a height of the restore holds 2^31 differing cubes, or 2^28 differing cells, or more");
             if (at + P.cubes[H - 1] > R.n_cubes || P.cells[H - 1] > held) {
                 *grow_cubes = at + P.cubes[H - 1];
                 *grow_front = P.cells[H - 1];
@@ -319,13 +410,69 @@ int region_walk(och_world &w, const RegionBox &B, const RegionWork &R, uint32_t 
         const uint64_t n_cubes = P.cubes[H - 1], n_cells = P.cells[H - 1];
         N.f = (uint32_t)n_cells;
         if (n_cubes || n_cells) {
-            hipLaunchKernelGGL(k_region_emit<kRestore>, blocks((size_t)f * 8), dim3(256), 0, st, w.S, B, F, H, R.pos,
+            hipLaunchKernelGGL((k_region_emit<kRestore, Shape>), blocks((size_t)f * 8), dim3(256), 0, st, w.S, B, F, H, R.pos,
                                R.cubes + P.first[H - 1], kRestore ? R.cube_words + P.first[H - 1] : nullptr, (uint32_t)n_cubes, N);
             GPU_TRY(hipGetLastError());
         }
         at += n_cubes;
         cur ^= 1;
         f = (uint32_t)n_cells;
+    }
+    return OCH_OK;
+}
+
+// A fill's walk for a shape without closed forms, its counts on the device and
+// no read-back per level.  bound[H] >= 1 cells are launched and scanned at
+// level H (at most what R's frontiers hold); each level's kernels read their
+// real frontier from the totals the level above left (k_region_count_dev).
+// One read-back after the last level brings every level's totals.  Then, top
+// down, each level's real frontier against what was launched and the cubes
+// against the buffer: a level's totals are right whenever all levels above it
+// ran whole.  P is complete on return, or *grow_front / *grow_cubes name what
+// the first level that was cut short needs (its height in *grow_at) and the
+// caller walks again with more.
+template <class Shape>
+int region_walk_dev(och_world &w, const Shape &B, const RegionWork &R, const uint64_t bound[22], RegionPlan &P, uint64_t *grow_cubes,
+                    uint64_t *grow_front, int *grow_at)
+{
+    const hipStream_t st = w.st;
+    hipLaunchKernelGGL(k_region_seed, dim3(1), dim3(64), 0, st, R.front[0], 0u, 0u, false, R.totals, w.depth);
+    GPU_TRY(hipGetLastError());
+    int cur = 0;
+    for (int H = w.depth; H >= 1; --H) {
+        RegionFront F = R.front[cur];
+        const RegionFront N = R.front[cur ^ 1];
+        F.f = (uint32_t)bound[H];
+        hipLaunchKernelGGL(k_region_count_dev<Shape>, blocks((size_t)F.f * 8), dim3(256), 0, st, w.S, B, F, H, R.totals, R.cnt);
+        GPU_TRY(hipGetLastError());
+        size_t tb = R.temp_bytes;
+        GPU_TRY(hipcub::DeviceScan::InclusiveSum(R.temp, tb, R.cnt, R.pos, (int)F.f, st));
+        hipLaunchKernelGGL(k_region_emit_dev<Shape>, blocks((size_t)F.f * 8), dim3(256), 0, st, w.S, B, F, H, R.pos, R.totals, R.cubes,
+                           R.n_cubes, N);
+        GPU_TRY(hipGetLastError());
+        cur ^= 1;
+    }
+    RegionTotals T;
+    if (const int rs = world_read_back(w, {{&T, R.totals, sizeof T}})) return rs;
+    P = RegionPlan{};
+    P.cells[w.depth] = 1;
+    P.front = 1;
+    uint64_t at = 0;
+    for (int h = w.depth - 1; h >= 0; --h) {
+        P.cubes[h] = T.tot[h] >> 32;
+        P.cells[h] = T.tot[h] & 0xFFFFFFFFull;
+        P.first[h] = at;
+        if (at + P.cubes[h] >= kRegionLimit || P.cells[h] >= kRegionFrontLimit)
+            return och::report(OCH_E_INVALID, "och_world: a height of the ball holds 2^31 cubes, or 2^28 cells, or more");
+        if (at + P.cubes[h] > R.n_cubes || (h >= 1 && P.cells[h] > bound[h])) {
+            *grow_cubes = at + P.cubes[h];
+            *grow_front = P.cells[h];
+            *grow_at = h;
+            return OCH_OK;
+        }
+        at += P.cubes[h];
+        P.front += P.cells[h];
+        P.rows[h] = P.cells[h + 1];   // a straddling cell holds a voxel of the ball: it always has an entry
     }
     return OCH_OK;
 }
@@ -484,7 +631,7 @@ int world_fill_box(och_world &w, const int32_t lo[3], const int32_t hi[3], uint3
         if (const int hs = region_head(w)) return hs;
         const RegionBox B{{C.lo[0], C.lo[1], C.lo[2]}, {C.hi[0], C.hi[1], C.hi[2]}};
         if (C.top < w.depth)
-            if (const int ws = region_walk<false>(w, B, R, 0, 0, P, nullptr, nullptr)) return ws;
+            if (const int ws = region_walk<false, RegionBox>(w, B, R, 0, 0, P, nullptr, nullptr)) return ws;
         if (!phase("walk")) return OCH_E_HIP;
         const uint32_t *d_root = nullptr;
         if (const int ls = region_levels(w, R, P, id, T, false, &d_root)) return ls;
@@ -498,44 +645,51 @@ int world_fill_box(och_world &w, const int32_t lo[3], const int32_t hi[3], uint3
     return OCH_OK;
 }
 
-int world_restore_box(och_world &w, uint64_t snapshot, const int32_t lo[3], const int32_t hi[3], och_region_stats *out)
+// What a restore needs of its shape besides the classifier: the shape's
+// clipped axis box (any: something of the shape lies inside the tree), whether
+// it covers the whole tree, and the first sizes of the walk's buffers.
+struct RegionClip {
+    WorldBox box;
+    bool whole = false;
+    uint64_t want_cubes = 1, want_front = 1;
+};
+
+template <class Shape>
+int world_restore_region(och_world &w, uint64_t snapshot, const char *who, const Shape &B, const RegionClip &C, och_region_stats rs,
+                         och_region_stats *out)
 {
     PhaseTimer phase = world_phase(w);
     WorldSnapshot s;
-    if (const int ss = world_snapshot_of(w, snapshot, "och_world_restore_box", &s)) return ss;
-    const och::BoxCubes C = och::box_cube_counts(lo, hi, w.depth);
-    och_region_stats rs = region_stats(C);
+    if (const int ss = world_snapshot_of(w, snapshot, who, &s)) return ss;
     const auto done = [&] {
         ++w.strokes;
         region_trace(w, phase, "restore", rs);
         if (out) *out = rs;
         return OCH_OK;
     };
-    if (!C.any || s.root == w.now.root) return done();   // equal ids: equal content
-    WorldBox grown = region_world_box(C);   // the clipped box inside the snapshot's
+    if (!C.box.any || s.root == w.now.root) return done();   // equal ids: equal content
+    WorldBox grown = C.box;   // the clipped box inside the snapshot's
     for (int a = 0; a < 3; ++a) {
         grown.lo[a] = std::max(grown.lo[a], s.box.lo[a]);
         grown.hi[a] = std::min(grown.hi[a], s.box.hi[a]);
         grown.any = grown.any && s.box.any && grown.lo[a] < grown.hi[a];
     }
-    if (C.top == w.depth) {   // the whole tree
+    if (C.whole) {   // the whole tree
         region_set_root(w, s.root, s.root_mask);
         rs.cubes = 1;
         box_union(w.now.box, grown);
         return done();
     }
-    const RegionBox B{{C.lo[0], C.lo[1], C.lo[2]}, {C.hi[0], C.hi[1], C.hi[2]}};
     RegionWork R;
     RegionPlan P;
-    // the buffers start at the box's closed forms where those are small (a restore's cubes and cells
-    // are subsets of the fill's) and grow with what the walk finds: a level that outgrows them ends
-    // the walk, which starts over from the roots
-    uint64_t want_cubes = std::min<uint64_t>(C.n_cubes, 1u << 16), want_front = 1;
-    for (int h = 0; h <= w.depth; ++h) want_front = std::max(want_front, std::min<uint64_t>(C.cells[h], 1u << 14));
+    // the buffers start at what a fill of the shape would take where that is small (a restore's cubes
+    // and cells are subsets of the fill's) and grow with what the walk finds: a level that outgrows
+    // them ends the walk, which starts over from the roots
+    uint64_t want_cubes = C.want_cubes, want_front = C.want_front;
     for (;;) {
         if (const int rr = region_reserve(w, want_cubes, want_front, true, R)) return rr;
         uint64_t grow_cubes = 0, grow_front = 0;
-        if (const int ws = region_walk<true>(w, B, R, w.now.root, s.root, P, &grow_cubes, &grow_front)) return ws;
+        if (const int ws = region_walk<true, Shape>(w, B, R, w.now.root, s.root, P, &grow_cubes, &grow_front)) return ws;
         if (!grow_cubes && !grow_front) break;
         if (grow_cubes > want_cubes) want_cubes = std::max(grow_cubes, 2 * want_cubes);
         if (grow_front > want_front) want_front = std::max(grow_front, 2 * want_front);
@@ -561,6 +715,151 @@ int world_restore_box(och_world &w, uint64_t snapshot, const int32_t lo[3], cons
     return done();
 }
 
+constexpr uint64_t kRestoreCubes = 1u << 16, kRestoreFront = 1u << 14;   // a restore's first buffers, at most
+
+int world_restore_box(och_world &w, uint64_t snapshot, const int32_t lo[3], const int32_t hi[3], och_region_stats *out)
+{
+    const och::BoxCubes C = och::box_cube_counts(lo, hi, w.depth);
+    RegionClip clip;
+    clip.box = region_world_box(C);
+    clip.whole = C.top == w.depth;
+    clip.want_cubes = std::min<uint64_t>(C.n_cubes, kRestoreCubes);
+    for (int h = 0; h <= w.depth; ++h) clip.want_front = std::max(clip.want_front, std::min<uint64_t>(C.cells[h], kRestoreFront));
+    const RegionBox B{{C.lo[0], C.lo[1], C.lo[2]}, {C.hi[0], C.hi[1], C.hi[2]}};
+    return world_restore_region(w, snapshot, "och_world_restore_box", B, clip, region_stats(C), out);
+}
+
+// A ball against a tree of `depth`, on the host: its clipped axis box, what the
+// root cell is to it, and upper bounds of what its walk finds.  A straddling
+// cell of side s meets the sphere's surface, so it lies in the shell of radii
+// r -+ s sqrt 3 around the centre: cells[H] <= the shell's volume / s^3, and
+// at most the cells of height H that the axis box touches, and at most eight
+// times the level above.  The cubes of a ball number about 4 pi r^2: `cubes`
+// is an estimate with room, not a bound, and at most 7 per straddling cell.
+// Nothing rests on either: region_walk_dev checks every level against them.
+struct BallPlan {
+    WorldBox box;
+    int root = 0;                // region_class of the root cell: 0 outside, 1 straddling, 2 inside
+    uint64_t cells[22] = {0};    // 1 <= cells[H], H = 1 .. depth
+    uint64_t cubes = 1;
+};
+
+BallPlan ball_plan(const int32_t c2[3], uint32_t diameter, int depth)
+{
+    BallPlan b;
+    b.box.any = och::ball_axis_box(c2, diameter, depth, b.box.lo, b.box.hi);
+    if (!b.box.any) return b;
+    const int32_t origin[3] = {0, 0, 0};
+    b.root = och::ball_class(och::make_ball(c2, diameter), origin, depth);
+    const double r = 0.5 * diameter, pi = 3.14159265358979323846;
+    uint64_t sum = 0;
+    b.cells[depth] = 1;
+    for (int H = depth - 1; H >= 1; --H) {
+        const double s = (double)((uint64_t)1 << H), out = r + s * 1.7320508075688773, in = std::max(0.0, r - s * 1.7320508075688773);
+        const double shell = 4.0 / 3.0 * pi * (out * out * out - in * in * in) / (s * s * s) * 1.001 + 8.0;
+        uint64_t touch = 1;
+        for (int a = 0; a < 3; ++a) touch *= (uint64_t)(((b.box.hi[a] - 1) >> H) - (b.box.lo[a] >> H) + 1);
+        b.cells[H] = std::max<uint64_t>(1, std::min({touch, 8 * b.cells[H + 1], shell < 1e18 ? (uint64_t)shell : ~(uint64_t)0}));
+    }
+    for (int H = 1; H <= depth; ++H) sum += 7 * b.cells[H];
+    const double area = 1.25 * pi * (double)diameter * (double)diameter + 64.0;
+    b.cubes = std::min<uint64_t>(sum, area < 1e18 ? (uint64_t)area : ~(uint64_t)0);
+    return b;
+}
+
+och_region_stats region_stats(const WorldBox &b)
+{
+    och_region_stats rs{};
+    std::memcpy(rs.lo, b.lo, sizeof rs.lo);
+    std::memcpy(rs.hi, b.hi, sizeof rs.hi);
+    return rs;
+}
+
+// A fill's first buffers and launched frontiers, at most: the bounds are loose (a ball clipped by the
+// tree, a shell several cells thick), a walk interns nothing and costs little beside the levels, and
+// a stroke that needs more walks again with it.
+constexpr uint64_t kFillCubes = 1u << 17, kFillFront = 1u << 15;
+
+int world_fill_sphere(och_world &w, const int32_t c2[3], uint32_t diameter, uint32_t id, och_region_stats *out)
+{
+    PhaseTimer phase = world_phase(w);
+    if (const char *range = och::ball_range_error(c2, diameter)) return och::fail(OCH_E_INVALID, "och_world_fill_sphere: %s", range);
+    const BallPlan C = ball_plan(c2, diameter, w.depth);
+    och_region_stats rs = region_stats(C.box);
+    if (!C.box.any || C.root == 0) {   // no voxel of the ball inside the tree
+        ++w.strokes;
+        if (out) *out = rs;
+        return OCH_OK;
+    }
+    const RegionBall B = och::make_ball(c2, diameter);
+    RegionWork R;
+    RegionPlan P;
+    int T = 0;
+    if (C.root == 2) {   // the whole tree: one cube of height depth, no cell
+        T = id ? w.depth : 0;
+        rs.cubes = 1;
+    } else {
+        uint64_t want_cubes = std::min(C.cubes, kFillCubes), cap_front = kFillFront, slack = 1;
+        for (;;) {
+            uint64_t bound[22] = {0}, n_front = 1;
+            for (int H = 1; H <= w.depth; ++H) {
+                bound[H] = std::min(C.cells[H] * slack, cap_front);
+                n_front = std::max(n_front, bound[H]);
+            }
+            if (const int rr = region_reserve(w, want_cubes, n_front, false, R)) return rr;
+            uint64_t grow_cubes = 0, grow_front = 0;
+            int grow_at = 0;
+            if (const int ws = region_walk_dev(w, B, R, bound, P, &grow_cubes, &grow_front, &grow_at)) return ws;
+            if (!grow_cubes && !grow_front) break;
+            // a frontier grows about fourfold a level down to height 1; the cubes, once short, get the whole estimate
+            if (grow_at >= 1 && grow_front > bound[grow_at]) {
+                while (C.cells[grow_at] * slack < grow_front) slack *= 2;   // the bound itself fell short: nothing rests on it
+                cap_front = std::min(kRegionFrontLimit, std::max(2 * cap_front, grow_front << (2 * std::min(grow_at - 1, 8))));
+            }
+            if (grow_cubes > want_cubes) want_cubes = std::max({grow_cubes, 2 * want_cubes, std::min(C.cubes, kRegionLimit)});
+        }
+        for (int h = 0; h < w.depth; ++h) {
+            rs.cubes += P.cubes[h];
+            if (P.cubes[h]) T = id ? h : 0;
+        }
+        rs.cells = P.front;
+    }
+    if (!phase("walk")) return OCH_E_HIP;
+    // after the walk, before anything is interned: the ball and the depth alone decide
+    if ((uint64_t)w.used + rs.cells + (uint64_t)T > w.S.cap) return report_build(OCH_E_CAPACITY, "och_world", "");
+    if (C.root == 2 && !id) {   // the whole tree, cleared
+        region_set_root(w, 0, 0);
+    } else {
+        uint64_t widest = 1;
+        for (int h = 0; h < w.depth; ++h) widest = std::max(widest, P.cubes[h] + P.cells[h]);
+        if (widest >= kRegionLimit) return och::report(OCH_E_INVALID, kRegionTooMany);
+        if (const int ws = world_reserve(w, (uint32_t)widest + 1)) return ws;
+        if (const int hs = region_head(w)) return hs;
+        const uint32_t *d_root = nullptr;
+        if (const int ls = region_levels(w, R, P, id, T, false, &d_root)) return ls;
+        if (const int fs = region_finish(w, d_root, rs)) return fs;
+        if (!phase("levels")) return OCH_E_HIP;
+    }
+    if (id) box_union(w.now.box, C.box);
+    ++w.strokes;
+    region_trace(w, phase, id ? "fill sphere" : "clear sphere", rs);
+    if (out) *out = rs;
+    return OCH_OK;
+}
+
+int world_restore_sphere(och_world &w, uint64_t snapshot, const int32_t c2[3], uint32_t diameter, och_region_stats *out)
+{
+    if (const char *range = och::ball_range_error(c2, diameter)) return och::fail(OCH_E_INVALID, "och_world_restore_sphere: %s", range);
+    const BallPlan C = ball_plan(c2, diameter, w.depth);
+    RegionClip clip;
+    clip.box = C.box;
+    clip.box.any = C.box.any && C.root != 0;
+    clip.whole = C.root == 2;
+    clip.want_cubes = std::min(C.cubes, kRestoreCubes);
+    for (int H = 1; H <= w.depth; ++H) clip.want_front = std::max(clip.want_front, std::min(C.cells[H], kRestoreFront));
+    return world_restore_region(w, snapshot, "och_world_restore_sphere", och::make_ball(c2, diameter), clip, region_stats(C.box), out);
+}
+
 }  // namespace
 
 OCH_API int och_world_fill_box(och_world *w, const int32_t lo[3], const int32_t hi[3], uint32_t id, och_region_stats *stats)
@@ -575,4 +874,19 @@ OCH_API int och_world_restore_box(och_world *w, uint64_t snapshot, const int32_t
     if (!lo || !hi) return och::report(OCH_E_INVALID, "och_world_restore_box: lo or hi is NULL");
     return world_call(w, "och_world_restore_box", "och_world", kBreaks, kOwnTexts,
                       [&] { return world_restore_box(*w, snapshot, lo, hi, stats); });
+}
+
+OCH_API int och_world_fill_sphere(och_world *w, const int32_t centre2[3], uint32_t diameter, uint32_t id, och_region_stats *stats)
+{
+    if (!centre2) return och::report(OCH_E_INVALID, "och_world_fill_sphere: centre2 is NULL");
+    return world_call(w, "och_world_fill_sphere", "och_world", kBreaks, kOwnTexts,
+                      [&] { return world_fill_sphere(*w, centre2, diameter, id, stats); });
+}
+
+OCH_API int och_world_restore_sphere(och_world *w, uint64_t snapshot, const int32_t centre2[3], uint32_t diameter,
+                                     och_region_stats *stats)
+{
+    if (!centre2) return och::report(OCH_E_INVALID, "och_world_restore_sphere: centre2 is NULL");
+    return world_call(w, "och_world_restore_sphere", "och_world", kBreaks, kOwnTexts,
+                      [&] { return world_restore_sphere(*w, snapshot, centre2, diameter, stats); });
 }

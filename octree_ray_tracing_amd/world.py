@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 from ._lib import HostPool, OchError, call
 from ._marshal import ScopedHandle, host_array, host_pool_result, nodes_arg, records_arg, struct_dict
-from .builder import VOXELS_GRID_U8, NodePool, _box_args, _capacity, _read_box_args
+from .builder import VOXELS_GRID_U8, NodePool, _ball_args, _box_args, _capacity, _read_box_args
 from .tracer import HOctree
 
 
@@ -22,6 +22,7 @@ class World(ScopedHandle):
     """A 1-based DAG resident on one GPU: edit() applies a record list as edit_voxels would, make_pool()
     and flush() show it, download() gives the canonical pool, compact() drops what strokes left behind;
     fill_box() and restore_box() set or restore a whole box at a cost that follows its surface;
+    fill_sphere() and restore_sphere() do the same for a ball;
     at() and read_box() ask it what it holds without a download, tighten() makes its box exact;
     snapshot(), checkout() and release() remember and restore earlier states (UndoStack, below), diff()
     gives what changed between two of them."""
@@ -247,6 +248,32 @@ class World(ScopedHandle):
         lo, hi = _box_args(lo, hi, "World.restore_box")
         st = _lib.RegionStats()
         call("och_world_restore_box", h, s, lo, hi, C.byref(st))
+        return struct_dict(st)
+
+    # -- balls (och_world_fill_sphere / och_world_restore_sphere)
+
+    def fill_sphere(self, centre2, diameter: int, id: int) -> dict:
+        """One stroke: every voxel of the ball becomes id (0 removes), as edit(sphere_records(centre2,
+        diameter, id)) would leave the world, without a record (och_world_fill_sphere).  centre2 is twice the
+        centre in voxels, diameter counts voxels, both integers; sphere_records says which voxels those are.
+        Returns fill_box's dict: sphere_cubes' two totals, the ids consumed and the ball's clipped axis box."""
+        h = self._open("fill_sphere")
+        c2, d = _ball_args(centre2, diameter, "World.fill_sphere")
+        if isinstance(id, bool) or not isinstance(id, (int, np.integer)) or not 0 <= int(id) <= 0xFFFFFFFF:
+            raise ValueError(f"World.fill_sphere: id is an integer inside uint32, not {id!r}")
+        st = _lib.RegionStats()
+        call("och_world_fill_sphere", h, c2, d, int(id), C.byref(st))
+        return struct_dict(st)
+
+    def restore_sphere(self, s: int, centre2, diameter: int) -> dict:
+        """One stroke: inside the ball the content of snapshot s, outside it the current content
+        (och_world_restore_sphere): restore_box for a round brush.  Returns fill_box's dict; cubes and cells
+        count only what differs."""
+        h = self._open("restore_sphere")
+        s = self._handle(s, "restore_sphere")
+        c2, d = _ball_args(centre2, diameter, "World.restore_sphere")
+        st = _lib.RegionStats()
+        call("och_world_restore_sphere", h, s, c2, d, C.byref(st))
         return struct_dict(st)
 
 
