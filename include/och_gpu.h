@@ -1009,8 +1009,10 @@ OCH_API int och_world_diff(och_world *world, uint64_t from, uint64_t to, void *r
  * whose records all lie outside the tree.
  * A ball (och_world_fill_sphere, och_world_restore_sphere) is the second
  * shape: the same cubes, cells and levels, classified against a sphere.
+ * Strokes conditional on the old voxel (och_world_paint_box, _paint_sphere)
+ * close the section.
  * Out of scope: shapes other than boxes and balls; copying a box to another
- * place; fills conditional on the old voxel; replicated worlds. */
+ * place; replicated worlds. */
 typedef struct och_region_stats {
     uint64_t cubes;      /* child words written: the maximal aligned cubes inside the box that were emitted */
     uint64_t cells;      /* straddling cells expanded = rows rebuilt, summed over the levels */
@@ -1138,6 +1140,63 @@ OCH_API int och_world_fill_sphere(och_world *world, const int32_t centre2[3], ui
  * ball's surface. */
 OCH_API int och_world_restore_sphere(och_world *world, uint64_t snapshot, const int32_t centre2[3], uint32_t diameter,
                                      och_region_stats *stats /* may be NULL */);
+
+/* Conditional strokes: inside the shape a voxel whose current id is v becomes
+ * pred(v) ? id : v, with pred(v) = (v == match) for OCH_WHEN_IS and
+ * (v != match) for OCH_WHEN_IS_NOT.  Paint the solid voxels: (IS_NOT, 0, id);
+ * fill under, the empty ones only: (IS, 0, id); replace a material: (IS, m, n);
+ * erase it: (IS, m, 0); keep only it: (IS_NOT, m, 0).
+ *
+ * The world is left exactly as och_world_edit would leave it given the records
+ * {(x, y, z, id) : voxel in the shape, in the tree, pred(current id)}, content
+ * and canonical och_world_download alike; that record stroke afterwards
+ * consumes no id and leaves the root where it is.  Shape, clipping, argument
+ * ranges, the ball's integer inequality and the axis box are
+ * och_world_fill_box' and och_world_fill_sphere's.  Append-only like every
+ * stroke; a HIP failure breaks the world.
+ *
+ * A cube inside the shape is one child word and its new word a function of the
+ * subtree the old word names, evaluated once per distinct node of the DAG: the
+ * cost follows the shape's surface plus the distinct nodes under it, never its
+ * volume.  Heights: a voxel is 0, a node of height h >= 1 has children of
+ * height h - 1.  A cube's word is what the current root holds at its position
+ * (an interior word at or above the capacity reads as 0).  A cube of height h
+ * is open when the stroke can touch it: always for h >= 1 and word != 0,
+ * otherwise (an empty cube, a voxel) iff pred(word).  stats.cells counts the
+ * straddling open cells the walk expanded, the root cell included; stats.cubes
+ * the open cubes inside the shape whose parent is not (a shape that covers the
+ * tree: one cube of height depth, no cell).  N_h is the set of distinct
+ * non-empty nodes of height h >= 1 that are a counted cube's word or a
+ * non-zero child of a member of N_(h+1); stats.nodes = sum |N_h|.  T = the
+ * greatest height of a counted cube when pred(0) and id != 0 (the uniform
+ * subtrees empty positions turn into), else 0.  All of these depend on the
+ * world's content, the shape and the predicate alone.
+ *
+ * cubes = 0 changes nothing but strokes (+ 1): no id, never refused for
+ * capacity, the world's box left alone.  OCH_E_CAPACITY, with the world
+ * unchanged, when used + cells + nodes + T > capacity; checked after the walk
+ * and the map's way down, before the first intern.  The world's box grows by
+ * the clipped (axis) box only when pred(0), id != 0 and cubes > 0: no other
+ * conditional stroke makes an empty voxel solid.  OCH_E_INVALID: a `when`
+ * other than 0 or 1, a NULL or broken world, NULL pointers, the ball's
+ * argument range, a height with 2^31 or more cubes, candidates or nodes, a
+ * frontier of 2^28 or more cells.  One 8-byte read-back per level of the walk,
+ * one of 4 bytes per height of the map and per level on the way up. */
+#define OCH_WHEN_IS      0   /* voxels whose current id == match   (match 0: the empty ones) */
+#define OCH_WHEN_IS_NOT  1   /* voxels whose current id != match   (match 0: the solid ones) */
+
+typedef struct och_paint_stats {
+    uint64_t cubes;     /* open maximal cubes inside the shape */
+    uint64_t cells;     /* open straddling cells the walk expanded, the root cell included */
+    uint64_t nodes;     /* distinct nodes mapped, summed over the heights */
+    uint64_t new_ids;   /* ids the stroke consumed */
+    int32_t  lo[3], hi[3];   /* the clipped (axis) box, as och_region_stats */
+} och_paint_stats;           /* 56 bytes */
+
+OCH_API int och_world_paint_box(och_world *world, const int32_t lo[3], const int32_t hi[3], int when, uint32_t match,
+                                uint32_t id, och_paint_stats *stats /* may be NULL */);
+OCH_API int och_world_paint_sphere(och_world *world, const int32_t centre2[3], uint32_t diameter, int when, uint32_t match,
+                                   uint32_t id, och_paint_stats *stats /* may be NULL */);
 
 /* ------------------------------------------------------------ editor */
 /* Interactive editing (the demo's place/remove, ORT/test_och_h_octree.cpp:

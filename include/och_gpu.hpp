@@ -24,6 +24,9 @@ enum class direction : int32_t {
     x_pos = 0, y_pos = 1, z_pos = 2, x_neg = 3, y_neg = 4, z_neg = 5, exit = 6, inside = 7, error = 8
 };
 
+// Which voxels a conditional stroke touches (OCH_WHEN_*): those whose id is, or is not, `match`.
+enum class when : int { is = OCH_WHEN_IS, is_not = OCH_WHEN_IS_NOT };
+
 struct error : std::runtime_error {
     int status;
     error(int s, const std::string &what) : std::runtime_error(what), status(s) {}
@@ -316,7 +319,8 @@ inline box_cube_list sphere_cubes(const int32_t centre2[3], uint32_t diameter, i
 // applies a record list as edit_voxels would, flush() publishes the stroke's
 // new nodes to a tree made by make_pool(), download() gives the canonical pool;
 // at() and read_box() ask it what it holds, tighten() makes its box exact;
-// snapshot(), checkout() and release() keep earlier states, diff() compares two.
+// snapshot(), checkout() and release() keep earlier states, diff() compares two;
+// paint_box() and paint_sphere() are the strokes conditional on the old voxel.
 class world {
 public:
     world(const uint32_t *nodes, uint32_t n_nodes, uint32_t root, int depth, uint32_t capacity = 0, int device = -1)
@@ -413,6 +417,22 @@ public:
     {
         och_region_stats st;
         check(och_world_restore_sphere(w_, snapshot, centre2, diameter, &st), "och_world_restore_sphere");
+        return st;
+    }
+
+    // Inside the box a voxel v becomes id where the predicate holds (when::is: v == match, when::is_not:
+    // v != match) and stays otherwise: paint is (is_not, 0), fill-under (is, 0), replace (is, m).
+    och_paint_stats paint_box(const int32_t lo[3], const int32_t hi[3], uint32_t id, gpu::when w = gpu::when::is_not, uint32_t match = 0)
+    {
+        och_paint_stats st;
+        check(och_world_paint_box(w_, lo, hi, static_cast<int>(w), match, id, &st), "och_world_paint_box");
+        return st;
+    }
+    och_paint_stats paint_sphere(const int32_t centre2[3], uint32_t diameter, uint32_t id, gpu::when w = gpu::when::is_not,
+                                 uint32_t match = 0)
+    {
+        och_paint_stats st;
+        check(och_world_paint_sphere(w_, centre2, diameter, static_cast<int>(w), match, id, &st), "och_world_paint_sphere");
         return st;
     }
 

@@ -78,6 +78,12 @@ class RegionStats(C.Structure):
                 ("hi", C.c_int32 * 3)]
 
 
+class PaintStats(C.Structure):
+    """och_paint_stats: what the conditional strokes (och_world_paint_box, _paint_sphere) report."""
+    _fields_ = [("cubes", C.c_uint64), ("cells", C.c_uint64), ("nodes", C.c_uint64), ("new_ids", C.c_uint64),
+                ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+
 class TerrainParams(C.Structure):
     _fields_ = [("depth", C.c_int32), ("tunnels", C.c_int32), ("dedup", C.c_int32),
                 ("rand_kind", C.c_int32), ("threads", C.c_int32), ("use_gpu", C.c_int32)]
@@ -199,6 +205,8 @@ PROTOTYPES = {
     "och_sphere_cubes": (C.c_int, [_P, _u32, C.c_int, _P, _P, C.c_uint64, _P, _P, C.POINTER(C.c_uint64)]),
     "och_world_fill_sphere": (C.c_int, [_P, _P, _u32, _u32, C.POINTER(RegionStats)]),
     "och_world_restore_sphere": (C.c_int, [_P, C.c_uint64, _P, _u32, C.POINTER(RegionStats)]),
+    "och_world_paint_box": (C.c_int, [_P, _P, _P, C.c_int, _u32, _u32, C.POINTER(PaintStats)]),
+    "och_world_paint_sphere": (C.c_int, [_P, _P, _u32, C.c_int, _u32, _u32, C.POINTER(PaintStats)]),
     "och_pool_pack": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "och_pool_at": (_u32, [_P, _u32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "och_pool_occupied_box": (C.c_int, [_P, _u32, _u32, C.c_int, C.c_int, _P, _P]),
@@ -237,6 +245,9 @@ PROTOTYPES = {
 
 # och_world_checkout / och_world_diff: the world's current root (include/och_gpu.h OCH_WORLD_*)
 WORLD_CURRENT, WORLD_MAX_SNAPSHOTS = 0, 65536
+
+# och_world_paint_box / _paint_sphere: which voxels the stroke touches (include/och_gpu.h OCH_WHEN_*)
+WHEN_IS, WHEN_IS_NOT = 0, 1
 
 # och_light.flags (include/och_gpu.h OCH_LIGHT_*)
 LIGHT_SUN, LIGHT_AO = 1, 2

@@ -131,6 +131,48 @@ def records_arg(voxels, who: str, device: int | None = None, use_gpu: bool = Tru
     return voxels, voxels.data_ptr(), voxels.shape[0], True
 
 
+def u32_arg(v, who: str, what: str) -> int:
+    """A voxel id (or another uint32 argument) as an int; a bool, a float or a value outside uint32 is refused."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 0xFFFFFFFF:
+        raise ValueError(f"{who}: {what} is an integer inside uint32, not {v!r}")
+    return int(v)
+
+
+def when_arg(when, who: str) -> int:
+    """The predicate of a conditional stroke: WHEN_IS (0) or WHEN_IS_NOT (1)."""
+    if isinstance(when, bool) or not isinstance(when, (int, np.integer)) or int(when) not in (0, 1):
+        raise ValueError(f"{who}: when is WHEN_IS (0) or WHEN_IS_NOT (1), not {when!r}")
+    return int(when)
+
+
+def select_records(grid, origin, id, when, match, mask=None) -> np.ndarray:
+    """The records of a conditional stroke, on the host: (x, y, z, id) for every voxel v of a dense grid
+    (indexed [z, y, x], read_box's layout, its lo as `origin`) with v == match (WHEN_IS) or v != match
+    (WHEN_IS_NOT), optionally only where the boolean `mask` of the grid's shape holds.  An (n, 4) np.uint32
+    array in the grid's own order; a coordinate below 0 wraps as box_records' do.  What World.paint_box
+    and paint_sphere are held to: edit() of these records leaves the same world."""
+    id = u32_arg(id, "select_records", "id")
+    match = u32_arg(match, "select_records", "match")
+    when = when_arg(when, "select_records")
+    grid = np.asarray(host_array(grid))
+    if grid.ndim != 3 or grid.dtype.kind not in "iu":
+        raise ValueError(f"select_records: a dense (nz, ny, nx) integer grid, not shape {grid.shape} {grid.dtype}")
+    origin = [int(v) for v in origin]
+    if len(origin) != 3:
+        raise ValueError(f"select_records: origin is (x, y, z), not {origin!r}")
+    hit = (grid.astype(np.int64) & 0xFFFFFFFF == match) != bool(when)
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.shape != grid.shape or mask.dtype != np.bool_:
+            raise ValueError(f"select_records: mask is a boolean array of the grid's shape {grid.shape}, not "
+                             f"{mask.shape} {mask.dtype}")
+        hit &= mask
+    z, y, x = np.nonzero(hit)
+    out = np.empty((x.size, 4), np.int64)
+    out[:, 0], out[:, 1], out[:, 2], out[:, 3] = x + origin[0], y + origin[1], z + origin[2], id
+    return (out & 0xFFFFFFFF).astype(np.uint32)
+
+
 # -- what the library fills in
 
 def struct_dict(st) -> dict:

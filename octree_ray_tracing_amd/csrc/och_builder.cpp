@@ -10,7 +10,8 @@
 // wrapper, the staging and read-back steps); what reads that world back on the
 // device (at, a box to a grid, the exact box) is och_world_read.h; snapshots
 // of that world, checkout and the diff of two roots are och_world_history.h;
-// its box- and ball-shaped strokes (fill, clear, restore) are och_world_region.h.
+// its box- and ball-shaped strokes (fill, clear, restore) are och_world_region.h,
+// those conditional on the old voxel (paint, fill-under, replace) och_world_paint.h.
 // One translation unit: the headers are included here and nowhere else.
 //
 // The reference builds its tree by recursive create_volume + per-voxel
@@ -45,6 +46,7 @@
 #include "och_world_read.h"
 #include "och_world_history.h"
 #include "och_world_region.h"
+#include "och_world_paint.h"
 
 namespace {
 

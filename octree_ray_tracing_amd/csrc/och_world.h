@@ -48,8 +48,9 @@
 // paths; 0-based pools; depth 22.  Reading the world back (at, a box to a grid,
 // the exact box after removals) is och_world_read.h, with what stays out of
 // scope there; remembering earlier roots (snapshot, checkout, the diff of two
-// roots) is och_world_history.h; strokes whose shape is a box (fill, clear,
-// restore from a snapshot) are och_world_region.h.
+// roots) is och_world_history.h; strokes whose shape is a box or a ball (fill,
+// clear, restore from a snapshot) are och_world_region.h, those conditional on
+// the old voxel (paint, fill-under, replace) och_world_paint.h.
 #pragma once
 #include <map>
 #include <memory>
@@ -195,6 +196,8 @@ struct och_world {
     size_t diff_temp_bytes = 0;
     // och_world_region.h: a region stroke's cubes, frontiers, counts and scan storage, sized by its box, kept
     och::DevBuf<uint8_t> d_region;
+    // och_world_paint.h: a conditional stroke's map (the distinct nodes under the shape, their sort and scan), kept
+    och::DevBuf<uint8_t> d_paint;
 
     uint32_t *head() const { return S.next; }
     ~och_world()

@@ -77,8 +77,12 @@
 // the host holds each level's real frontier against what was launched, top
 // down, and walks again with more where one was cut short.
 //
+// A third mode of the walk (kWalkPaint) serves the strokes conditional on the
+// old voxel, och_world_paint.h: one root, and a child the predicate cannot
+// touch is dropped.
+//
 // Out of scope: shapes other than boxes and balls; copying a box to another
-// place; fills conditional on the old voxel; replicated worlds.
+// place; replicated worlds.
 #pragma once
 #include "och_world_history.h"
 
@@ -117,10 +121,46 @@ __device__ inline int region_class(const RegionBall &B, uint64_t key, int h)
     return och::ball_class(B, c, h);
 }
 
+// What a walk reads of the store: nothing (a fill), each child's words under
+// two roots, equal ones dropped (a restore), or its word under one root, a
+// child that is not open dropped (a paint: RegionPaint).
+constexpr int kWalkFill = 0, kWalkRestore = 1, kWalkPaint = 2;
+
+// A shape with a predicate on the old voxel, pred(v) = (v == match) != when:
+// the shape's classifier, and which children a paint's walk keeps.
+template <class Shape>
+struct RegionPaint {
+    Shape shape;
+    uint32_t when, match;
+};
+
+template <class Shape>
+__device__ inline int region_class(const RegionPaint<Shape> &B, uint64_t key, int h)
+{
+    return region_class(B.shape, key, h);
+}
+
+__host__ __device__ inline bool paint_pred(uint32_t when, uint32_t match, uint32_t v) { return (v == match) != (when != 0); }
+
+// A child of height H - 1 whose word is w is open when the stroke can touch
+// it: a node always, an empty cube or a voxel iff pred(w).
+template <class Shape>
+__device__ inline bool region_open(const Shape &, int, uint32_t)
+{
+    return true;
+}
+
+template <class Shape>
+__device__ inline bool region_open(const RegionPaint<Shape> &B, int H, uint32_t w)
+{
+    return (H > 1 && w) || paint_pred(B.when, B.match, w);
+}
+
 // Candidate q = 8 i + k, child k of cell i of the frontier at height H: its
 // key, whether it is a cube or a cell of the next frontier, and (restore) its
-// two words.  An interior word at or above cap reads as empty (k_world_at).
-template <bool kRestore, class Shape>
+// two words, (paint) its word in wa.  An interior word at or above cap reads
+// as empty (k_world_at).
+template <int kMode, class Shape>
 __device__ inline void region_child(const GpuStore &S, const Shape &B, const RegionFront &F, int H, size_t q, uint64_t &key,
                                     uint32_t &wa, uint32_t &wb, bool &cube, bool &cell)
 {
@@ -132,7 +172,7 @@ __device__ inline void region_child(const GpuStore &S, const Shape &B, const Reg
     key = F.keys[i] << 3 | k;
     const int c = region_class(B, key, H - 1);
     if (!c) return;
-    if (kRestore) {
+    if (kMode == kWalkRestore) {
         wa = S.nodes[(size_t)F.fa[i] * 8 + k];   // id 0 is the zero row
         wb = S.nodes[(size_t)F.fb[i] * 8 + k];
         if (H > 1) {
@@ -141,36 +181,42 @@ __device__ inline void region_child(const GpuStore &S, const Shape &B, const Reg
         }
         if (wa == wb) return;
     }
+    if (kMode == kWalkPaint) {
+        wa = S.nodes[(size_t)F.fa[i] * 8 + k];
+        if (H > 1) wa = wa < S.cap ? wa : 0u;
+        if (!region_open(B, H, wa)) return;
+    }
     cube = c == 2;
     cell = c == 1;
 }
 
 // cnt[i] = cell i's cubes << 32 | its cells of the next frontier.
-template <bool kRestore, class Shape>
+template <int kMode, class Shape>
 __device__ inline void region_count(const GpuStore &S, const Shape &B, const RegionFront &F, int H, uint64_t *__restrict__ cnt)
 {
     const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t key;
     uint32_t wa, wb;
     bool cube, cell;
-    region_child<kRestore>(S, B, F, H, q, key, wa, wb, cube, cell);
+    region_child<kMode>(S, B, F, H, q, key, wa, wb, cube, cell);
     const uint64_t bc = __ballot(cube), bf = __ballot(cell);
     const uint32_t lane = threadIdx.x & 63u;
     if (q < (size_t)F.f * 8 && (lane & 7u) == 0)
         cnt[q >> 3] = (uint64_t)__popcll((bc >> lane) & 0xFFull) << 32 | (uint64_t)__popcll((bf >> lane) & 0xFFull);
 }
 
-template <bool kRestore, class Shape>
+template <int kMode, class Shape>
 __global__ __launch_bounds__(256) void k_region_count(GpuStore S, Shape B, RegionFront F, int H, uint64_t *__restrict__ cnt)
 {
-    region_count<kRestore>(S, B, F, H, cnt);
+    region_count<kMode>(S, B, F, H, cnt);
 }
 
 // Survivor j of either kind: pos[] is the inclusive sum of k_region_count's
 // cnt[].  A cube: entry j of height H - 1 (cubes, and for a restore its word
-// under the snapshot).  A cell: cell j of the next frontier.  n_cubes and
-// N.f are what the buffers hold; the counts never exceed them.
-template <bool kRestore, class Shape>
+// under the snapshot, for a paint its word).  A cell: cell j of the next
+// frontier.  n_cubes and N.f are what the buffers hold; the counts never
+// exceed them.
+template <int kMode, class Shape>
 __device__ inline void region_emit(const GpuStore &S, const Shape &B, const RegionFront &F, int H, const uint64_t *__restrict__ pos,
                                    uint64_t *__restrict__ cubes, uint32_t *__restrict__ cube_words, uint32_t n_cubes,
                                    const RegionFront &N)
@@ -179,7 +225,7 @@ __device__ inline void region_emit(const GpuStore &S, const Shape &B, const Regi
     uint64_t key;
     uint32_t wa, wb;
     bool cube, cell;
-    region_child<kRestore>(S, B, F, H, q, key, wa, wb, cube, cell);
+    region_child<kMode>(S, B, F, H, q, key, wa, wb, cube, cell);
     const uint64_t bc = __ballot(cube), bf = __ballot(cell);
     if (!cube && !cell) return;
     const uint32_t lane = threadIdx.x & 63u, k = (uint32_t)(q & 7u);
@@ -189,24 +235,22 @@ __device__ inline void region_emit(const GpuStore &S, const Shape &B, const Regi
         const uint32_t j = (uint32_t)(base >> 32) + (uint32_t)__popcll((bc >> (lane & 56u)) & lower);
         if (j >= n_cubes) return;
         cubes[j] = key;
-        if (kRestore) cube_words[j] = wb;
+        if (kMode) cube_words[j] = kMode == kWalkPaint ? wa : wb;
     } else {
         const uint32_t j = (uint32_t)base + (uint32_t)__popcll((bf >> (lane & 56u)) & lower);
         if (j >= N.f) return;
         N.keys[j] = key;
-        if (kRestore) {
-            N.fa[j] = wa;
-            N.fb[j] = wb;
-        }
+        if (kMode) N.fa[j] = wa;
+        if (kMode == kWalkRestore) N.fb[j] = wb;
     }
 }
 
-template <bool kRestore, class Shape>
+template <int kMode, class Shape>
 __global__ __launch_bounds__(256) void k_region_emit(GpuStore S, Shape B, RegionFront F, int H, const uint64_t *__restrict__ pos,
                                                      uint64_t *__restrict__ cubes, uint32_t *__restrict__ cube_words,
                                                      uint32_t n_cubes, RegionFront N)
 {
-    region_emit<kRestore>(S, B, F, H, pos, cubes, cube_words, n_cubes, N);
+    region_emit<kMode>(S, B, F, H, pos, cubes, cube_words, n_cubes, N);
 }
 
 // A fill's walk with its counts on the device: what the walk of a shape
@@ -229,7 +273,7 @@ __global__ __launch_bounds__(256) void k_region_count_dev(GpuStore S, Shape B, R
 {
     const uint32_t bound = F.f;
     F.f = (uint32_t)min((uint64_t)bound, T->tot[H] & 0xFFFFFFFFull);
-    region_count<false>(S, B, F, H, cnt);
+    region_count<kWalkFill>(S, B, F, H, cnt);
     const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= (size_t)F.f * 8 && q < (size_t)bound * 8 && (q & 7u) == 0) cnt[q >> 3] = 0;
 }
@@ -251,7 +295,7 @@ __global__ __launch_bounds__(256) void k_region_emit_dev(GpuStore S, Shape B, Re
         if (H >= 2) T->first[H - 2] = first + (total >> 32);
     }
     const uint64_t room = first < n_cubes ? n_cubes - first : 0;
-    region_emit<false>(S, B, F, H, pos, cubes + min(first, n_cubes), nullptr, (uint32_t)min(room, (uint64_t)0xFFFFFFFFull), N);
+    region_emit<kWalkFill>(S, B, F, H, pos, cubes + min(first, n_cubes), nullptr, (uint32_t)min(room, (uint64_t)0xFFFFFFFFull), N);
 }
 
 // The first frontier: the root cell, key 0, with its two ids; T: a walk with
@@ -367,40 +411,43 @@ struct RegionPlan {
 };
 
 // The walk from the root cell down.  Fill: P is complete before the call and
-// nothing is read back.  Restore (ra != rb): P is filled in as the levels'
-// totals come back; grow_cubes / grow_front != 0 on return: a level outgrew
-// the buffers, the caller reserves that much and walks again.
-template <bool kRestore, class Shape>
+// nothing is read back.  Restore (ra != rb) and paint (ra, the one root): P is
+// filled in as the levels' totals come back; grow_cubes / grow_front != 0 on
+// return: a level outgrew the buffers, the caller reserves that much and walks
+// again.
+template <int kMode, class Shape>
 int region_walk(och_world &w, const Shape &B, const RegionWork &R, uint32_t ra, uint32_t rb, RegionPlan &P, uint64_t *grow_cubes,
                 uint64_t *grow_front)
 {
     const hipStream_t st = w.st;
-    hipLaunchKernelGGL(k_region_seed, dim3(1), dim3(64), 0, st, R.front[0], ra, rb, kRestore, static_cast<RegionTotals *>(nullptr), 0);
+    hipLaunchKernelGGL(k_region_seed, dim3(1), dim3(64), 0, st, R.front[0], ra, rb, kMode != kWalkFill, static_cast<RegionTotals *>(nullptr), 0);
     GPU_TRY(hipGetLastError());
     uint32_t f = 1;
     uint64_t at = 0;   // the cubes emitted so far
     int cur = 0;
-    if (kRestore) P = RegionPlan{};
+    if (kMode) P = RegionPlan{};
     for (int H = w.depth; H >= 1 && f; --H) {
         RegionFront F = R.front[cur], N = R.front[cur ^ 1];
         const uint32_t held = N.f;
         F.f = f;
-        if (kRestore) {
+        if (kMode) {
             P.cells[H] = f;
             P.front += f;
         }
-        hipLaunchKernelGGL((k_region_count<kRestore, Shape>), blocks((size_t)f * 8), dim3(256), 0, st, w.S, B, F, H, R.cnt);
+        hipLaunchKernelGGL((k_region_count<kMode, Shape>), blocks((size_t)f * 8), dim3(256), 0, st, w.S, B, F, H, R.cnt);
         GPU_TRY(hipGetLastError());
         size_t tb = R.temp_bytes;
         GPU_TRY(hipcub::DeviceScan::InclusiveSum(R.temp, tb, R.cnt, R.pos, (int)f, st));
-        if (kRestore) {
+        if (kMode) {
             uint64_t total = 0;
             if (const int rs = world_read_back(w, {{&total, R.pos + (f - 1), 8}})) return rs;
             P.cubes[H - 1] = total >> 32;
             P.cells[H - 1] = total & 0xFFFFFFFFull;
             P.first[H - 1] = at;
             if (at + P.cubes[H - 1] >= kRegionLimit || P.cells[H - 1] >= kRegionFrontLimit)
-                return och::report(OCH_E_INVALID, "och_world: a height of the restore holds 2^31 differing cubes, or 2^28 differing cells, or more");
+                return och::report(OCH_E_INVALID, kMode == kWalkRestore
+                                                      ? "och_world: a height of the restore holds 2^31 differing cubes, or 2^28 differing cells, or more"
+                                                      : "och_world: a height of the paint holds 2^31 open cubes, or 2^28 open cells, or more");
             if (at + P.cubes[H - 1] > R.n_cubes || P.cells[H - 1] > held) {
                 *grow_cubes = at + P.cubes[H - 1];
                 *grow_front = P.cells[H - 1];
@@ -410,8 +457,8 @@ int region_walk(och_world &w, const Shape &B, const RegionWork &R, uint32_t ra, 
         const uint64_t n_cubes = P.cubes[H - 1], n_cells = P.cells[H - 1];
         N.f = (uint32_t)n_cells;
         if (n_cubes || n_cells) {
-            hipLaunchKernelGGL((k_region_emit<kRestore, Shape>), blocks((size_t)f * 8), dim3(256), 0, st, w.S, B, F, H, R.pos,
-                               R.cubes + P.first[H - 1], kRestore ? R.cube_words + P.first[H - 1] : nullptr, (uint32_t)n_cubes, N);
+            hipLaunchKernelGGL((k_region_emit<kMode, Shape>), blocks((size_t)f * 8), dim3(256), 0, st, w.S, B, F, H, R.pos,
+                               R.cubes + P.first[H - 1], kMode ? R.cube_words + P.first[H - 1] : nullptr, (uint32_t)n_cubes, N);
             GPU_TRY(hipGetLastError());
         }
         at += n_cubes;
@@ -631,7 +678,7 @@ int world_fill_box(och_world &w, const int32_t lo[3], const int32_t hi[3], uint3
         if (const int hs = region_head(w)) return hs;
         const RegionBox B{{C.lo[0], C.lo[1], C.lo[2]}, {C.hi[0], C.hi[1], C.hi[2]}};
         if (C.top < w.depth)
-            if (const int ws = region_walk<false, RegionBox>(w, B, R, 0, 0, P, nullptr, nullptr)) return ws;
+            if (const int ws = region_walk<kWalkFill, RegionBox>(w, B, R, 0, 0, P, nullptr, nullptr)) return ws;
         if (!phase("walk")) return OCH_E_HIP;
         const uint32_t *d_root = nullptr;
         if (const int ls = region_levels(w, R, P, id, T, false, &d_root)) return ls;
@@ -689,7 +736,7 @@ int world_restore_region(och_world &w, uint64_t snapshot, const char *who, const
     for (;;) {
         if (const int rr = region_reserve(w, want_cubes, want_front, true, R)) return rr;
         uint64_t grow_cubes = 0, grow_front = 0;
-        if (const int ws = region_walk<true, Shape>(w, B, R, w.now.root, s.root, P, &grow_cubes, &grow_front)) return ws;
+        if (const int ws = region_walk<kWalkRestore, Shape>(w, B, R, w.now.root, s.root, P, &grow_cubes, &grow_front)) return ws;
         if (!grow_cubes && !grow_front) break;
         if (grow_cubes > want_cubes) want_cubes = std::max(grow_cubes, 2 * want_cubes);
         if (grow_front > want_front) want_front = std::max(grow_front, 2 * want_front);
@@ -717,16 +764,21 @@ int world_restore_region(och_world &w, uint64_t snapshot, const char *who, const
 
 constexpr uint64_t kRestoreCubes = 1u << 16, kRestoreFront = 1u << 14;   // a restore's first buffers, at most
 
+RegionClip region_clip(const och::BoxCubes &C, int depth)
+{
+    RegionClip clip;
+    clip.box = region_world_box(C);
+    clip.whole = C.top == depth;
+    clip.want_cubes = std::min<uint64_t>(C.n_cubes, kRestoreCubes);
+    for (int h = 0; h <= depth; ++h) clip.want_front = std::max(clip.want_front, std::min<uint64_t>(C.cells[h], kRestoreFront));
+    return clip;
+}
+
 int world_restore_box(och_world &w, uint64_t snapshot, const int32_t lo[3], const int32_t hi[3], och_region_stats *out)
 {
     const och::BoxCubes C = och::box_cube_counts(lo, hi, w.depth);
-    RegionClip clip;
-    clip.box = region_world_box(C);
-    clip.whole = C.top == w.depth;
-    clip.want_cubes = std::min<uint64_t>(C.n_cubes, kRestoreCubes);
-    for (int h = 0; h <= w.depth; ++h) clip.want_front = std::max(clip.want_front, std::min<uint64_t>(C.cells[h], kRestoreFront));
     const RegionBox B{{C.lo[0], C.lo[1], C.lo[2]}, {C.hi[0], C.hi[1], C.hi[2]}};
-    return world_restore_region(w, snapshot, "och_world_restore_box", B, clip, region_stats(C), out);
+    return world_restore_region(w, snapshot, "och_world_restore_box", B, region_clip(C, w.depth), region_stats(C), out);
 }
 
 // A ball against a tree of `depth`, on the host: its clipped axis box, what the
@@ -765,6 +817,17 @@ BallPlan ball_plan(const int32_t c2[3], uint32_t diameter, int depth)
     const double area = 1.25 * pi * (double)diameter * (double)diameter + 64.0;
     b.cubes = std::min<uint64_t>(sum, area < 1e18 ? (uint64_t)area : ~(uint64_t)0);
     return b;
+}
+
+RegionClip region_clip(const BallPlan &C, int depth)
+{
+    RegionClip clip;
+    clip.box = C.box;
+    clip.box.any = C.box.any && C.root != 0;
+    clip.whole = C.root == 2;
+    clip.want_cubes = std::min(C.cubes, kRestoreCubes);
+    for (int H = 1; H <= depth; ++H) clip.want_front = std::max(clip.want_front, std::min(C.cells[H], kRestoreFront));
+    return clip;
 }
 
 och_region_stats region_stats(const WorldBox &b)
@@ -851,13 +914,8 @@ int world_restore_sphere(och_world &w, uint64_t snapshot, const int32_t c2[3], u
 {
     if (const char *range = och::ball_range_error(c2, diameter)) return och::fail(OCH_E_INVALID, "och_world_restore_sphere: %s", range);
     const BallPlan C = ball_plan(c2, diameter, w.depth);
-    RegionClip clip;
-    clip.box = C.box;
-    clip.box.any = C.box.any && C.root != 0;
-    clip.whole = C.root == 2;
-    clip.want_cubes = std::min(C.cubes, kRestoreCubes);
-    for (int H = 1; H <= w.depth; ++H) clip.want_front = std::max(clip.want_front, std::min(C.cells[H], kRestoreFront));
-    return world_restore_region(w, snapshot, "och_world_restore_sphere", och::make_ball(c2, diameter), clip, region_stats(C.box), out);
+    return world_restore_region(w, snapshot, "och_world_restore_sphere", och::make_ball(c2, diameter), region_clip(C, w.depth),
+                                region_stats(C.box), out);
 }
 
 }  // namespace

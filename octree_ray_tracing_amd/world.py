@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HostPool, OchError, call
-from ._marshal import ScopedHandle, host_array, host_pool_result, nodes_arg, records_arg, struct_dict
+from ._marshal import ScopedHandle, host_array, host_pool_result, nodes_arg, records_arg, struct_dict, u32_arg, when_arg
 from .builder import VOXELS_GRID_U8, NodePool, _ball_args, _box_args, _capacity, _read_box_args
 from .tracer import HOctree
 
@@ -23,6 +23,7 @@ class World(ScopedHandle):
     and flush() show it, download() gives the canonical pool, compact() drops what strokes left behind;
     fill_box() and restore_box() set or restore a whole box at a cost that follows its surface;
     fill_sphere() and restore_sphere() do the same for a ball;
+    paint_box() and paint_sphere() change only the voxels that are, or are not, one id (paint, fill-under, replace);
     at() and read_box() ask it what it holds without a download, tighten() makes its box exact;
     snapshot(), checkout() and release() remember and restore earlier states (UndoStack, below), diff()
     gives what changed between two of them."""
@@ -274,6 +275,35 @@ class World(ScopedHandle):
         c2, d = _ball_args(centre2, diameter, "World.restore_sphere")
         st = _lib.RegionStats()
         call("och_world_restore_sphere", h, s, c2, d, C.byref(st))
+        return struct_dict(st)
+
+    # -- conditional strokes (och_world_paint_box / och_world_paint_sphere)
+
+    def paint_box(self, lo, hi, id: int, when: int = _lib.WHEN_IS_NOT, match: int = 0) -> dict:
+        """One stroke: inside the box lo <= (x, y, z) < hi a voxel v becomes id where v != match (when =
+        WHEN_IS_NOT) or v == match (WHEN_IS), and stays otherwise, as edit(select_records(...)) of the box's
+        grid would leave the world, without reading it (och_world_paint_box).  The defaults paint the solid
+        voxels; (WHEN_IS, 0) fills only the empty ones; (WHEN_IS, m) replaces material m, with id 0 erases
+        it; (WHEN_IS_NOT, m) with id 0 keeps only m.  The cost follows the box's surface and the distinct
+        nodes under it.  Returns {"cubes", "cells", "nodes", "new_ids", "lo", "hi"}.  OchError CAPACITY
+        leaves the world unchanged: compact() and retry."""
+        h = self._open("paint_box")
+        lo, hi = _box_args(lo, hi, "World.paint_box")
+        id, match = u32_arg(id, "World.paint_box", "id"), u32_arg(match, "World.paint_box", "match")
+        when = when_arg(when, "World.paint_box")
+        st = _lib.PaintStats()
+        call("och_world_paint_box", h, lo, hi, when, match, id, C.byref(st))
+        return struct_dict(st)
+
+    def paint_sphere(self, centre2, diameter: int, id: int, when: int = _lib.WHEN_IS_NOT, match: int = 0) -> dict:
+        """paint_box for a round brush (och_world_paint_sphere): centre2 and diameter as fill_sphere takes
+        them, the predicate and the returned dict as paint_box'."""
+        h = self._open("paint_sphere")
+        c2, d = _ball_args(centre2, diameter, "World.paint_sphere")
+        id, match = u32_arg(id, "World.paint_sphere", "id"), u32_arg(match, "World.paint_sphere", "match")
+        when = when_arg(when, "World.paint_sphere")
+        st = _lib.PaintStats()
+        call("och_world_paint_sphere", h, c2, d, when, match, id, C.byref(st))
         return struct_dict(st)
 
 

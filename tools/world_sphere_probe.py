@@ -29,7 +29,7 @@ centre in voxels and its diameter in voxels (include/och_gpu.h).
 
 Also recorded: each sphere stroke's OCH_BUILD_TRACE phase lines, its stats and the ids it consumed.
 
-python tools/world_sphere_probe.py [--out profiles/world_sphere/probe.json] [--reps 7]
+python tools/world_sphere_probe.py [--out profiles/world_sphere/probe.json] [--reps 7] [--arms brush,ball512]
 """
 from __future__ import annotations
 
@@ -56,6 +56,7 @@ def main():
     ap.add_argument("--depth", type=int, default=12)
     ap.add_argument("--limit", type=int, default=300, help="seconds for the set-up and for each group of arms")
     ap.add_argument("--out", default="profiles/world_sphere/probe.json")
+    ap.add_argument("--arms", default="brush,ball512,clear2047,restore", help="the groups of arms to run, comma-separated")
     a = ap.parse_args()
 
     import torch
@@ -71,6 +72,9 @@ def main():
     watchdog()
     torch.cuda.set_device(0)
     depth, dim = a.depth, 1 << a.depth
+    groups = set(a.arms.split(","))
+    if not groups <= {"brush", "ball512", "clear2047", "restore"}:
+        raise SystemExit(f"world_sphere_probe: --arms names brush, ball512, clear2047 and restore, not {a.arms!r}")
     res = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "warmup": a.warmup,
            "clock": "time.perf_counter around the whole step, synchronisation included"}
     outp = Path(a.out)
@@ -169,132 +173,136 @@ def main():
         brush_box = put_and_cut("box", lambda i: world.fill_box(*axis_box(*brush_ball(i)), 1),
                                 lambda i: world.fill_box(*axis_box(*brush_ball(i)), 0))
 
-        c2, d = brush_ball(0)
-        coords = sample(c2, d, 1 << 14)
-        world.checkout(s_terrain)
-        before = world.at(coords)
-        st_put = world.fill_sphere(c2, d, 1)
-        equal = np.array_equal(world.at(coords), at_truth(coords, c2, d, 1, before)) and stats_equal(st_put, c2, d)
-        st_cut = world.fill_sphere(c2, d, 0)
-        equal = equal and np.array_equal(world.at(coords), at_truth(coords, c2, d, 0, before)) and stats_equal(st_cut, c2, d)
-        brush_fill(0), brush_edit(0)
-        equal = equal and roots["fill put"] == roots["edit put"] and roots["fill cut"] == roots["edit cut"]
-        used_before = world.info()["used"]
-        measure("brush", [("fill_sphere+flush", brush_fill), ("edit+flush", brush_edit), ("fill_box+flush", brush_box)],
-                {"equal": bool(equal), "centre2": list(c2), "diameter": d, "records": len(ort.sphere_records(c2, d, 1)),
-                 "put": st_put, "cut": st_cut, "each_time_is": "one put + flush and one cut + flush"})
-        res["brush"]["ids_added_by_the_arms"] = world.info()["used"] - used_before
-        world.checkout(s_terrain)
-        res["brush"]["trace_put"] = traced(lambda: world.fill_sphere(c2, d, 1))
-        res["brush"]["trace_cut"] = traced(lambda: world.fill_sphere(c2, d, 0))
-        world.checkout(s_terrain)
-        res["brush"]["trace_edit_put"] = traced(lambda: world.edit(ort.sphere_records(c2, d, 1)))
-        save()
+        if "brush" in groups:
+            c2, d = brush_ball(0)
+            coords = sample(c2, d, 1 << 14)
+            world.checkout(s_terrain)
+            before = world.at(coords)
+            st_put = world.fill_sphere(c2, d, 1)
+            equal = np.array_equal(world.at(coords), at_truth(coords, c2, d, 1, before)) and stats_equal(st_put, c2, d)
+            st_cut = world.fill_sphere(c2, d, 0)
+            equal = equal and np.array_equal(world.at(coords), at_truth(coords, c2, d, 0, before)) and stats_equal(st_cut, c2, d)
+            brush_fill(0), brush_edit(0)
+            equal = equal and roots["fill put"] == roots["edit put"] and roots["fill cut"] == roots["edit cut"]
+            used_before = world.info()["used"]
+            measure("brush", [("fill_sphere+flush", brush_fill), ("edit+flush", brush_edit), ("fill_box+flush", brush_box)],
+                    {"equal": bool(equal), "centre2": list(c2), "diameter": d, "records": len(ort.sphere_records(c2, d, 1)),
+                     "put": st_put, "cut": st_cut, "each_time_is": "one put + flush and one cut + flush"})
+            res["brush"]["ids_added_by_the_arms"] = world.info()["used"] - used_before
+            world.checkout(s_terrain)
+            res["brush"]["trace_put"] = traced(lambda: world.fill_sphere(c2, d, 1))
+            res["brush"]["trace_cut"] = traced(lambda: world.fill_sphere(c2, d, 0))
+            world.checkout(s_terrain)
+            res["brush"]["trace_edit_put"] = traced(lambda: world.edit(ort.sphere_records(c2, d, 1)))
+            save()
 
         # ---- the diameter-512 ball across the surface
-        c2, d = (2 * c, 2 * c, 2 * top), 512
-        lo, hi = axis_box(c2, d)
-        ax = [torch.arange(int(l), int(h), dtype=torch.int64, device="cuda") for l, h in zip(lo, hi)]
-        off = [(2 * v + 1 - m) ** 2 for v, m in zip(ax, c2)]
-        inside = (off[2][:, None, None] + off[1][None, :, None] + off[0][None, None, :]) <= d * d
-        z, y, x = torch.nonzero(inside, as_tuple=True)
-        del inside
-        records = torch.stack([x + lo[0], y + lo[1], z + lo[2], torch.ones_like(x)], -1).to(torch.int32).contiguous()
-        del x, y, z
-        coords = sample(c2, d)
-        world.checkout(s_terrain)
-        before = world.at(coords)
-        used = world.info()["used"]
-        st = world.fill_sphere(c2, d, 1)
-        ids_fill = world.info()["used"] - used
-        root_fill = world.info()["root"]
-        equal = np.array_equal(world.at(coords), at_truth(coords, c2, d, 1, before)) and stats_equal(st, c2, d)
-        world.checkout(s_terrain)
-        used = world.info()["used"]
-        world.edit(records)
-        equal = equal and world.info()["root"] == root_fill
-
-        def ball_fill(i):
+        if "ball512" in groups:
+            c2, d = (2 * c, 2 * c, 2 * top), 512
+            lo, hi = axis_box(c2, d)
+            ax = [torch.arange(int(l), int(h), dtype=torch.int64, device="cuda") for l, h in zip(lo, hi)]
+            off = [(2 * v + 1 - m) ** 2 for v, m in zip(ax, c2)]
+            inside = (off[2][:, None, None] + off[1][None, :, None] + off[0][None, None, :]) <= d * d
+            z, y, x = torch.nonzero(inside, as_tuple=True)
+            del inside
+            records = torch.stack([x + lo[0], y + lo[1], z + lo[2], torch.ones_like(x)], -1).to(torch.int32).contiguous()
+            del x, y, z
+            coords = sample(c2, d)
             world.checkout(s_terrain)
-            return clocked(lambda: world.fill_sphere(c2, d, 1))
-
-        def ball_edit(i):
+            before = world.at(coords)
+            used = world.info()["used"]
+            st = world.fill_sphere(c2, d, 1)
+            ids_fill = world.info()["used"] - used
+            root_fill = world.info()["root"]
+            equal = np.array_equal(world.at(coords), at_truth(coords, c2, d, 1, before)) and stats_equal(st, c2, d)
             world.checkout(s_terrain)
-            return clocked(lambda: world.edit(records))
+            used = world.info()["used"]
+            world.edit(records)
+            equal = equal and world.info()["root"] == root_fill
 
-        measure("ball512", [("fill_sphere", ball_fill), ("edit_device", ball_edit)],
-                {"equal": bool(equal), "centre2": list(c2), "diameter": d, "records": int(records.shape[0]),
-                 "record_bytes": int(records.shape[0]) * 16, "stats": st, "ids_first_fill": ids_fill,
-                 "ids_edit_after_fill": world.info()["used"] - used})
-        world.checkout(s_terrain)
-        res["ball512"]["trace"] = traced(lambda: world.fill_sphere(c2, d, 1))
-        del records
-        save()
+            def ball_fill(i):
+                world.checkout(s_terrain)
+                return clocked(lambda: world.fill_sphere(c2, d, 1))
+
+            def ball_edit(i):
+                world.checkout(s_terrain)
+                return clocked(lambda: world.edit(records))
+
+            measure("ball512", [("fill_sphere", ball_fill), ("edit_device", ball_edit)],
+                    {"equal": bool(equal), "centre2": list(c2), "diameter": d, "records": int(records.shape[0]),
+                     "record_bytes": int(records.shape[0]) * 16, "stats": st, "ids_first_fill": ids_fill,
+                     "ids_edit_after_fill": world.info()["used"] - used})
+            world.checkout(s_terrain)
+            res["ball512"]["trace"] = traced(lambda: world.fill_sphere(c2, d, 1))
+            del records
+            save()
 
         # ---- the diameter-2047 ball cleared
-        c2, d = (2 * c, 2 * c, 2 * top), 2047
-        coords = sample(c2, d)
-        world.checkout(s_terrain)
-        before = world.at(coords)
-        used = world.info()["used"]
-        st = world.fill_sphere(c2, d, 0)
-        ids_clear = world.info()["used"] - used
-        equal = np.array_equal(world.at(coords), at_truth(coords, c2, d, 0, before)) and stats_equal(st, c2, d)
-        equal = equal and int((before != 0).sum()) > 1000          # the ball does hold terrain
-
-        def clear(i):
+        if "clear2047" in groups:
+            c2, d = (2 * c, 2 * c, 2 * top), 2047
+            coords = sample(c2, d)
             world.checkout(s_terrain)
-            return clocked(lambda: world.fill_sphere(c2, d, 0))
+            before = world.at(coords)
+            used = world.info()["used"]
+            st = world.fill_sphere(c2, d, 0)
+            ids_clear = world.info()["used"] - used
+            equal = np.array_equal(world.at(coords), at_truth(coords, c2, d, 0, before)) and stats_equal(st, c2, d)
+            equal = equal and int((before != 0).sum()) > 1000          # the ball does hold terrain
 
-        measure("clear2047", [("fill_sphere", clear)],
-                {"equal": bool(equal), "centre2": list(c2), "diameter": d, "stats": st, "ids_first_clear": ids_clear,
-                 "the_parents_record_list": {"records": 4_400_000_000, "bytes": 71_000_000_000}})
-        world.checkout(s_terrain)
-        res["clear2047"]["trace"] = traced(lambda: world.fill_sphere(c2, d, 0))
-        save()
+            def clear(i):
+                world.checkout(s_terrain)
+                return clocked(lambda: world.fill_sphere(c2, d, 0))
+
+            measure("clear2047", [("fill_sphere", clear)],
+                    {"equal": bool(equal), "centre2": list(c2), "diameter": d, "stats": st, "ids_first_clear": ids_clear,
+                     "the_parents_record_list": {"records": 4_400_000_000, "bytes": 71_000_000_000}})
+            world.checkout(s_terrain)
+            res["clear2047"]["trace"] = traced(lambda: world.fill_sphere(c2, d, 0))
+            save()
 
         # ---- restore: the brush ball back as it was before the stroke
-        c2, d = brush_ball(0)
-        lo, hi = axis_box(c2, d)
-        brush = ort.sphere_records(c2, d, 1)
-        world.checkout(s_terrain)
-        world.edit(brush)
-        s_brush = world.snapshot()
-        kept = {}
-        at = torch.from_numpy(brush[:, :3].astype(np.int64) - np.asarray(lo, np.int64)).cuda()
-
-        def restore(i):
-            world.checkout(s_brush)
-            world.flush(pool)
-            t = clocked(lambda: (kept.__setitem__("stats", world.restore_sphere(s_terrain, c2, d)), world.flush(pool)))
-            kept["root restore"] = world.info()["root"]
-            return t
-
-        def paint_back(i):
+        if "restore" in groups:
+            c2, d = brush_ball(0)
+            lo, hi = axis_box(c2, d)
+            brush = ort.sphere_records(c2, d, 1)
             world.checkout(s_terrain)
-            t1 = clocked(lambda: kept.__setitem__("grid", world.read_box(lo, hi, np.uint32, device=True)))
-            world.checkout(s_brush)
-            world.flush(pool)
+            world.edit(brush)
+            s_brush = world.snapshot()
+            kept = {}
+            at = torch.from_numpy(brush[:, :3].astype(np.int64) - np.asarray(lo, np.int64)).cuda()
 
-            def undo():
-                back = torch.from_numpy(brush.view(np.int32)).cuda()
-                back[:, 3] = kept["grid"][at[:, 2], at[:, 1], at[:, 0]]     # the grid is indexed [z, y, x]
-                world.edit(back)
+            def restore(i):
+                world.checkout(s_brush)
                 world.flush(pool)
-            t2 = clocked(undo)
-            kept["root paint"] = world.info()["root"]
-            return t1 + t2
+                t = clocked(lambda: (kept.__setitem__("stats", world.restore_sphere(s_terrain, c2, d)), world.flush(pool)))
+                kept["root restore"] = world.info()["root"]
+                return t
 
-        restore(0), paint_back(0)
-        equal = kept["root restore"] == kept["root paint"] == root_terrain
-        used_before = world.info()["used"]
-        measure("restore", [("restore_sphere+flush", restore), ("read_box+edit+flush", paint_back)],
-                {"equal": bool(equal), "stats": kept["stats"]})
-        res["restore"]["ids_added_by_the_arms"] = world.info()["used"] - used_before
-        world.checkout(s_brush)
-        res["restore"]["trace"] = traced(lambda: world.restore_sphere(s_terrain, c2, d))
-        res["world"]["used_at_the_end"] = world.info()["used"]
-        save()
+            def paint_back(i):
+                world.checkout(s_terrain)
+                t1 = clocked(lambda: kept.__setitem__("grid", world.read_box(lo, hi, np.uint32, device=True)))
+                world.checkout(s_brush)
+                world.flush(pool)
+
+                def undo():
+                    back = torch.from_numpy(brush.view(np.int32)).cuda()
+                    back[:, 3] = kept["grid"][at[:, 2], at[:, 1], at[:, 0]]     # the grid is indexed [z, y, x]
+                    world.edit(back)
+                    world.flush(pool)
+                t2 = clocked(undo)
+                kept["root paint"] = world.info()["root"]
+                return t1 + t2
+
+            restore(0), paint_back(0)
+            equal = kept["root restore"] == kept["root paint"] == root_terrain
+            used_before = world.info()["used"]
+            measure("restore", [("restore_sphere+flush", restore), ("read_box+edit+flush", paint_back)],
+                    {"equal": bool(equal), "stats": kept["stats"]})
+            res["restore"]["ids_added_by_the_arms"] = world.info()["used"] - used_before
+            world.checkout(s_brush)
+            res["restore"]["trace"] = traced(lambda: world.restore_sphere(s_terrain, c2, d))
+            res["world"]["used_at_the_end"] = world.info()["used"]
+            save()
     finally:
         pool.close()
         world.close()
